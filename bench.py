@@ -10,7 +10,9 @@ RCCL all-reduce of P+4 floats per step).  Synthetic band-limited frames, random-
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
 
-Prints ONE JSON line on rank 0.  `value` = whole-job IQ samples/s with inputs resident in HBM.
+Prints ONE JSON line on rank 0.  `value` = whole-job IQ samples/s with inputs resident in HBM, `ms_per_step` = one
+timed step.  `--dump-outputs DIR` also writes what the last timed step left its caller (loss, parameters, gradient,
+AdamW moments) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 `roofline` prices the dominant kernel (the fused fwd+loss+bwd launch).  The step is compute bound
 (~360 flop per algorithmic byte): the bound that binds is the exact-fp32 MFMA / vector rate (157.3
 TFLOP/s, the two are the same rate on gfx950), priced with ALGORITHMIC flops = 2 x 3 x 948 MACs per IQ
@@ -134,6 +136,18 @@ def run_steps(opt, x, t, steps, warmup, count, dist, events=False):
     el = time.perf_counter() - t0
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs])) if events else None
     return el, kern_ms, float(loss.item())
+
+
+def dump_outputs(out_dir, net, opt, loss):
+    """What the timed steps left their caller after the last one, as out_dir/<name>.npy (float32): the step's loss, every parameter of
+    the trained model under its state-dict name, and the optimiser state the next step starts from (the last step's gradient, the
+    AdamW moments).  The inputs are seeded, so two builds run with the same arguments can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    P = opt.backbone.n_flat
+    arrays = {"loss": torch.tensor([loss]), "grad": opt.grad[:P], "exp_avg": opt.exp_avg, "exp_avg_sq": opt.exp_avg_sq}
+    arrays.update({f"param.{k}": v for k, v in net.named_parameters()})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().to("cpu", torch.float32).numpy())
 
 
 class _EpochLoader:
@@ -335,6 +349,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cascade", action="store_true", help="skip the train_dpd (cascade) side figure")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling figures at the reference's global batch sizes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step left the caller (loss, parameters, gradient, AdamW moments) "
+                         "as DIR/<name>.npy (float32; rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -373,6 +390,8 @@ def main():
         x, t = FrameBatch(xs_, ys_, torch.arange(B, device=dev, dtype=torch.int64), T, 1), None
     count = world * B * T * 2
     el, kern_ms, loss = run_steps(opt, x, t, args.steps, args.warmup, count, dist, events=True)
+    if args.dump_outputs and rank == 0:      # before any side figure trains this model further
+        dump_outputs(args.dump_outputs, net, opt, loss)
     el_t = torch.tensor([el], device=dev, dtype=torch.float64)
     if dist is not None:
         dist.all_reduce(el_t, op=dist.ReduceOp.MAX)

@@ -23,6 +23,17 @@ from tests import dp_worker as W
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _PORT = [29540]
+# Processes that may hold the GPU at the same time while the suite runs.  A launch on one GPU opens the device in pytest, in the
+# torch.distributed launcher and in every rank; one that would need more than this skips with the reason (a host that allows fewer
+# processes per device sets ODPD_TEST_GPU_PROCS).
+GPU_PROCS = int(os.environ.get("ODPD_TEST_GPU_PROCS", "16"))
+
+
+def _fits_gpu_procs(world):
+    """skip unless this process, the launcher and `world` ranks (each of them opens the device) may hold the GPU at once"""
+    need = world + 2
+    if need > GPU_PROCS:
+        pytest.skip(f"needs {need} processes on the GPU at once (pytest, the launcher, {world} ranks); ODPD_TEST_GPU_PROCS allows {GPU_PROCS}")
 
 
 def _torchrun(nproc, script_args, env, timeout=600):
@@ -36,6 +47,7 @@ def _torchrun(nproc, script_args, env, timeout=600):
 
 def _ranks(specs, tmp_path, world, comm, backend="gloo", share_gpu=True):
     """the specs run one after the other by `world` ranks of ONE launch: [spec][rank] -> result dict"""
+    _fits_gpu_procs(world)
     job = dict(specs=specs, backend=backend, share_gpu=share_gpu, out=str(tmp_path / "r"))
     path = tmp_path / "job.json"
     path.write_text(json.dumps(job))
@@ -169,10 +181,12 @@ _TWO_GPU_SPECS = [dict(mode="step", bb="dgru", H=13, B=64), dict(mode="epoch", b
                   dict(mode="cascade_epoch", bb="deltagru_tcnskip", H=15, pa_bb="dgru", pa_H=23, B=33, n=400)]
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
 @pytest.mark.parametrize("comm", ["auto", "rccl", "xchg"])
 def test_two_gpus_equal_the_single_process_run(comm, tmp_path, monkeypatch):
     """dgru, cfg 4's vdlstm and cfg 3's cascade on two devices: all-reduced result == single process, replicas bit-identical"""
+    n_gpus = torch.cuda.device_count()
+    if n_gpus < 2:
+        pytest.skip(f"needs 2 GPUs, found {n_gpus}")
     specs = [dict(s, T=40) for s in _TWO_GPU_SPECS]
     got = _ranks(specs, tmp_path, 2, comm, backend="nccl", share_gpu=False)
     for spec, ranks in zip(specs, got):
@@ -207,13 +221,28 @@ def test_eight_ranks_on_one_gpu_equal_the_single_process_run(comm, tmp_path, mon
     """The driver's N = 8 shape on the one-GPU box: eight processes share the device, data plane = the one-shot exchange with a world of
     eight (slot rows of eight sources, both parities, rank-order sums), shards of 8 / 4 / 1 / 0 frames per rank, whole sharded epochs from
     the native loops — against the single-process run."""
+    _fits_gpu_procs(8)
     specs = [dict(mode="step", bb="dgru", H=13, B=64, steps=3), dict(mode="step", bb="dgru", H=13, B=5, steps=2),       # B = 5: ranks 5..7 hold empty shards
              dict(mode="epoch", bb="dgru", H=13, B=64, n=360), dict(mode="epoch", bb="vdlstm", H=13, B=37, n=200)]
+    _many_ranks_equal_the_single_process_run(8, comm, specs, tmp_path, monkeypatch)
+
+
+@pytest.mark.parametrize("comm", ["xchg", "xchg_shm"])
+def test_three_ranks_on_one_gpu_equal_the_single_process_run(comm, tmp_path, monkeypatch):
+    """The same comparisons with a world of three (an odd world: slot rows of three sources, uneven shards of 22 / 21 / 21 frames and an
+    empty one, B = 2: rank 2); it also runs where ODPD_TEST_GPU_PROCS is too small for the eight-rank launch."""
+    _fits_gpu_procs(3)
+    specs = [dict(mode="step", bb="dgru", H=13, B=64, steps=3), dict(mode="step", bb="dgru", H=13, B=2, steps=2),
+             dict(mode="epoch", bb="dgru", H=13, B=64, n=360), dict(mode="epoch", bb="vdlstm", H=13, B=37, n=200)]
+    _many_ranks_equal_the_single_process_run(3, comm, specs, tmp_path, monkeypatch)
+
+
+def _many_ranks_equal_the_single_process_run(world, comm, specs, tmp_path, monkeypatch):
     if comm == "xchg":
-        specs.append(dict(mode="cascade_epoch", bb="deltagru_tcnskip", H=15, pa_bb="dgru", pa_H=23, B=32, n=170))
+        specs = specs + [dict(mode="cascade_epoch", bb="deltagru_tcnskip", H=15, pa_bb="dgru", pa_H=23, B=32, n=170)]
     specs = [dict(s, T=40) for s in specs]
-    got = _ranks(specs, tmp_path, 8, comm)
+    got = _ranks(specs, tmp_path, world, comm)
     for spec, ranks in zip(specs, got):
         ref = _single(spec, monkeypatch)
-        assert len(ranks) == 8
+        assert len(ranks) == world
         _check(ranks, ref, comm, _name(spec))

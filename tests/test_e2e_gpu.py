@@ -628,12 +628,14 @@ def test_registry_backbone_without_kernels_trains_through_the_api(tiny_workdir, 
     assert f"_M_{bb.upper()}_H_{H}_" in os.path.basename(res["model_path"])
 
 
-def test_configuration_outside_the_kernel_envelope_trains_through_the_api(workdir):
+def test_configuration_outside_the_kernel_envelope_trains_through_the_api(workdir, monkeypatch):
     """a pgjanet with 40 hidden units is beyond the HIP kernels: CoreModel builds the ATen restatement (backbones/wide.py) with
     a warning and the same Project flow runs — train_pa of a wide PA, then train_dpd of a kernel-backed DPD (HIP autograd
     bridge) through that ATen PA with torch.optim.AdamW."""
     import warnings
     import opendpd_amd as od
+    from opendpd_amd.backbones import wide
+    monkeypatch.setattr(wide, "_warned", set())      # the warning comes once per process: another test may have built this model
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         kw = dict(dataset_name="DPA_200MHz", PA_backbone="pgjanet", PA_hidden_size=40, frame_length=50, batch_size=256, lr=2e-3, seed=0,

@@ -1,10 +1,9 @@
-"""Host metrics and framing against known answers produced by the reference (tests/golden/metrics_framing.npz and,
-when the reference checkout with its bundled datasets is present, the dataset-level numbers of BASELINE.md §2)."""
+"""Host metrics and framing against known answers produced by the reference (tests/golden/metrics_framing.npz and the
+dataset-level numbers of BASELINE.md §2 on the bundled datasets, stored under tests/golden)."""
 import json
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from opendpd_amd import data, metrics
@@ -34,10 +33,23 @@ def test_framing_and_segments():
     assert np.array_equal(torch.randperm(22991)[:16].numpy(), g["perm_head_22991"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/datasets/DPA_200MHz"), reason="reference datasets not present")
-def test_dataset_level_known_answers():
+_DATASET_FIXTURES = {"DPA_200MHz": "dpa200_dataset.npz", "APA_200MHz": "apa200_dataset.npz", "APA_200MHz_b": "apa200b_dataset.npz"}
+
+
+def test_dataset_level_known_answers(tmp_path, monkeypatch):
+    """the bundled datasets (stored as arrays in tests/golden/*_dataset.npz) written back as the split CSVs + spec.json that
+    data.load_dataset reads"""
+    import pandas as pd
     ans = json.load(open(os.path.join(GOLDEN, "dataset_known_answers.json")))
-    os.environ["OPENDPD_DATASETS"] = "/root/reference/datasets"
+    assert sorted(ans) == sorted(_DATASET_FIXTURES)
+    for ds, fx in _DATASET_FIXTURES.items():
+        d = dict(np.load(os.path.join(GOLDEN, fx)))
+        out = tmp_path / "datasets" / ds
+        out.mkdir(parents=True)
+        (out / "spec.json").write_text(str(d.pop("spec")))
+        for k, v in d.items():
+            pd.DataFrame(v, columns=["I", "Q"]).to_csv(out / f"{k}.csv", index=False)
+    monkeypatch.setenv("OPENDPD_DATASETS", str(tmp_path / "datasets"))
     for ds, ref in ans.items():
         spec = data.load_spec(dataset_name=ds)
         Xtr, ytr, _, _, Xte, yte = data.load_dataset(dataset_name=ds)
