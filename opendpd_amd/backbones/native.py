@@ -68,7 +68,11 @@ def init_linear(lin, weight="xavier"):
 
 
 class _BackboneFn(torch.autograd.Function):
-    """y = backbone(x) through odpd_backbone_fwd / odpd_backbone_bwd."""
+    """y = backbone(x) through odpd_backbone_fwd / odpd_backbone_bwd.
+
+    The kernel-selection knobs (odpd_set_tuning) choose the kernel, and with it the checkpoint layout, at each of the two calls, and the
+    checkpoint carries no record of the layout it was written in.  So the backward refuses to run when odpd_tuning_generation moved since
+    its forward wrote the checkpoints.  The rule is deliberately conservative: any movement refuses, also a knob set and then set back."""
 
     @staticmethod
     def forward(ctx, x, mod, grad_mode, *params):
@@ -86,9 +90,11 @@ class _BackboneFn(torch.autograd.Function):
             # and backward of THIS call to them (include/opendpd_hip.h: ODPD_FLAG_NEED_DX)
             mod.desc.flags = (mod.desc.flags & ~_lib.FLAG_NEED_DX) | (_lib.FLAG_NEED_DX if ctx.needs_input_grad[0] else 0)
         ctx.flags = mod.desc.flags
+        ctx.generation = None
         y = torch.empty_like(x)
         ckpt = None
         if need_grad:
+            ctx.generation = int(lib.odpd_tuning_generation())      # (before the size query: the layout is the one of this generation)
             n = lib.odpd_ckpt_floats(C.byref(mod.desc), B, T)
             _lib.check(0 if n >= 0 else int(n), "odpd_ckpt_floats")
             ckpt = torch.empty(max(int(n), 1), dtype=torch.float32, device=x.device)
@@ -106,6 +112,12 @@ class _BackboneFn(torch.autograd.Function):
         mod = ctx.mod
         x, ckpt, flat = ctx.saved_tensors
         B, T = x.shape[0], x.shape[1]
+        if ctx.generation is not None and int(lib.odpd_tuning_generation()) != ctx.generation:
+            if mod.dx_needs_flag:
+                mod.desc.flags &= ~_lib.FLAG_NEED_DX       # (as after a backward that ran: nothing stale for the next user of the descriptor)
+            raise RuntimeError(f"{mod.backbone_name}: the kernel-selection knobs (odpd_set_tuning) changed between forward and backward; "
+                               "the checkpoints of the forward may be laid out for another kernel, so no gradients were written. "
+                               "Run the forward again under the current knobs.")
         dy = dy.contiguous().float()
         need_dx = ctx.needs_input_grad[0]
         need_w = any(ctx.needs_input_grad[3:])

@@ -143,7 +143,7 @@ extern "C" int odpd_set_tuning(const char* key, int64_t value) {
     if (!strcmp(key, "s16x")) { tuning().s16x = (int)value; ++g_tuning_generation; return 0; }
     if (!strcmp(key, "s16x_train")) { tuning().s16x_train = (int)value; ++g_tuning_generation; return 0; }
     if (!strcmp(key, "lstm_pack")) { tuning().lstm_pack = (int)value; return 0; }      // (same buffers either way)
-    if (!strcmp(key, "qat_u3")) { tuning().qat_u3 = (int)value; return 0; }            // (same buffers either way)
+    if (!strcmp(key, "qat_u3")) { tuning().qat_u3 = (int)value; ++g_tuning_generation; return 0; }   // (same buffer sizes, but the slot count maps units into each checkpoint record)
     return ODPD_EINVAL;
 }
 extern "C" int64_t odpd_tuning_generation(void) { return g_tuning_generation; }

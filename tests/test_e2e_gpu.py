@@ -751,6 +751,39 @@ def test_baseline_config_3_epoch_on_apa_matches_reference_log(apa_workdir, steps
     PA the REFERENCE trained (its state dict is a fixture), 919 steps of 64 x 200 frames through the cascade step,
     against the row the reference logged (tests/golden/ref_runs_apa.json).  Thresholded model: rounding-level differences
     flip a few delta decisions over 919 steps, hence dB-level tolerances on the metrics."""
+    _baseline_config_3(steps_seen)
+
+
+def test_baseline_config_3_on_chained_launches_matches_reference_log(apa_workdir, steps_seen):
+    """config 3 once more with the one-launch cascade step switched off (knob "cascade_one_launch" = 0): every step as the chained launches
+    (DPD forward, frozen-PA forward + loss + dL/du, DPD backward) that serve batches above 256 frames or frames longer than LDS holds — held to
+    the same reference row and the same bounds"""
+    _on_chained_launches(lambda: _baseline_config_3(steps_seen), steps_seen)
+
+
+def _on_chained_launches(run, steps_seen):
+    from opendpd_amd import _lib
+    lib = _lib.load()
+
+    def one_launch_rows():
+        """the one-launch step's rows for the epoch's batch shape, asked in train mode (run_dpd / the validation pass leave a quantised
+        DPD's descriptor in eval mode, which the one-launch step never serves)"""
+        opt = steps_seen["optimizer"]
+        opt.net.train()
+        for bb in (opt.backbone, opt.pa):
+            if hasattr(bb, "sync_mode"):
+                bb.sync_mode()
+        return opt.cascade_one_launch(64, 200, torch.device("cuda"))
+    try:
+        assert lib.odpd_set_tuning(b"cascade_one_launch", 0) == 0
+        run()
+        assert one_launch_rows() is None          # (the epoch did take the chained launches)
+    finally:
+        lib.odpd_set_tuning(b"cascade_one_launch", 1)
+    assert one_launch_rows() is not None          # (... and only because of the knob)
+
+
+def _baseline_config_3(steps_seen):
     import opendpd_amd as od
     ref = json.load(open(os.path.join(GOLDEN, "ref_runs_apa.json")))["config3_apa200"]
     m = dict(np.load(os.path.join(GOLDEN, "ref_runs_apa_models.npz")))
@@ -859,7 +892,8 @@ def _check_first_steps(key, losses, n_exact, rel_exact=1e-6, rel_all=2e-3):
 
 @pytest.fixture
 def steps_seen(monkeypatch):
-    """per-step losses of the (one) training epoch a test runs: FusedAdamW.last_epoch_losses of the optimiser net_train was given"""
+    """per-step losses of the (one) training epoch a test runs: FusedAdamW.last_epoch_losses of the optimiser net_train was given (and that
+    optimiser)"""
     from opendpd_amd import project
     seen = {}
     inner = project.net_train
@@ -867,6 +901,7 @@ def steps_seen(monkeypatch):
     def spy(log, net, loader, optimizer, *a, **k):
         out = inner(log, net, loader, optimizer, *a, **k)
         seen["losses"] = optimizer.last_epoch_losses
+        seen["optimizer"] = optimizer
         return out
     monkeypatch.setattr(project, "net_train", spy)
     return seen
@@ -877,6 +912,16 @@ def test_baseline_config_5_qat_epoch_on_apa_matches_reference_log(apa_workdir, s
     the REFERENCE trained, 919 steps of 64 x 200, against the row the reference logged (tests/golden/ref_runs_qat.json,
     oracle/gen_run_anchor_qat.py).  The quantised cell is bit-exact per step (tests/test_quant_gpu.py); the float PA in the loop
     differs at rounding level, which can move a value across a quantisation boundary: dB-level tolerances."""
+    _baseline_config_5(steps_seen)
+
+
+def test_baseline_config_5_on_chained_launches_matches_reference_log(apa_workdir, steps_seen):
+    """config 5 with the one-launch cascade step switched off ("cascade_one_launch" = 0): the chained launches against the same reference
+    row and the same bounds"""
+    _on_chained_launches(lambda: _baseline_config_5(steps_seen), steps_seen)
+
+
+def _baseline_config_5(steps_seen):
     import opendpd_amd as od
     ref = json.load(open(os.path.join(GOLDEN, "ref_runs_qat.json")))
     m = dict(np.load(os.path.join(GOLDEN, "ref_runs_apa_models.npz")))

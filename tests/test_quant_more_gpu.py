@@ -181,8 +181,8 @@ def test_three_unit_slots_on_16_bit_grids_agree_with_four_to_the_summation_order
     assert rel_err(outs[0][1], outs[1][1]) < 1e-3 and rel_err(outs[0][2], outs[1][2]) < 1e-3
 
 
-def _w8a8_against_the_oracle(bb, H, B, T):
-    from oracle.oracle import Oracle, make_model
+def _w8a8_model(bb, H, B, T):
+    """the seeded W8A8 model of _w8a8_against_the_oracle and its (x, dy)"""
     tres = bb == "deltagru_tcnskip"
     thx, thh = (0.01, 0.05) if tres else (0.0, 0.0)
     torch.manual_seed(H + B + T)
@@ -195,6 +195,18 @@ def _w8a8_against_the_oracle(bb, H, B, T):
             elif k.endswith("weight") and p.dim() == 2:
                 p.mul_(1.7)
     x, dy = _signal(B, T, B + T)
+    return q, x, dy
+
+
+def _w8a8_against_the_oracle(bb, H, B, T, q=None):
+    """`q`: a model _w8a8_model made for these arguments (default: a fresh one); its parameters come out frozen"""
+    from oracle.oracle import Oracle, make_model
+    tres = bb == "deltagru_tcnskip"
+    thx, thh = (0.01, 0.05) if tres else (0.0, 0.0)
+    if q is None:
+        q, x, dy = _w8a8_model(bb, H, B, T)
+    else:
+        x, dy = _signal(B, T, B + T)
     o = Oracle("f32")
     m = make_model(bb, H, thx, thh, bits_w=8, bits_a=8)
     p = np.concatenate([v.detach().cpu().numpy().reshape(-1) for v in q.parameters()])
