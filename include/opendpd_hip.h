@@ -94,6 +94,13 @@ typedef struct odpd_model {
  * weight_hh_l1, bias_ih_l1, bias_hh_l1, fc_out.weight, fc_out.bias[, dgru: fc_hid.weight, fc_hid.bias]).  Forward / backward only (odpd_backbone_fwd / _bwd); every fused entry point
  * answers ODPD_EUNSUPPORTED and the caller chains forward, loss, backward. */
 #define ODPD_FLAG_TWO_LAYERS 4
+/* the forward starts from a caller-given state h0 (B, H) and the backward may return dL/dh0 (CoreModel.forward(x, h_0): gru.py:45 /
+ * lstm.py:46 — lstm starts h and c both at h0): odpd_backbone_fwd_state / _bwd_state on the lane-per-unit kernels (gru_wide.hip,
+ * lstm_wide.hip) at every hidden size 1 .. 64.  Valid on float gru / dgru / qgru / qgru_amp1 / lstm descriptors of one layer with 1 .. 64
+ * hidden units; on any other descriptor every entry point answers ODPD_EUNSUPPORTED.  With the flag, odpd_ckpt_floats and
+ * odpd_partial_rows(fused = 0) answer the sizes of those kernels; odpd_backbone_fwd / _bwd answer ODPD_EINVAL (use the _state calls); the
+ * fused, framed, epoch, sweep, cascade and frozen-loss entry points answer ODPD_EUNSUPPORTED. */
+#define ODPD_FLAG_INIT_STATE 8
 
 /* loss kinds — project.py:262-272 */
 enum odpd_loss { ODPD_LOSS_L2 = 0, ODPD_LOSS_L1 = 1 };
@@ -158,6 +165,14 @@ int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int T, const f
  * and, if dx != NULL, dL/dx (B,T,2) OVERWRITTEN (needed when the backbone is the PA of a cascade). */
 int odpd_backbone_bwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                       const float* x, const float* dy, const float* ckpt, float* partials, float* dx);
+/* The state route (m->flags & ODPD_FLAG_INIT_STATE; ODPD_EINVAL without the flag).  Forward: y = backbone(x) starting from h0 ((B, H) fp32,
+ * not NULL; lstm: h and c both start at h0); ckpt may be NULL (inference), else it holds odpd_ckpt_floats of the flagged descriptor.
+ * Backward: as odpd_backbone_bwd from the same x, h0 and the forward's ckpt (not NULL); partials, dx and dh0 may each be NULL, not all
+ * three; dh0 ((B, H), OVERWRITTEN) = dL/dh0. */
+int odpd_backbone_fwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
+                            float* y, float* ckpt);
+int odpd_backbone_bwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
+                            const float* dy, const float* ckpt, float* partials, float* dx, float* dh0);
 /* Deterministic second-stage reduction: grad[p] = sum_rows partials[row][p]  (grad OVERWRITTEN or
  * ACCUMULATED if accumulate != 0).  Columns P..P+3 of `partials` carry loss partial sums; their
  * reduction lands in grad[P..P+3] (so `grad` holds P+4 floats). */

@@ -9,7 +9,7 @@ fills two 16-slot tiles)."""
 import torch
 import torch.nn as nn
 
-from .native import NativeBackbone
+from .native import NativeBackbone, H0_IGNORED
 
 MAX_HIDDEN = 14
 
@@ -27,6 +27,7 @@ class _RRUParams(nn.Module):
 
 
 class APNRRU(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "apnrru"
 
     def __init__(self, hidden_size, bias=True):

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from .gru import _check_single_layer
-from .native import NativeBackbone, init_gatewise, init_linear
+from .native import NativeBackbone, init_gatewise, init_linear, H0_IGNORED
 
 
 class _DeltaStats:
@@ -56,6 +56,7 @@ class _GruLayerParams(nn.Module):
 
 
 class _DeltaBase(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     dx_needs_flag = True
 
     def _setup_delta(self, hidden_size, thx, thh):

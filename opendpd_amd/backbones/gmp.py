@@ -6,10 +6,11 @@ is, models.py:26-28: memory_length 11, degree 5 -> 495 parameters).  Kernels: cs
 import torch
 import torch.nn as nn
 
-from .native import NativeBackbone
+from .native import NativeBackbone, H0_IGNORED
 
 
 class GMP(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "gmp"
 
     def __init__(self, memory_length=11, degree=5):

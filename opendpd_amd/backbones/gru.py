@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from .. import _lib
 
-from .native import NativeBackbone, RnnParams, init_gatewise, init_linear
+from .native import NativeBackbone, RnnParams, init_gatewise, init_linear, H0_STATE
 
 
 def _check_layers(num_layers, bidirectional, hidden_size):
@@ -26,6 +26,7 @@ def _check_single_layer(num_layers, bidirectional):
 
 
 class GRU(NativeBackbone):
+    initial_state = H0_STATE      # CoreModel.forward's h_0
     backbone_name = "gru"
 
     def __init__(self, input_size, hidden_size, output_size, num_layers, bidirectional=False, batch_first=True,
@@ -47,6 +48,7 @@ class GRU(NativeBackbone):
 
 
 class DGRU(NativeBackbone):
+    initial_state = H0_STATE      # CoreModel.forward's h_0
     backbone_name = "dgru"
 
     def __init__(self, hidden_size, output_size, num_layers, bidirectional=False, batch_first=True, bias=True):
@@ -68,6 +70,7 @@ class DGRU(NativeBackbone):
 
 class QGRU(NativeBackbone):
     """Float path of backbones/qgru.py (features I,Q,|x|^2,|x|^4)."""
+    initial_state = H0_STATE      # CoreModel.forward's h_0
     backbone_name = "qgru"
 
     def __init__(self, hidden_size, output_size, num_layers, bidirectional=False, batch_first=True, bias=True):

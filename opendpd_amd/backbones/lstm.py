@@ -11,10 +11,11 @@ import torch.nn as nn
 
 from .. import _lib
 from .gru import _check_layers, _check_single_layer
-from .native import NativeBackbone, RnnParams, init_gatewise, init_linear
+from .native import NativeBackbone, RnnParams, init_gatewise, init_linear, H0_IGNORED, H0_STATE
 
 
 class LSTM(NativeBackbone):
+    initial_state = H0_STATE      # CoreModel.forward's h_0
     backbone_name = "lstm"
 
     def __init__(self, input_size, hidden_size, output_size, num_layers, bidirectional=False, batch_first=True,
@@ -36,6 +37,7 @@ class LSTM(NativeBackbone):
 
 
 class VDLSTM(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "vdlstm"
 
     def __init__(self, input_size, hidden_size, output_size, num_layers, window_length=4, stride=1, bidirectional=False,

@@ -7,12 +7,13 @@ registry's reset_parameters() a second time — both draws are kept so that a se
 reference does).  The torch modules are parameter holders only; the arithmetic is csrc/mcldnn.hip (hidden = channels C <= 16)."""
 import torch.nn as nn
 
-from .native import NativeBackbone
+from .native import NativeBackbone, H0_IGNORED
 
 MAX_HIDDEN = 16
 
 
 class MCLDNN(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "mcldnn"
 
     def __init__(self, hidden_size=8):

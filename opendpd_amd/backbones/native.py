@@ -148,12 +148,102 @@ class _BackboneFn(torch.autograd.Function):
         return (dx, None, None) + gparams
 
 
+class _BackboneStateFn(torch.autograd.Function):
+    """y = backbone(x) from the initial state h_0 (1, B, H) through odpd_backbone_fwd_state / odpd_backbone_bwd_state (ODPD_FLAG_INIT_STATE:
+    the lane-per-unit kernels of gru_wide.hip / lstm_wide.hip); the backward also returns dL/dh_0, in h_0's dtype and shape.
+
+    The flag is set on the descriptor for each call and cleared after it.  The backward refuses to run when odpd_tuning_generation moved
+    since its forward, as _BackboneFn's does."""
+
+    @staticmethod
+    def forward(ctx, x, h_0, mod, grad_mode, *params):
+        lib = _lib.load()
+        if not x.is_cuda:
+            raise RuntimeError("opendpd_amd backbones run on a HIP device only (no CPU fallback)")
+        x = x.contiguous().float()
+        B, T = x.shape[0], x.shape[1]
+        h0 = h_0.detach().reshape(B, mod.hidden_size).float().contiguous()      # the kernels run in fp32
+        flat = mod.flat_params()
+        need_grad = grad_mode and any(ctx.needs_input_grad)
+        ctx.generation = None
+        y = torch.empty_like(x)
+        ckpt = None
+        mod.desc.flags |= _lib.FLAG_INIT_STATE
+        try:
+            if need_grad:
+                ctx.generation = int(lib.odpd_tuning_generation())
+                n = lib.odpd_ckpt_floats(C.byref(mod.desc), B, T)
+                _lib.check(0 if n >= 0 else int(n), "odpd_ckpt_floats")
+                ckpt = torch.empty(max(int(n), 1), dtype=torch.float32, device=x.device)
+            rc = lib.odpd_backbone_fwd_state(_lib.stream_ptr(), C.byref(mod.desc), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(h0),
+                                             _lib.ptr(y), _lib.ptr(ckpt))
+        finally:
+            mod.desc.flags &= ~_lib.FLAG_INIT_STATE
+        _lib.check(rc, f"odpd_backbone_fwd_state[{mod.backbone_name}]")
+        ctx.mod = mod
+        ctx.h0_dtype, ctx.h0_shape = h_0.dtype, h_0.shape
+        ctx.save_for_backward(x, h0, ckpt if ckpt is not None else x.new_empty(0), flat)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        mod = ctx.mod
+        x, h0, ckpt, flat = ctx.saved_tensors
+        B, T = x.shape[0], x.shape[1]
+        if ctx.generation is not None and int(lib.odpd_tuning_generation()) != ctx.generation:
+            raise RuntimeError(f"{mod.backbone_name}: the kernel-selection knobs (odpd_set_tuning) changed between forward and backward; "
+                               "the checkpoints of the forward may be laid out for another kernel, so no gradients were written. "
+                               "Run the forward again under the current knobs.")
+        need_dx, need_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_w = any(ctx.needs_input_grad[4:])
+        if not (need_w or need_dx or need_dh0):
+            return (None,) * len(ctx.needs_input_grad)
+        dy = dy.contiguous().float()
+        P = mod.n_flat
+        partials = dx = dh0 = None
+        if need_dx:
+            dx = torch.empty_like(x)
+        if need_dh0:
+            dh0 = torch.empty_like(h0)
+        mod.desc.flags |= _lib.FLAG_INIT_STATE
+        try:
+            if need_w:
+                rows = int(lib.odpd_partial_rows(C.byref(mod.desc), B, T, 0))
+                _lib.check(0 if rows > 0 else rows, "odpd_partial_rows")
+                partials = torch.empty(rows, P + _lib.LOSS_COLS, dtype=torch.float32, device=x.device)
+            rc = lib.odpd_backbone_bwd_state(_lib.stream_ptr(), C.byref(mod.desc), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(h0),
+                                             _lib.ptr(dy), _lib.ptr(ckpt) if ckpt.numel() else None, _lib.ptr(partials), _lib.ptr(dx),
+                                             _lib.ptr(dh0))
+        finally:
+            mod.desc.flags &= ~_lib.FLAG_INIT_STATE
+        _lib.check(rc, f"odpd_backbone_bwd_state[{mod.backbone_name}]")
+        gparams = (None,) * (len(ctx.needs_input_grad) - 4)
+        if need_w:
+            grad = torch.empty(P + _lib.LOSS_COLS, dtype=torch.float32, device=x.device)
+            rc = lib.odpd_reduce_partials(_lib.stream_ptr(), partials.shape[0], P, _lib.ptr(partials), _lib.ptr(grad), 0)
+            _lib.check(rc, "odpd_reduce_partials")
+            gparams = tuple(grad[o:o + n].view(shape) if need else None
+                            for (o, n, shape), need in zip(mod._slices, ctx.needs_input_grad[4:]))
+        if dh0 is not None:
+            dh0 = dh0.view(ctx.h0_shape).to(ctx.h0_dtype)
+        return (dx, dh0, None, None) + gparams
+
+
+# how the reference's backbone treats the h_0 argument of CoreModel.forward (models.py:150-160), per NativeBackbone subclass:
+#   "state"    the initial state of the recurrence (gru.py:45, dgru.py:70, qgru.py, qgru_amp1.py; lstm.py:46: h and c)
+#   "ignored"  never read, or set to None / zeros (deltagru, deltajanet, deltagru_tcnskip, vdlstm, apnrru, mcldnn, gmp, tcnn, rvtdcnn, neuraltx)
+#   "refused"  an initial state the kernels do not take (pgjanet, bojanet, dvrjanet, quantised models)
+H0_STATE, H0_IGNORED, H0_REFUSED = "state", "ignored", "refused"
+
+
 class NativeBackbone(nn.Module):
     """nn.Module whose parameters are views into one flat fp32 buffer consumed by the HIP kernels."""
 
     backbone_name = None
     native = True
     dx_needs_flag = False      # True for the delta backbones (ODPD_FLAG_NEED_DX)
+    initial_state = H0_REFUSED
 
     def _finalize(self, hidden_size, thx=0.0, thh=0.0, bits_w=0, bits_a=0):
         """Call at the end of __init__ once every parameter holder is registered."""
@@ -212,3 +302,17 @@ class NativeBackbone(nn.Module):
 
     def forward(self, x, h_0=None):
         return _BackboneFn.apply(x, self, torch.is_grad_enabled(), *self.parameters())
+
+    def state_refusal(self):
+        """None when this model can start from a given state on the kernels (forward_state), else the reason it cannot."""
+        if self.desc.bits_w > 0 and self.backbone_name != "dvrjanet":      # (dvrjanet: bits_w carries num_dvr_units)
+            return f"quantised '{self.backbone_name}'"
+        if self.initial_state != H0_STATE:
+            return f"'{self.backbone_name}'"
+        if self.desc.flags & _lib.FLAG_TWO_LAYERS:
+            return f"two-layer '{self.backbone_name}'"
+        return None
+
+    def forward_state(self, x, h_0):
+        """y = backbone(x) from the initial state h_0 (1, B, H); h_0 may require grad (the state route, ODPD_FLAG_INIT_STATE)."""
+        return _BackboneStateFn.apply(x, h_0, self, torch.is_grad_enabled(), *self.parameters())

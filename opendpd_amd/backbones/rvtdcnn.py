@@ -6,10 +6,11 @@ Kernels: csrc/rvtdcnn.hip (window 4, 3 channels, 3 x 3 kernel — the only confi
 larger sizes run as the ATen restatement of backbones/extras.py, said aloud like every configuration outside the envelope)."""
 import torch.nn as nn
 
-from .native import NativeBackbone
+from .native import NativeBackbone, H0_IGNORED
 
 
 class RVTDCNN(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "rvtdcnn"
 
     def __init__(self, window_size=4, out_channels=3, kernel_size=3, stride=1, padding=(1, 0), dilation=1, fc_hid_size=6):

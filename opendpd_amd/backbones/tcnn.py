@@ -5,10 +5,11 @@ with PyTorch's default Conv1d initialisation (the reference defines no reset_par
 Kernels: csrc/tcnn.hip."""
 import torch.nn as nn
 
-from .native import NativeBackbone
+from .native import NativeBackbone, H0_IGNORED
 
 
 class TCNN(NativeBackbone):
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "tcnn"
 
     def __init__(self, hidden_channels):
@@ -29,6 +30,7 @@ class NeuralTX(NativeBackbone):
     names, construction order and initialisation as the reference — `reset_parameters()` runs in the constructor AND once more from
     the registry (models.py:144-148), re-drawing the FIR taps and IQ_match while `network` keeps PyTorch's default init.
     Kernels: the NTX instantiation of csrc/tcnn.hip."""
+    initial_state = H0_IGNORED      # CoreModel.forward's h_0
     backbone_name = "neuraltx"
 
     def __init__(self, hidden_channels):

@@ -58,10 +58,17 @@ inline int feat_dim(int bb) {
     default: return 0;
     }
 }
-// models served by the lane-per-unit kernels (gru_wide.hip, lstm_wide.hip, vdlstm_wide.hip, delta_wide.hip: 33 .. 64 hidden units; janet_wide.hip: pgjanet 17 .. 32): forward / backward
-// only — the fused entry points answer ODPD_EUNSUPPORTED for them and the caller chains forward, loss, backward
+// ODPD_FLAG_INIT_STATE: the descriptor asks for the state route (a caller-given initial state), which the lane-per-unit kernels of
+// gru_wide.hip / lstm_wide.hip serve for the float gru / dgru / qgru / qgru_amp1 / lstm of 1 .. 64 hidden units, one layer; every entry point
+// answers ODPD_EUNSUPPORTED for the flag on any other descriptor
+inline bool init_state(const odpd_model_t* m) { return (m->flags & ODPD_FLAG_INIT_STATE) != 0; }
+inline bool init_state_ok(const odpd_model_t* m) { return gru_state_ok(m) || lstm_state_ok(m); }
+// models served by the lane-per-unit kernels (gru_wide.hip, lstm_wide.hip, vdlstm_wide.hip, delta_wide.hip: 33 .. 64 hidden units; janet_wide.hip: pgjanet 17 .. 32;
+// every ODPD_FLAG_INIT_STATE descriptor): forward / backward only — the fused entry points answer ODPD_EUNSUPPORTED for them and the caller chains
+// forward, loss, backward
 inline bool lane_per_unit_model(const odpd_model_t* m) {
-    return gru_wide_ok(m) || lstm_wide_ok(m) || vdlstm_wide_ok(m) || delta_wide_ok(m) || pgjanet_wide_ok(m) || deltajanet_wide_ok(m) || pgjanet_q_ok(m);
+    return init_state(m) || gru_wide_ok(m) || lstm_wide_ok(m) || vdlstm_wide_ok(m) || delta_wide_ok(m) || pgjanet_wide_ok(m) || deltajanet_wide_ok(m) ||
+           pgjanet_q_ok(m);
 }
 // bits_w > 0 selects a quantised model only where one exists (include/opendpd_hip.h, odpd_model_t::bits_w); on every other backbone
 // the descriptor is refused outright — no entry point may answer it with the float kernels on a float parameter layout
@@ -187,11 +194,12 @@ extern "C" int odpd_probe_issue_ns(void* stream, int iters, double* ns_per_wave_
     return (int)hipGetLastError();
 }
 
-extern "C" int odpd_abi_version(void) { return 13; }   // 13: + odpd_probe_issue_ns; 12: + odpd_sweep_* / odpd_train_epoch_sweep / odpd_backbone_fwd_sweep (K runs of one model shape in lockstep: one launch per step carries them all); 11: + ODPD_FLAG_TWO_LAYERS (gru / qgru / qgru_amp1 with two recurrent layers), hidden 33 .. 64 for the GRU family and lstm, bits_w > 0 on lstm / vdlstm (INT_Linear heads); 10: + odpd_xchg_* (one-shot gradient exchange over peer-mapped slots), odpd_clip_optim_step_dp, odpd_comm_kind / _errors; 9: + odpd_cascade_rows, odpd_cascade_fwd_bwd (train_dpd step body in one launch); 8: + odpd_comm_*, odpd_shard_range, odpd_train_epoch_dp (RCCL inside the native step path); 7: quantised gru / dgru / deltagru_tcnskip descriptors (bits_w > 0), QAT hidden <= 32; 3: + odpd_clip_adamw_step_masked, odpd_tuning_generation, backbones 11..13; 4: backbones 14..17; 5: + odpd_framed_train_supported_shape; 6: + odpd_train_epoch_split
+extern "C" int odpd_abi_version(void) { return 13; }   // 13: + odpd_probe_issue_ns; + ODPD_FLAG_INIT_STATE, odpd_backbone_fwd_state / _bwd_state (backward compatible: no existing call changes); 12: + odpd_sweep_* / odpd_train_epoch_sweep / odpd_backbone_fwd_sweep (K runs of one model shape in lockstep: one launch per step carries them all); 11: + ODPD_FLAG_TWO_LAYERS (gru / qgru / qgru_amp1 with two recurrent layers), hidden 33 .. 64 for the GRU family and lstm, bits_w > 0 on lstm / vdlstm (INT_Linear heads); 10: + odpd_xchg_* (one-shot gradient exchange over peer-mapped slots), odpd_clip_optim_step_dp, odpd_comm_kind / _errors; 9: + odpd_cascade_rows, odpd_cascade_fwd_bwd (train_dpd step body in one launch); 8: + odpd_comm_*, odpd_shard_range, odpd_train_epoch_dp (RCCL inside the native step path); 7: quantised gru / dgru / deltagru_tcnskip descriptors (bits_w > 0), QAT hidden <= 32; 3: + odpd_clip_adamw_step_masked, odpd_tuning_generation, backbones 11..13; 4: backbones 14..17; 5: + odpd_framed_train_supported_shape; 6: + odpd_train_epoch_split
 extern "C" const char* odpd_built_arch(void) { return "gfx950"; }
 
 extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
     if (!model_ok(m)) return ODPD_EINVAL;
+    if (init_state(m) && !init_state_ok(m)) return ODPD_EUNSUPPORTED;
     if (family_of(m) == FAM_GRU2) return gru2_ok(m) ? gru2_param_count(m) : lstm2_ok(m) ? lstm2_param_count(m) : (int64_t)ODPD_EUNSUPPORTED;
     if (family_of(m) == FAM_QAT) return qat_s16_param_count(m);
     const int64_t H = m->hidden, F = feat_dim(m->backbone);
@@ -220,6 +228,8 @@ extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
 
 extern "C" int64_t odpd_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
+    if (init_state(m))      // the per-step records of the lane-per-unit kernels, at every hidden size they serve on the state route
+        return !init_state_ok(m) ? (int64_t)ODPD_EUNSUPPORTED : family_of(m) == FAM_LSTM ? lstm_wide_ckpt_floats(m, B, T) : gru_wide_ckpt_floats(m, B, T);
     if (family_of(m) == FAM_TCNN || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN) return 0;   // not recurrent: nothing to checkpoint
     if (family_of(m) == FAM_DVR) return dvrjanet_ckpt_floats(m, B, T);
     if (family_of(m) == FAM_BOJ) return bojanet_ckpt_floats(m, B, T);
@@ -257,6 +267,8 @@ extern "C" int64_t odpd_ckpt_floats(const odpd_model_t* m, int B, int T) {
 
 extern "C" int64_t odpd_partial_rows(const odpd_model_t* m, int B, int T, int fused) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
+    if (init_state(m))
+        return (fused || !init_state_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : family_of(m) == FAM_LSTM ? (int64_t)lstm_wide_rows(m, B) : (int64_t)gru_wide_rows(m, B);
     switch (family_of(m)) {
     case FAM_GRU2: return fused ? (int64_t)ODPD_EUNSUPPORTED : gru2_ok(m) ? (int64_t)gru2_rows(m, B) : lstm2_ok(m) ? (int64_t)lstm2_rows(m, B) : (int64_t)ODPD_EUNSUPPORTED;
     case FAM_GRU:
@@ -328,6 +340,7 @@ extern "C" int64_t odpd_train_workspace_floats(const odpd_model_t* m, int B, int
 extern "C" int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                                  const float* x, float* y, float* ckpt, double* stats) {
     if (!model_ok(m) || !params || !x || !y || B <= 0 || T <= 0) return ODPD_EINVAL;
+    if (init_state(m)) return init_state_ok(m) ? ODPD_EINVAL : ODPD_EUNSUPPORTED;      // (the flag's forward is odpd_backbone_fwd_state)
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.stats = stats;
     switch (family_of(m)) {
@@ -359,6 +372,7 @@ extern "C" int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int
 extern "C" int odpd_backbone_bwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                                  const float* x, const float* dy, const float* ckpt, float* partials, float* dx) {
     if (!model_ok(m) || !params || !x || !dy || B <= 0 || T <= 0 || (!partials && !dx)) return ODPD_EINVAL;
+    if (init_state(m)) return init_state_ok(m) ? ODPD_EINVAL : ODPD_EUNSUPPORTED;      // (the flag's backward is odpd_backbone_bwd_state)
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx;
     switch (family_of(m)) {
@@ -395,6 +409,25 @@ extern "C" int odpd_backbone_bwd(void* stream, const odpd_model_t* m, int B, int
         return qgru_family_bwd((hipStream_t)stream, m, a);
     default: return ODPD_EUNSUPPORTED;
     }
+}
+
+// the state route (ODPD_FLAG_INIT_STATE): the lane-per-unit kernels of gru_wide.hip / lstm_wide.hip at every hidden size 1 .. 64
+extern "C" int odpd_backbone_fwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
+                                       float* y, float* ckpt) {
+    if (!model_ok(m) || !params || !x || !h0 || !y || B <= 0 || T <= 0 || !init_state(m)) return ODPD_EINVAL;
+    if (!init_state_ok(m)) return ODPD_EUNSUPPORTED;
+    SeqArgs a = make_args(m, B, T);
+    a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.h0 = h0;
+    return family_of(m) == FAM_LSTM ? lstm_state_fwd((hipStream_t)stream, m, a) : gru_state_fwd((hipStream_t)stream, m, a);
+}
+extern "C" int odpd_backbone_bwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
+                                       const float* dy, const float* ckpt, float* partials, float* dx, float* dh0) {
+    if (!model_ok(m) || !params || !x || !h0 || !dy || !ckpt || B <= 0 || T <= 0 || (!partials && !dx && !dh0) || !init_state(m))
+        return ODPD_EINVAL;
+    if (!init_state_ok(m)) return ODPD_EUNSUPPORTED;
+    SeqArgs a = make_args(m, B, T);
+    a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx; a.h0 = h0; a.dh0 = dh0;
+    return family_of(m) == FAM_LSTM ? lstm_state_bwd((hipStream_t)stream, m, a) : gru_state_bwd((hipStream_t)stream, m, a);
 }
 
 extern "C" int odpd_train_fwd_bwd(void* stream, const odpd_model_t* m, int loss_kind, int B, int T, int64_t count,
@@ -463,7 +496,7 @@ static bool cascade_dpd_family(const odpd_model_t* m) {
 }
 extern "C" int64_t odpd_cascade_rows(const odpd_model_t* dpd, const odpd_model_t* pa, int B, int T) {
     if (!model_ok(dpd) || !model_ok(pa) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    if (!cascade_dpd_family(dpd) || family_of(pa) != FAM_GRU) return ODPD_EUNSUPPORTED;
+    if (!cascade_dpd_family(dpd) || family_of(pa) != FAM_GRU || init_state(dpd) || init_state(pa)) return ODPD_EUNSUPPORTED;
     // a quantised DPD whose module is in eval() (ODPD_FLAG_EVAL: the 16-bit output quantiser of fc_out is active): the one-launch step
     // only carries the train-mode arithmetic, the chained launches honour the flag — so the step goes to them
     if (family_of(dpd) == FAM_QAT && (dpd->flags & ODPD_FLAG_EVAL)) return ODPD_EUNSUPPORTED;
@@ -474,7 +507,7 @@ extern "C" int odpd_cascade_fwd_bwd(void* stream, const odpd_model_t* dpd, const
                                     const int64_t* frame_idx, int frame_stride, float* partials, double* dpd_stats) {
     if (!model_ok(dpd) || !model_ok(pa) || !dpd_params || !pa_params || !x || !target || !partials || B <= 0 || T <= 0 || count <= 0)
         return ODPD_EINVAL;
-    if (!cascade_dpd_family(dpd) || family_of(pa) != FAM_GRU) return ODPD_EUNSUPPORTED;
+    if (!cascade_dpd_family(dpd) || family_of(pa) != FAM_GRU || init_state(dpd) || init_state(pa)) return ODPD_EUNSUPPORTED;
     CascArgs a{};
     a.thx = dpd->thx; a.thh = dpd->thh; a.stats = dpd_stats; a.bits_w = dpd->bits_w; a.bits_a = dpd->bits_a;
     a.dpd_params = dpd_params; a.pa_params = pa_params; a.x = x; a.target = target; a.partials = partials;
@@ -486,6 +519,7 @@ extern "C" int odpd_cascade_fwd_bwd(void* stream, const odpd_model_t* dpd, const
 namespace {
 // backbones whose fused train kernel addresses frames inside resident streams (SeqArgs::frame_idx)
 inline bool framed_train_ok(const odpd_model_t* m) {
+    if (init_state(m)) return false;      // (ODPD_FLAG_INIT_STATE: forward / backward only, whatever the backbone)
     return (!lane_per_unit_model(m) && family_of(m) == FAM_GRU) || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN;
 }
 // ... for this batch shape: also the one-sequence-per-wave fused kernels of lstm / vdlstm / pgjanet (their large-batch kernels take tensors)
@@ -716,7 +750,7 @@ extern "C" int odpd_train_epoch_split(void* stream, const odpd_model_t* m, int l
         fr->stride <= 0 || batch <= 0 || !params || !grad || !state1 || !state2 || !xbuf || !tbuf || !ybuf || !dybuf || !partials ||
         !loss_scratch || !losses_out || first_step <= 0 || opt_kind > ODPD_OPT_RMSPROP)
         return ODPD_EINVAL;
-    if (fr->sample_format != ODPD_SAMPLES_F32) return ODPD_EUNSUPPORTED;
+    if (fr->sample_format != ODPD_SAMPLES_F32 || init_state(m)) return ODPD_EUNSUPPORTED;
     const int T = fr->frame_length;
     const int64_t P = odpd_param_count(m);
     if (P <= 0) return P < 0 ? (int)P : ODPD_EUNSUPPORTED;
@@ -782,6 +816,7 @@ extern "C" int64_t odpd_sweep_partial_rows(const odpd_model_t* m, int B, int T, 
 }
 extern "C" int64_t odpd_sweep_workspace_floats(const odpd_model_t* m, int B, int T, int flags) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
+    if (init_state(m)) return ODPD_EUNSUPPORTED;
     if (!(flags & ODPD_SWEEP_S16)) return 0;
     return odpd_sweep_s16_supported(m) ? gru_s16_workspace_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
 }

@@ -145,6 +145,9 @@ struct SeqArgs {
     int loss_kind;
     int B, T, H, ngroups, nck;
     int bits_w, bits_a, eval_out;      // quantised heads (lstm): grid widths; eval_out: ODPD_FLAG_EVAL (fc_out's 16-bit output quantiser)
+    // the state route (ODPD_FLAG_INIT_STATE, gru_wide.hip / lstm_wide.hip): (B,H) initial state; (B,H) dL/dh0, nullable (last: no field above moves)
+    const float* h0;
+    float* dh0;
 };
 
 // one run of a lockstep sweep (K independent runs of one model shape advancing together: odpd_train_epoch_sweep, odpd_backbone_fwd_sweep);
@@ -199,6 +202,10 @@ int64_t gru_wide_ckpt_floats(const odpd_model_t* m, int B, int T);
 int gru_wide_rows(const odpd_model_t* m, int B);
 int gru_wide_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_wide_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+// ... and the state route of the same kernels (ODPD_FLAG_INIT_STATE): float gru / dgru / qgru / qgru_amp1 of 1 .. 64 hidden units, one layer
+bool gru_state_ok(const odpd_model_t* m);
+int gru_state_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+int gru_state_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 // gru_layers2.hip: gru / qgru / qgru_amp1 with two recurrent layers (ODPD_FLAG_TWO_LAYERS), both layers in one wave, time-skewed
 bool gru2_ok(const odpd_model_t* m);
 int64_t gru2_param_count(const odpd_model_t* m);
@@ -219,6 +226,10 @@ int64_t lstm_wide_ckpt_floats(const odpd_model_t* m, int B, int T);
 int lstm_wide_rows(const odpd_model_t* m, int B);
 int lstm_wide_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int lstm_wide_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+// ... and its state route (ODPD_FLAG_INIT_STATE): float lstm of 1 .. 64 hidden units, one layer, h and c both starting at h0
+bool lstm_state_ok(const odpd_model_t* m);
+int lstm_state_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+int lstm_state_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 // vdlstm_wide.hip: float vdlstm of 33 .. 64 hidden units (same mapping; window inputs, lambda heads)
 bool vdlstm_wide_ok(const odpd_model_t* m);
 int64_t vdlstm_wide_ckpt_floats(const odpd_model_t* m, int B, int T);

@@ -8,6 +8,12 @@ qgru_amp1 / lstm also two layers of <= 32 units, csrc/gru_layers2.hip, lstm_laye
 <= 32 — gru / dgru / qgru / qgru_amp1 / lstm / vdlstm / deltagru / deltagru_tcnskip / deltajanet: <= 64, csrc/*_wide.hip; pgjanet <= 32 (janet_wide.hip); tcnn, neuraltx <= 64 channels; gmp as the registry builds it; rvtdcnn fc_hid_size <= 32; dvrjanet <= 16 with <= 8 DVR units; bojanet <= 16; apnrru <= 14) and as ATen restatements (backbones/wide.py,
 `native` False, with a warning) beyond it — backbones/wide.py for the hot-path names, backbones/extras.py for the SURVEY §8 f4 ones;
 mcldnn: <= 16 channels.  All 18 registry names are HIP-backed inside their envelopes.  Unknown names raise ValueError (models.py:139-141).
+`h_0` (models.py:150-160) on the kernels: gru / dgru / qgru / qgru_amp1 / lstm of one layer (float, hidden 1 .. 64) start from it — lstm
+starts h and c both at it (lstm.py:46) — and return dL/dh_0 when it requires grad; it must be (1, B, H) on x's device, as nn.GRU checks.
+A zero h_0 that needs no gradient runs the default kernels; any other runs the lane-per-unit state route (csrc/gru_wide.hip,
+lstm_wide.hip: ODPD_FLAG_INIT_STATE).  deltagru, deltajanet, deltagru_tcnskip, vdlstm, apnrru, mcldnn, gmp, tcnn, rvtdcnn and neuraltx
+ignore it, as the reference's do.  pgjanet, bojanet, dvrjanet, two-layer and quantised models raise NotImplementedError for a non-zero
+h_0 or one that requires grad.  Outside the envelope the ATen restatements pass h_0 through.
 """
 import warnings
 
@@ -17,6 +23,7 @@ import torch.nn as nn
 from . import backbones as B
 from .backbones import extras as X
 from .backbones import wide as W
+from .backbones.native import H0_IGNORED
 
 # names the reference registry accepts (models.py:26-141)
 REFERENCE_BACKBONES = ("gmp", "gru", "dgru", "qgru", "qgru_amp1", "lstm", "vdlstm", "rvtdcnn", "apnrru", "bojanet",
@@ -127,9 +134,27 @@ class CoreModel(nn.Module):
             with torch.backends.cudnn.flags(enabled=False):
                 return self.backbone(x, h_0)
         # the reference creates a zero h_0 (models.py:154-155); the kernels start from the zero state
-        if h_0 is not None and bool((h_0 != 0).any()):
-            raise NotImplementedError("non-zero initial hidden state is not supported by the HIP kernels")
-        return self.backbone(x, None)
+        bb = self.backbone
+        if h_0 is None or bb.initial_state == H0_IGNORED:      # (the reference's backbone never reads it)
+            return bb(x, None)
+        refusal = bb.state_refusal()
+        if refusal is None:      # nn.GRU / nn.LSTM's own check of the state (one layer)
+            B = x.size(0)
+            if h_0.device != x.device:
+                raise RuntimeError(f"Input and hidden tensors are not at the same device, found input tensor at {x.device} and hidden "
+                                   f"tensor at {h_0.device}")
+            if tuple(h_0.shape) != (1, B, self.hidden_size):
+                raise RuntimeError(f"Expected hidden size {(1, B, self.hidden_size)}, got {list(h_0.shape)}")
+        # a zero state that needs no gradient is the kernels' own start: today's path, bit for bit
+        needs_state = (torch.is_grad_enabled() and h_0.requires_grad) or bool((h_0 != 0).any())
+        if not needs_state:
+            return bb(x, None)
+        if refusal is not None:
+            raise NotImplementedError(f"an initial hidden state h_0 (non-zero, or requiring grad) is not supported by the HIP kernels of "
+                                      f"{refusal}: it runs on float gru / dgru / qgru / qgru_amp1 / lstm of one layer with 1 .. 64 hidden "
+                                      f"units; deltagru, deltajanet, deltagru_tcnskip, vdlstm, apnrru, mcldnn, gmp, tcnn, rvtdcnn and "
+                                      f"neuraltx ignore h_0, as the reference does")
+        return bb.forward_state(x, h_0)
 
 
 class CascadedModel(nn.Module):
