@@ -76,7 +76,9 @@ typedef struct odpd_model {
                          dvrjanet: num_dvr_units (models.py:119);
                          > 0 on rvtdcnn: Conv2d as INT_Conv2D (two scales behind its bias), fc_hid / fc_out as INT_Linear (three scales each);
                          > 0 on pgjanet (hidden <= 32): its six nn.Linear as INT_Linear, three scales behind each layer's bias;
-                         > 0 on any other backbone (no quantised kernels: apnrru, bojanet, mcldnn, deltagru; nothing to
+                         > 0 on bojanet (hidden <= 16) TOGETHER WITH ODPD_FLAG_QUANT_CELL: its eight nn.Linear as INT_Linear (bojanet_q.hip), three
+                         scales behind each layer's weight / bias — without the flag the descriptor is refused like the ones below;
+                         > 0 on any other backbone (no quantised kernels: apnrru, mcldnn, deltagru; nothing to
                          quantise: gmp, tcnn): every entry point answers ODPD_EINVAL — never the float kernels */
     int32_t bits_a;   /* QAT activation bits */
     int32_t flags;    /* ODPD_FLAG_* */
@@ -101,6 +103,13 @@ typedef struct odpd_model {
  * odpd_partial_rows(fused = 0) answer the sizes of those kernels; odpd_backbone_fwd / _bwd answer ODPD_EINVAL (use the _state calls); the
  * fused, framed, epoch, sweep, cascade and frozen-loss entry points answer ODPD_EUNSUPPORTED. */
 #define ODPD_FLAG_INIT_STATE 8
+/* the quantised model of a backbone whose nn.Linear layers sit INSIDE the recurrent cell (the surgery of quant/quant_envs.py:40-60, 145-148 swaps
+ * all of them for INT_Linear): together with bits_w > 0 and bits_a > 0 (each <= 16) it selects the kernels of bojanet_q.hip.  Valid on bojanet with
+ * 1 .. 16 hidden units only; on any other descriptor every entry point answers ODPD_EUNSUPPORTED.  `params` follows named_parameters() of the
+ * quantised module (per layer: weight, bias if it has one, weight_quantizer.scale, act_quantizer.scale, out_quantizer.scale: P = 2H^2 + 28H + 218).
+ * With the flag, odpd_param_count, odpd_ckpt_floats, odpd_partial_rows(fused = 0) and odpd_backbone_fwd / _bwd serve the model; the fused,
+ * framed, epoch, sweep, cascade and frozen-loss entry points answer ODPD_EUNSUPPORTED and the caller chains forward, loss, backward. */
+#define ODPD_FLAG_QUANT_CELL 16
 
 /* loss kinds — project.py:262-272 */
 enum odpd_loss { ODPD_LOSS_L2 = 0, ODPD_LOSS_L1 = 1 };

@@ -308,6 +308,45 @@ class QuantPGJANET(_QuantBase):
         self._finish(H, bits_w, bits_a)
 
 
+class QuantBOJANET(_QuantBase):
+    """bojanet after the surgery: all eight nn.Linear of the backbone — the FIR banks fir_I, fir_Q, the gates W_fi, W_fh, W_gi, W_gh and the
+    read-outs W_out_I, W_out_Q (bojanet.py:15-26) — become INT_Linear in named_children order, each with three scales; the functional
+    sigmoid / tanh / sqrt calls stay float; no module is named fc_out, so no output quantiser runs (train mode = eval mode).  Kernels:
+    csrc/bojanet_q.hip (hidden <= 16), selected by ODPD_FLAG_QUANT_CELL on the descriptor."""
+    backbone_name = "bojanet"
+    MAX_HIDDEN = 16
+    LAYERS = ("fir_I", "fir_Q", "W_fi", "W_fh", "W_gi", "W_gh", "W_out_I", "W_out_Q")
+
+    def __init__(self, hidden_size, bits_w, bits_a):
+        super().__init__()
+        H, P = hidden_size, 6
+        self.hidden_size, self.output_size, self.window_size, self.num_vd_units, self.bias = H, 2, 16, P, True
+        self.fir_I = _QLinear(16, P, bits_w, bits_a, bias=False)
+        self.fir_Q = _QLinear(16, P, bits_w, bits_a, bias=False)
+        self.W_fi = _QLinear(2 * P, H, bits_w, bits_a)
+        self.W_fh = _QLinear(H, H, bits_w, bits_a, bias=False)
+        self.W_gi = _QLinear(2 * P, H, bits_w, bits_a)
+        self.W_gh = _QLinear(H, H, bits_w, bits_a, bias=False)
+        self.W_out_I = _QLinear(H, 1, bits_w, bits_a)
+        self.W_out_Q = _QLinear(H, 1, bits_w, bits_a)
+        self._finish(H, bits_w, bits_a)
+        self.desc.flags |= _lib.FLAG_QUANT_CELL          # (sync_mode keeps every flag bit but ODPD_FLAG_EVAL)
+
+    def forward(self, x, h_0=None):
+        """the out_quantizer scales are outside the graph (no module is named fc_out): they reach the kernel call detached, so their `grad`
+        stays None as it does in the reference, and AdamW skips them (`frozen_mask`)"""
+        from .backbones.native import _BackboneFn
+        self.sync_mode()
+        params = [p.detach() if "out_quantizer" in n else p for n, p in self.named_parameters()]
+        return _BackboneFn.apply(x, self, torch.is_grad_enabled(), *params)
+
+    @staticmethod
+    def serves(model, bits_w, bits_a, dev):
+        """a bojanet on a HIP device within the kernels' envelope (csrc/bojanet_q.hip::bojanet_q_ok); everything else keeps the ATen route"""
+        return (model.backbone_type == "bojanet" and dev.type == "cuda" and model.hidden_size <= QuantBOJANET.MAX_HIDDEN and
+                2 <= bits_w <= 16 and 2 <= bits_a <= 16)
+
+
 class _QDeltaLayer(nn.Module):
     """DeltaGRULayer of deltagru_tcnskip.py:133-162 after the surgery: bias-free INT_Linear x2h / h2h, Quant_add / mult / sigmoid /
     tanh in the layer's own registration order."""
@@ -375,6 +414,8 @@ class QuantTResDeltaGRU(_QuantBase):
 
 MAX_HIDDEN = 32          # csrc/qat_s16.hip: two 16-unit tiles
 _UNTOUCHED = ("gmp", "tcnn")       # no nn.GRU, no nn.Linear, no op modules: the surgery returns an identical deep copy
+# nn.Linear / nn.Conv2d layers INSIDE a recurrent cell: the announced ATen route (`_quantise_aten`) — except bojanet of <= 16 hidden units on a
+# HIP device, whose quantised cell has kernels (`_quantise_bojanet`, csrc/bojanet_q.hip)
 _PARTIAL = ("apnrru", "bojanet", "dvrjanet", "mcldnn")
 _HEAD_ONLY = ("lstm", "vdlstm", "deltajanet", "neuraltx", "rvtdcnn", "pgjanet")    # only nn.Linear / nn.Conv2d layers to swap, and kernels for the result exist
 _HEAD_MAX_HIDDEN = {"deltajanet": 64, "neuraltx": 64, "lstm": 64}      # csrc/deltajanet_wide.hip, tcnn.hip, lstm_wide.hip (33 .. 64) carry the quantised head
@@ -454,26 +495,50 @@ def _aten_swap(mod, layer_type, bits_w, bits_a):
             _aten_swap(child, layer_type, bits_w, bits_a)
 
 
+def _float_state(model, pre):
+    """the float backbone's state dict the surgery starts from: the model's own, or — load_model strict-loads the float checkpoint before the
+    layers are swapped (quant_envs.py:173-182) — the checkpoint's; raises what the reference's try block would catch"""
+    sd = {k: v.detach().cpu() for k, v in model.backbone.state_dict().items()}
+    if pre:
+        pre_sd = torch.load(pre, map_location="cpu")
+        want = {"backbone." + k: tuple(v.shape) for k, v in sd.items()}
+        if not isinstance(pre_sd, dict) or set(pre_sd) != set(want) or any(tuple(pre_sd[k].shape) != s_ for k, s_ in want.items()):
+            raise RuntimeError("Error(s) in loading state_dict for CoreModel")
+        sd = {k: pre_sd["backbone." + k] for k in sd}
+    return sd
+
+
+def _quantise_bojanet(model, bits_w, bits_a, pre, dev):
+    """bojanet of <= 16 hidden units on a HIP device: the same surgery as `_quantise_aten` performs on the ATen restatement — the same RNG draws
+    (eight INT_Linear in named_children order, each a fresh default nn.Linear init that keeps only the float layer's weight), the same
+    `pretrained_model` handling, the same state-dict keys, order and values — with the result held by `QuantBOJANET`: `native` True, the kernels
+    of csrc/bojanet_q.hip, FusedAdamW."""
+    try:
+        sd = _float_state(model, pre)
+    except Exception as exc:
+        return _warn_float(exc, model)
+    with torch.no_grad():
+        bb = QuantBOJANET(model.hidden_size, bits_w, bits_a)
+        for name in QuantBOJANET.LAYERS:
+            getattr(bb, name).weight.copy_(sd[name + ".weight"])
+    return _wrap(model, bb, dev)
+
+
 def _quantise_aten(model, bits_w, bits_a, pre, dev):
     """apnrru / bojanet / dvrjanet / mcldnn (quant_envs.py:285-306 runs on them like on every registry model): their gates, FIR banks and
     read-outs are nn.Linear (mcldnn: two nn.Conv2d and two nn.Linear next to a float Conv1d and nn.LSTM) — all of them become INT_Linear /
-    INT_Conv2D, the functional sigmoid / tanh calls stay float.  There are no HIP kernels for a quantised mat-vec INSIDE these cells: the
-    quantised model is the ATen restatement of the backbone (backbones/extras.py) with the surgery applied to it — `native` False, said
-    aloud once per configuration, torch optimiser — pinned to fixtures produced by the reference (tests/test_quant_partial_cpu.py)."""
+    INT_Conv2D, the functional sigmoid / tanh calls stay float.  The quantised model is the ATen restatement of the backbone
+    (backbones/extras.py) with the surgery applied to it — `native` False, said aloud once per configuration, torch optimiser — pinned to
+    fixtures produced by the reference (tests/test_quant_partial_cpu.py).  apnrru, dvrjanet and mcldnn have no HIP kernels for a quantised
+    mat-vec INSIDE their cells; bojanet has them for hidden <= 16 on a HIP device (`_quantise_bojanet`: get_quant_model goes there first) and
+    comes here on the CPU, at hidden 17 / 18 and for other bit widths."""
     import warnings
     from .backbones import extras as X
     bt, H = model.backbone_type, model.hidden_size
-    fb = model.backbone
-    sd = {k: v.detach().cpu() for k, v in fb.state_dict().items()}
-    if pre:
-        try:      # load_model strict-loads the float checkpoint before the layers are swapped (quant_envs.py:173-182)
-            pre_sd = torch.load(pre, map_location="cpu")
-            want = {"backbone." + k: tuple(v.shape) for k, v in sd.items()}
-            if not isinstance(pre_sd, dict) or set(pre_sd) != set(want) or any(tuple(pre_sd[k].shape) != s_ for k, s_ in want.items()):
-                raise RuntimeError("Error(s) in loading state_dict for CoreModel")
-            sd = {k: pre_sd["backbone." + k] for k in sd}
-        except Exception as exc:
-            return _warn_float(exc, model)
+    try:
+        sd = _float_state(model, pre)
+    except Exception as exc:
+        return _warn_float(exc, model)
     rng = torch.get_rng_state()      # building the holder draws initialisations the reference (a deepcopy) does not: keep the stream where it was
     ext = {"apnrru": lambda: X.APNRRU(hidden_size=H, bias=True), "bojanet": lambda: X.BOJANET(hidden_size=H, output_size=2, bias=True),
            "dvrjanet": lambda: X.DVRJANET(hidden_size=H, output_size=2, num_dvr_units=model.num_dvr_units, bias=True),
@@ -500,8 +565,10 @@ def get_quant_model(proj, model):
     reference swaps it for a plain GRU and then fails in forward (TypeError, deltagru.py:74-77): refused here at construction.  In lstm,
     vdlstm, deltajanet and neuraltx the surgery finds only nn.Linear HEADS (float core, INT_Linear heads: `_quantise_heads`; deltajanet
     and neuraltx up to 64 units / channels); the backbones whose gates or convolutions are themselves nn.Linear / nn.Conv2d modules INSIDE a recurrent
-    cell (`_PARTIAL`: apnrru, bojanet, dvrjanet, mcldnn) have no quantised kernels: their quantised model is the ATen restatement of the backbone
-    with the surgery applied (`_quantise_aten`: `native` False, announced by a warning) — it trains, as it does in the reference.
+    cell (`_PARTIAL`: apnrru, bojanet, dvrjanet, mcldnn): bojanet of <= 16 hidden units on a HIP device runs its eight INT_Linear on the kernels
+    of csrc/bojanet_q.hip (`_quantise_bojanet`: `QuantBOJANET`, `native` True); the others — and bojanet on the CPU, at hidden 17 / 18 or with
+    bit widths outside 2 .. 16 — have no quantised kernels: their quantised model is the ATen restatement of the backbone with the surgery
+    applied (`_quantise_aten`: `native` False, announced by a warning) — it trains, as it does in the reference.
 
     `pretrained_model` follows Base_GRUQuantEnv.load_model (quant_envs.py:173-182): the checkpoint is strict-loaded into the FLOAT
     holder before quantisation — for the GRU-cell models its keys are `backbone.rnn.rnn_cell_list.0.{x2h,h2h}.{weight,bias}`,
@@ -522,7 +589,10 @@ def get_quant_model(proj, model):
                            "model then fails in forward (TypeError); use 'deltagru_tcnskip'")
     bits_w, bits_a = int(getattr(proj, "n_bits_w", 8)), int(getattr(proj, "n_bits_a", 8))
     if bt in _PARTIAL:
-        return _quantise_aten(model, bits_w, bits_a, getattr(proj, "pretrained_model", ""), next(model.parameters()).device)
+        dev, pre = next(model.parameters()).device, getattr(proj, "pretrained_model", "")
+        if QuantBOJANET.serves(model, bits_w, bits_a, dev):
+            return _quantise_bojanet(model, bits_w, bits_a, pre, dev)
+        return _quantise_aten(model, bits_w, bits_a, pre, dev)
     H = model.hidden_size
     max_h = _HEAD_MAX_HIDDEN.get(bt, MAX_HIDDEN)
     # pgjanet, rvtdcnn and neuraltx ignore num_layers (models.py:26-141 never hands it to them; wide.outside_envelope treats them the same way):
