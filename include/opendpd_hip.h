@@ -62,7 +62,8 @@ typedef struct odpd_model {
     int32_t hidden;   /* hidden_size (channels for tcnn; memory_length for gmp): <= 32 — float gru / dgru / qgru / qgru_amp1 / lstm / vdlstm / deltagru /
                          deltagru_tcnskip / deltajanet: <= 64 (33 .. 64: forward / backward only, the fused entry points answer ODPD_EUNSUPPORTED) — (pgjanet: <= 32, its 17 .. 32 likewise;
                          tcnn: <= 64; gmp: 11; rvtdcnn: fc_hid_size), else ODPD_EUNSUPPORTED */
-    float thx;        /* delta threshold on inputs  (deltagru*, models.py:11) */
+    float thx;        /* delta threshold on inputs  (deltagru*, models.py:11); on dvrjanet WITH ODPD_FLAG_QUANT_CELL: num_dvr_units (1 .. 8) as an exact
+                         small integer, thh = 0 — anything else (2.5, 0, 9, thh != 0) answers ODPD_EUNSUPPORTED */
     float thh;        /* delta threshold on hidden state */
     int32_t bits_w;   /* QAT weight bits (0 = float model) — quant/quant_envs.py:145: > 0 on gru, dgru, qgru, qgru_amp1 or deltagru_tcnskip selects the
                          model the reference's surgery makes of it (quant_envs.py:114-130, 290-306: GRU of GRUCells / quantised delta layer,
@@ -73,7 +74,8 @@ typedef struct odpd_model {
                          INT_Linear, three scales behind fc_out.bias; > 0 on neuraltx: IQ_match (the one nn.Linear; the Conv1d layers are not in the
                          surgery's layer map, quant_envs.py:145-148) becomes a bias-free INT_Linear, three scales behind IQ_match.weight, no
                          output quantiser in either mode (no module is named fc_out);
-                         dvrjanet: num_dvr_units (models.py:119);
+                         dvrjanet: num_dvr_units (models.py:119) — except TOGETHER WITH ODPD_FLAG_QUANT_CELL (hidden <= 16): then bits_w, bits_a > 0 are
+                         the bit widths of its nine nn.Linear as INT_Linear (dvrjanet_q.hip) and num_dvr_units rides in thx;
                          > 0 on rvtdcnn: Conv2d as INT_Conv2D (two scales behind its bias), fc_hid / fc_out as INT_Linear (three scales each);
                          > 0 on pgjanet (hidden <= 32): its six nn.Linear as INT_Linear, three scales behind each layer's bias;
                          > 0 on bojanet (hidden <= 16) TOGETHER WITH ODPD_FLAG_QUANT_CELL: its eight nn.Linear as INT_Linear (bojanet_q.hip), three
@@ -104,9 +106,11 @@ typedef struct odpd_model {
  * fused, framed, epoch, sweep, cascade and frozen-loss entry points answer ODPD_EUNSUPPORTED. */
 #define ODPD_FLAG_INIT_STATE 8
 /* the quantised model of a backbone whose nn.Linear layers sit INSIDE the recurrent cell (the surgery of quant/quant_envs.py:40-60, 145-148 swaps
- * all of them for INT_Linear): together with bits_w > 0 and bits_a > 0 (each <= 16) it selects the kernels of bojanet_q.hip.  Valid on bojanet with
- * 1 .. 16 hidden units only; on any other descriptor every entry point answers ODPD_EUNSUPPORTED.  `params` follows named_parameters() of the
- * quantised module (per layer: weight, bias if it has one, weight_quantizer.scale, act_quantizer.scale, out_quantizer.scale: P = 2H^2 + 28H + 218).
+ * all of them for INT_Linear): together with bits_w > 0 and bits_a > 0 (each <= 16) it selects the kernels of bojanet_q.hip / dvrjanet_q.hip.  Valid
+ * on bojanet with 1 .. 16 hidden units and on dvrjanet with 1 .. 16 hidden units and thx = num_dvr_units in 1 .. 8, thh = 0; on any other
+ * descriptor every entry point answers ODPD_EUNSUPPORTED.  `params` follows named_parameters() of the quantised module (dvrjanet: cs first; per
+ * layer: weight, bias if it has one, weight_quantizer.scale, act_quantizer.scale, out_quantizer.scale: P = 2H^2 + 28H + 218 for bojanet,
+ * 7H^2 + 7H + 29 + num_dvr_units for dvrjanet).
  * With the flag, odpd_param_count, odpd_ckpt_floats, odpd_partial_rows(fused = 0) and odpd_backbone_fwd / _bwd serve the model; the fused,
  * framed, epoch, sweep, cascade and frozen-loss entry points answer ODPD_EUNSUPPORTED and the caller chains forward, loss, backward. */
 #define ODPD_FLAG_QUANT_CELL 16

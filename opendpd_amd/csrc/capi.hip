@@ -17,8 +17,8 @@ inline Family family_of(int bb);
 // a quantisation-aware model: bits_w > 0 on one of the backbones the reference's surgery turns into a quantised cell
 // (quant/quant_envs.py:114-130, 290-306: gru, dgru, qgru, qgru_amp1 through the GRU swap; deltagru_tcnskip through its op modules)
 inline Family family_of(const odpd_model_t* m) {
-    // ODPD_FLAG_QUANT_CELL: a family of its own (bojanet_q.hip: forward / backward) — like FAM_GRU2 below, so that no entry point written for the
-    // float bojanet kernels reads the quantised parameter buffer, and the flag on any other descriptor finds no kernel anywhere
+    // ODPD_FLAG_QUANT_CELL: a family of its own (bojanet_q.hip, dvrjanet_q.hip: forward / backward) — like FAM_GRU2 below, so that no entry point
+    // written for the float bojanet / dvrjanet kernels reads the quantised parameter buffer, and the flag on any other descriptor finds no kernel anywhere
     if (m->flags & ODPD_FLAG_QUANT_CELL) return FAM_QCELL;
     // two recurrent layers: a family of its own (gru_layers2.hip: forward / backward) — every entry point written for the one-layer kernels
     // tests `family_of(m) == FAM_...` and so answers ODPD_EUNSUPPORTED for these descriptors instead of misreading their parameter buffer
@@ -65,9 +65,10 @@ inline int feat_dim(int bb) {
 // gru_wide.hip / lstm_wide.hip serve for the float gru / dgru / qgru / qgru_amp1 / lstm of 1 .. 64 hidden units, one layer; every entry point
 // answers ODPD_EUNSUPPORTED for the flag on any other descriptor
 inline bool init_state(const odpd_model_t* m) { return (m->flags & ODPD_FLAG_INIT_STATE) != 0; }
-// ODPD_FLAG_QUANT_CELL: the quantised bojanet of 1 .. 16 hidden units (bojanet_q.hip); every entry point answers ODPD_EUNSUPPORTED for the flag on
-// any other descriptor (the state route included)
+// ODPD_FLAG_QUANT_CELL: the quantised bojanet (bojanet_q.hip) and dvrjanet (dvrjanet_q.hip) of 1 .. 16 hidden units; every entry point answers
+// ODPD_EUNSUPPORTED for the flag on any other descriptor (the state route included)
 inline bool quant_cell(const odpd_model_t* m) { return (m->flags & ODPD_FLAG_QUANT_CELL) != 0; }
+inline bool quant_cell_ok(const odpd_model_t* m) { return bojanet_q_ok(m) || dvrjanet_q_ok(m); }
 inline bool init_state_ok(const odpd_model_t* m) { return !quant_cell(m) && (gru_state_ok(m) || lstm_state_ok(m)); }
 // models served by the lane-per-unit kernels (gru_wide.hip, lstm_wide.hip, vdlstm_wide.hip, delta_wide.hip: 33 .. 64 hidden units; janet_wide.hip: pgjanet 17 .. 32;
 // every ODPD_FLAG_INIT_STATE descriptor): forward / backward only — the fused entry points answer ODPD_EUNSUPPORTED for them and the caller chains
@@ -80,7 +81,7 @@ inline bool lane_per_unit_model(const odpd_model_t* m) {
 // the descriptor is refused outright — no entry point may answer it with the float kernels on a float parameter layout
 inline bool quant_desc_ok(const odpd_model_t* m) {
     if (m->bits_w <= 0 || m->backbone == ODPD_DVRJANET) return true;      // (dvrjanet: bits_w carries num_dvr_units)
-    if (quant_cell(m)) return true;      // (what the flag is valid on is answered with ODPD_EUNSUPPORTED, not here: bojanet_q_ok)
+    if (quant_cell(m)) return true;      // (what the flag is valid on is answered with ODPD_EUNSUPPORTED, not here: quant_cell_ok)
     switch (m->backbone) {
     case ODPD_GRU: case ODPD_DGRU: case ODPD_QGRU: case ODPD_QGRU_AMP1: case ODPD_TRES_DELTAGRU:      // the surgery's quantised cells
     case ODPD_LSTM: case ODPD_VDLSTM: case ODPD_DELTAJANET: case ODPD_NEURALTX:                      // float core, INT_Linear heads
@@ -207,7 +208,7 @@ extern "C" const char* odpd_built_arch(void) { return "gfx950"; }
 extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
     if (!model_ok(m)) return ODPD_EINVAL;
     if (init_state(m) && !init_state_ok(m)) return ODPD_EUNSUPPORTED;
-    if (quant_cell(m)) return bojanet_q_ok(m) ? bojanet_q_param_count(m) : (int64_t)ODPD_EUNSUPPORTED;
+    if (quant_cell(m)) return bojanet_q_ok(m) ? bojanet_q_param_count(m) : dvrjanet_q_ok(m) ? dvrjanet_q_param_count(m) : (int64_t)ODPD_EUNSUPPORTED;
     if (family_of(m) == FAM_GRU2) return gru2_ok(m) ? gru2_param_count(m) : lstm2_ok(m) ? lstm2_param_count(m) : (int64_t)ODPD_EUNSUPPORTED;
     if (family_of(m) == FAM_QAT) return qat_s16_param_count(m);
     const int64_t H = m->hidden, F = feat_dim(m->backbone);
@@ -238,7 +239,7 @@ extern "C" int64_t odpd_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
     if (init_state(m))      // the per-step records of the lane-per-unit kernels, at every hidden size they serve on the state route
         return !init_state_ok(m) ? (int64_t)ODPD_EUNSUPPORTED : family_of(m) == FAM_LSTM ? lstm_wide_ckpt_floats(m, B, T) : gru_wide_ckpt_floats(m, B, T);
-    if (quant_cell(m)) return bojanet_q_ok(m) ? bojanet_q_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
+    if (quant_cell(m)) return bojanet_q_ok(m) ? bojanet_q_ckpt_floats(m, B, T) : dvrjanet_q_ok(m) ? dvrjanet_q_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
     if (family_of(m) == FAM_TCNN || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN) return 0;   // not recurrent: nothing to checkpoint
     if (family_of(m) == FAM_DVR) return dvrjanet_ckpt_floats(m, B, T);
     if (family_of(m) == FAM_BOJ) return bojanet_ckpt_floats(m, B, T);
@@ -279,7 +280,7 @@ extern "C" int64_t odpd_partial_rows(const odpd_model_t* m, int B, int T, int fu
     if (init_state(m))
         return (fused || !init_state_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : family_of(m) == FAM_LSTM ? (int64_t)lstm_wide_rows(m, B) : (int64_t)gru_wide_rows(m, B);
     switch (family_of(m)) {
-    case FAM_QCELL: return (fused || !bojanet_q_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)bojanet_q_rows(m, B);
+    case FAM_QCELL: return (fused || !quant_cell_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)(bojanet_q_ok(m) ? bojanet_q_rows(m, B) : dvrjanet_q_rows(m, B));
     case FAM_GRU2: return fused ? (int64_t)ODPD_EUNSUPPORTED : gru2_ok(m) ? (int64_t)gru2_rows(m, B) : lstm2_ok(m) ? (int64_t)lstm2_rows(m, B) : (int64_t)ODPD_EUNSUPPORTED;
     case FAM_GRU:
         if (gru_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)gru_wide_rows(m, B);
@@ -354,7 +355,8 @@ extern "C" int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.stats = stats;
     switch (family_of(m)) {
-    case FAM_QCELL: return bojanet_q_fwd((hipStream_t)stream, m, a);      // `--quant` on bojanet: eight INT_Linear (bojanet_q.hip)
+    case FAM_QCELL:      // `--quant` on bojanet: eight INT_Linear (bojanet_q.hip); on dvrjanet: nine (dvrjanet_q.hip)
+        return m->backbone == ODPD_DVRJANET ? dvrjanet_q_fwd((hipStream_t)stream, m, a) : bojanet_q_fwd((hipStream_t)stream, m, a);
     case FAM_GRU2: return lstm2_ok(m) ? lstm2_fwd((hipStream_t)stream, m, a) : gru2_fwd((hipStream_t)stream, m, a);
     case FAM_GRU: return gru_wide_ok(m) ? gru_wide_fwd((hipStream_t)stream, m, a) : gru_family_fwd((hipStream_t)stream, m, a);
     case FAM_LSTM:
@@ -387,7 +389,7 @@ extern "C" int odpd_backbone_bwd(void* stream, const odpd_model_t* m, int B, int
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx;
     switch (family_of(m)) {
-    case FAM_QCELL: return bojanet_q_bwd((hipStream_t)stream, m, a);
+    case FAM_QCELL: return m->backbone == ODPD_DVRJANET ? dvrjanet_q_bwd((hipStream_t)stream, m, a) : bojanet_q_bwd((hipStream_t)stream, m, a);
     case FAM_GRU2: return lstm2_ok(m) ? lstm2_bwd((hipStream_t)stream, m, a) : gru2_bwd((hipStream_t)stream, m, a);
     case FAM_GRU:
         if (gru_wide_ok(m)) return gru_wide_bwd((hipStream_t)stream, m, a);

@@ -425,6 +425,13 @@ int64_t bojanet_q_ckpt_floats(const odpd_model_t* m, int B, int T);
 int bojanet_q_rows(const odpd_model_t* m, int B);
 int bojanet_q_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int bojanet_q_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+// the quantised dvrjanet (ODPD_FLAG_QUANT_CELL, bits_w > 0, num_dvr_units in thx; csrc/dvrjanet_q.hip): forward / backward, hidden <= 16
+bool dvrjanet_q_ok(const odpd_model_t* m);
+int64_t dvrjanet_q_param_count(const odpd_model_t* m);
+int64_t dvrjanet_q_ckpt_floats(const odpd_model_t* m, int B, int T);
+int dvrjanet_q_rows(const odpd_model_t* m, int B);
+int dvrjanet_q_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+int dvrjanet_q_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 // the quantised rvtdcnn (bits_w > 0; csrc/rvtdcnn_q.hip)
 bool rvtdcnn_q_ok(const odpd_model_t* m, int T);
 int64_t rvtdcnn_q_param_count(const odpd_model_t* m);

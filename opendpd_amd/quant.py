@@ -308,7 +308,37 @@ class QuantPGJANET(_QuantBase):
         self._finish(H, bits_w, bits_a)
 
 
-class QuantBOJANET(_QuantBase):
+class _QuantCell(_QuantBase):
+    """What the backbones whose quantised layers sit INSIDE the recurrent cell share (bojanet, dvrjanet): the descriptor flag that selects their
+    kernels, the detached out_quantizer scales, the envelope test of `get_quant_model`."""
+    MAX_HIDDEN = 16
+    LAYERS = ()
+
+    def _finish_cell(self, hidden_size, bits_w, bits_a, thx=0.0):
+        self._finish(hidden_size, bits_w, bits_a, thx=thx)
+        self.desc.flags |= _lib.FLAG_QUANT_CELL          # (sync_mode keeps every flag bit but ODPD_FLAG_EVAL)
+
+    def forward(self, x, h_0=None):
+        """the out_quantizer scales are outside the graph (no module is named fc_out): they reach the kernel call detached, so their `grad`
+        stays None as it does in the reference, and AdamW skips them (`frozen_mask`)"""
+        from .backbones.native import _BackboneFn
+        self.sync_mode()
+        params = [p.detach() if "out_quantizer" in n else p for n, p in self.named_parameters()]
+        return _BackboneFn.apply(x, self, torch.is_grad_enabled(), *params)
+
+    @classmethod
+    def serves(cls, model, bits_w, bits_a, dev):
+        """a model of this backbone on a HIP device within the kernels' envelope (csrc/bojanet_q.hip::bojanet_q_ok, csrc/dvrjanet_q.hip::
+        dvrjanet_q_ok); everything else keeps the ATen route"""
+        return (model.backbone_type == cls.backbone_name and dev.type == "cuda" and model.hidden_size <= cls.MAX_HIDDEN and
+                2 <= bits_w <= 16 and 2 <= bits_a <= 16 and cls.serves_shape(model))
+
+    @staticmethod
+    def serves_shape(model):
+        return True
+
+
+class QuantBOJANET(_QuantCell):
     """bojanet after the surgery: all eight nn.Linear of the backbone — the FIR banks fir_I, fir_Q, the gates W_fi, W_fh, W_gi, W_gh and the
     read-outs W_out_I, W_out_Q (bojanet.py:15-26) — become INT_Linear in named_children order, each with three scales; the functional
     sigmoid / tanh / sqrt calls stay float; no module is named fc_out, so no output quantiser runs (train mode = eval mode).  Kernels:
@@ -329,22 +359,40 @@ class QuantBOJANET(_QuantBase):
         self.W_gh = _QLinear(H, H, bits_w, bits_a, bias=False)
         self.W_out_I = _QLinear(H, 1, bits_w, bits_a)
         self.W_out_Q = _QLinear(H, 1, bits_w, bits_a)
-        self._finish(H, bits_w, bits_a)
-        self.desc.flags |= _lib.FLAG_QUANT_CELL          # (sync_mode keeps every flag bit but ODPD_FLAG_EVAL)
+        self._finish_cell(H, bits_w, bits_a)
 
-    def forward(self, x, h_0=None):
-        """the out_quantizer scales are outside the graph (no module is named fc_out): they reach the kernel call detached, so their `grad`
-        stays None as it does in the reference, and AdamW skips them (`frozen_mask`)"""
-        from .backbones.native import _BackboneFn
-        self.sync_mode()
-        params = [p.detach() if "out_quantizer" in n else p for n, p in self.named_parameters()]
-        return _BackboneFn.apply(x, self, torch.is_grad_enabled(), *params)
+
+class QuantDVRJANET(_QuantCell):
+    """dvrjanet after the surgery: all nine nn.Linear of the backbone — the phase filter W_ph, W_pθ, the magnitude filter W_ah, W_ax, the gates
+    W_f, W_ccos, W_csin and the read-outs W_o1, W_o2 (dvrjanet.py:13-30) — become INT_Linear in named_children order, each with three scales;
+    `cs` stays a float parameter (registered where the reference registers it: named_parameters() lists it first); the functional atan2 / sqrt /
+    cos / sin / sigmoid / tanh / abs calls stay float; no module is named fc_out, so no output quantiser runs (train mode = eval mode).  Kernels:
+    csrc/dvrjanet_q.hip (hidden <= 16, 1 .. 8 DVR units), selected by ODPD_FLAG_QUANT_CELL on the descriptor; `num_dvr_units` rides in its thx
+    (bits_w, which carries it on the float descriptor, is the weight bit width here)."""
+    backbone_name = "dvrjanet"
+    MAX_DVR_UNITS = 8
+    LAYERS = ("W_ph", "W_pθ", "W_ah", "W_ax", "W_f", "W_ccos", "W_csin", "W_o1", "W_o2")
+
+    def __init__(self, hidden_size, num_dvr_units, bits_w, bits_a):
+        super().__init__()
+        H = hidden_size
+        self.hidden_size, self.output_size, self.num_dvr_units, self.bias, self.num_layers = H, 2, num_dvr_units, True, 1
+        self.W_ph = _QLinear(H, H, bits_w, bits_a, bias=False)
+        setattr(self, "W_pθ", _QLinear(1, H, bits_w, bits_a, bias=False))
+        self.W_ah = _QLinear(H, H, bits_w, bits_a, bias=False)
+        self.W_ax = _QLinear(1, H, bits_w, bits_a, bias=False)
+        self.cs = nn.Parameter(torch.zeros(num_dvr_units))       # (the surgery deep-copies it: no RNG draw; the caller fills it)
+        self.W_f = _QLinear(H, H, bits_w, bits_a)
+        self.W_ccos = _QLinear(2 * H, H, bits_w, bits_a)
+        self.W_csin = _QLinear(2 * H, H, bits_w, bits_a)
+        self.W_o1 = _QLinear(H, 1, bits_w, bits_a)
+        self.W_o2 = _QLinear(H, 1, bits_w, bits_a)
+        self._finish_cell(H, bits_w, bits_a, thx=float(num_dvr_units))
 
     @staticmethod
-    def serves(model, bits_w, bits_a, dev):
-        """a bojanet on a HIP device within the kernels' envelope (csrc/bojanet_q.hip::bojanet_q_ok); everything else keeps the ATen route"""
-        return (model.backbone_type == "bojanet" and dev.type == "cuda" and model.hidden_size <= QuantBOJANET.MAX_HIDDEN and
-                2 <= bits_w <= 16 and 2 <= bits_a <= 16)
+    def serves_shape(model):
+        K = model.num_dvr_units
+        return isinstance(K, int) and 1 <= K <= QuantDVRJANET.MAX_DVR_UNITS
 
 
 class _QDeltaLayer(nn.Module):
@@ -414,8 +462,8 @@ class QuantTResDeltaGRU(_QuantBase):
 
 MAX_HIDDEN = 32          # csrc/qat_s16.hip: two 16-unit tiles
 _UNTOUCHED = ("gmp", "tcnn")       # no nn.GRU, no nn.Linear, no op modules: the surgery returns an identical deep copy
-# nn.Linear / nn.Conv2d layers INSIDE a recurrent cell: the announced ATen route (`_quantise_aten`) — except bojanet of <= 16 hidden units on a
-# HIP device, whose quantised cell has kernels (`_quantise_bojanet`, csrc/bojanet_q.hip)
+# nn.Linear / nn.Conv2d layers INSIDE a recurrent cell: the announced ATen route (`_quantise_aten`) — except bojanet and dvrjanet of <= 16 hidden
+# units on a HIP device, whose quantised cells have kernels (`_quantise_bojanet`, csrc/bojanet_q.hip; `_quantise_dvrjanet`, csrc/dvrjanet_q.hip)
 _PARTIAL = ("apnrru", "bojanet", "dvrjanet", "mcldnn")
 _HEAD_ONLY = ("lstm", "vdlstm", "deltajanet", "neuraltx", "rvtdcnn", "pgjanet")    # only nn.Linear / nn.Conv2d layers to swap, and kernels for the result exist
 _HEAD_MAX_HIDDEN = {"deltajanet": 64, "neuraltx": 64, "lstm": 64}      # csrc/deltajanet_wide.hip, tcnn.hip, lstm_wide.hip (33 .. 64) carry the quantised head
@@ -508,20 +556,32 @@ def _float_state(model, pre):
     return sd
 
 
-def _quantise_bojanet(model, bits_w, bits_a, pre, dev):
-    """bojanet of <= 16 hidden units on a HIP device: the same surgery as `_quantise_aten` performs on the ATen restatement — the same RNG draws
-    (eight INT_Linear in named_children order, each a fresh default nn.Linear init that keeps only the float layer's weight), the same
-    `pretrained_model` handling, the same state-dict keys, order and values — with the result held by `QuantBOJANET`: `native` True, the kernels
-    of csrc/bojanet_q.hip, FusedAdamW."""
+def _quantise_cell(model, build, pre, dev):
+    """a backbone with kernels for its quantised cell: the same surgery as `_quantise_aten` performs on the ATen restatement — the same RNG draws
+    (every INT_Linear in named_children order, each a fresh default nn.Linear init that keeps only the float layer's weight), the same
+    `pretrained_model` handling, the same state-dict keys, order and values — with the result held by the module `build()` returns: `native` True,
+    FusedAdamW."""
     try:
         sd = _float_state(model, pre)
     except Exception as exc:
         return _warn_float(exc, model)
     with torch.no_grad():
-        bb = QuantBOJANET(model.hidden_size, bits_w, bits_a)
-        for name in QuantBOJANET.LAYERS:
+        bb = build()
+        for name in bb.LAYERS:
             getattr(bb, name).weight.copy_(sd[name + ".weight"])
+        for name, p in bb.named_parameters(recurse=False):      # parameters the surgery leaves alone (dvrjanet's cs)
+            p.copy_(sd[name])
     return _wrap(model, bb, dev)
+
+
+def _quantise_bojanet(model, bits_w, bits_a, pre, dev):
+    """bojanet of <= 16 hidden units on a HIP device: `QuantBOJANET`, the kernels of csrc/bojanet_q.hip (see `_quantise_cell`)"""
+    return _quantise_cell(model, lambda: QuantBOJANET(model.hidden_size, bits_w, bits_a), pre, dev)
+
+
+def _quantise_dvrjanet(model, bits_w, bits_a, pre, dev):
+    """dvrjanet of <= 16 hidden units and <= 8 DVR units on a HIP device: `QuantDVRJANET`, the kernels of csrc/dvrjanet_q.hip (see `_quantise_cell`)"""
+    return _quantise_cell(model, lambda: QuantDVRJANET(model.hidden_size, model.num_dvr_units, bits_w, bits_a), pre, dev)
 
 
 def _quantise_aten(model, bits_w, bits_a, pre, dev):
@@ -529,9 +589,9 @@ def _quantise_aten(model, bits_w, bits_a, pre, dev):
     read-outs are nn.Linear (mcldnn: two nn.Conv2d and two nn.Linear next to a float Conv1d and nn.LSTM) — all of them become INT_Linear /
     INT_Conv2D, the functional sigmoid / tanh calls stay float.  The quantised model is the ATen restatement of the backbone
     (backbones/extras.py) with the surgery applied to it — `native` False, said aloud once per configuration, torch optimiser — pinned to
-    fixtures produced by the reference (tests/test_quant_partial_cpu.py).  apnrru, dvrjanet and mcldnn have no HIP kernels for a quantised
-    mat-vec INSIDE their cells; bojanet has them for hidden <= 16 on a HIP device (`_quantise_bojanet`: get_quant_model goes there first) and
-    comes here on the CPU, at hidden 17 / 18 and for other bit widths."""
+    fixtures produced by the reference (tests/test_quant_partial_cpu.py).  apnrru and mcldnn have no HIP kernels for a quantised
+    mat-vec INSIDE their cells; bojanet and dvrjanet have them for hidden <= 16 on a HIP device (`_quantise_bojanet`, `_quantise_dvrjanet`:
+    get_quant_model goes there first) and come here on the CPU, at larger hidden sizes and for other bit widths."""
     import warnings
     from .backbones import extras as X
     bt, H = model.backbone_type, model.hidden_size
@@ -566,9 +626,10 @@ def get_quant_model(proj, model):
     vdlstm, deltajanet and neuraltx the surgery finds only nn.Linear HEADS (float core, INT_Linear heads: `_quantise_heads`; deltajanet
     and neuraltx up to 64 units / channels); the backbones whose gates or convolutions are themselves nn.Linear / nn.Conv2d modules INSIDE a recurrent
     cell (`_PARTIAL`: apnrru, bojanet, dvrjanet, mcldnn): bojanet of <= 16 hidden units on a HIP device runs its eight INT_Linear on the kernels
-    of csrc/bojanet_q.hip (`_quantise_bojanet`: `QuantBOJANET`, `native` True); the others — and bojanet on the CPU, at hidden 17 / 18 or with
-    bit widths outside 2 .. 16 — have no quantised kernels: their quantised model is the ATen restatement of the backbone with the surgery
-    applied (`_quantise_aten`: `native` False, announced by a warning) — it trains, as it does in the reference.
+    of csrc/bojanet_q.hip (`_quantise_bojanet`: `QuantBOJANET`, `native` True), dvrjanet of <= 16 hidden units and <= 8 DVR units its nine on
+    those of csrc/dvrjanet_q.hip (`_quantise_dvrjanet`: `QuantDVRJANET`); apnrru and mcldnn — and bojanet / dvrjanet on the CPU, at larger hidden
+    sizes or with bit widths outside 2 .. 16 — have no quantised kernels: their quantised model is the ATen restatement of the backbone with the
+    surgery applied (`_quantise_aten`: `native` False, announced by a warning) — it trains, as it does in the reference.
 
     `pretrained_model` follows Base_GRUQuantEnv.load_model (quant_envs.py:173-182): the checkpoint is strict-loaded into the FLOAT
     holder before quantisation — for the GRU-cell models its keys are `backbone.rnn.rnn_cell_list.0.{x2h,h2h}.{weight,bias}`,
@@ -590,8 +651,15 @@ def get_quant_model(proj, model):
     bits_w, bits_a = int(getattr(proj, "n_bits_w", 8)), int(getattr(proj, "n_bits_a", 8))
     if bt in _PARTIAL:
         dev, pre = next(model.parameters()).device, getattr(proj, "pretrained_model", "")
+        # train_dpd / run_dpd quantise the DPD while it is still on the CPU and move it afterwards (project.py): the route is chosen for the device
+        # the project runs on (Project.set_device), where it has one
+        target = getattr(proj, "device", None)
+        if dev.type == "cpu" and isinstance(target, torch.device) and target.type == "cuda":
+            dev = target
         if QuantBOJANET.serves(model, bits_w, bits_a, dev):
             return _quantise_bojanet(model, bits_w, bits_a, pre, dev)
+        if QuantDVRJANET.serves(model, bits_w, bits_a, dev):
+            return _quantise_dvrjanet(model, bits_w, bits_a, pre, dev)
         return _quantise_aten(model, bits_w, bits_a, pre, dev)
     H = model.hidden_size
     max_h = _HEAD_MAX_HIDDEN.get(bt, MAX_HIDDEN)
