@@ -4,8 +4,8 @@
 // (three scale parameters behind each layer's weight / bias); sigmoid, tanh, sqrt and the divisions are functional and stay float; no module is
 // named fc_out, so the 16-bit output quantiser never runs (train mode = eval mode).  Selected by ODPD_FLAG_QUANT_CELL with bits_w, bits_a > 0.
 //
-// ONE sequence per single-wave workgroup (the form of boj_gp_eval_kernel / pgjanet_q.hip), in chunks of 64 steps.  The parameters are staged in
-// LDS with the eight weight matrices quantised IN PLACE.  Per chunk:
+// ONE sequence per single-wave workgroup (the form of boj_gp_eval_kernel / pgjanet_q.hip), in chunks of 64 steps.  Parameter layout, setup (the
+// parameters staged in LDS with the eight weight matrices quantised IN PLACE) and write-out: odpd_qcell.h.  Per chunk:
 //   front       lane = time step: the frame chunk is staged with a 16-sample halo as FOUR quantised copies (fir_I and fir_Q are each called on the
 //               I window and on the Q window, bojanet.py:82-85: q_firI(I), q_firQ(I), q_firI(Q), q_firQ(Q)); the four 16-tap sums per filter,
 //               fi = fir_I(I) - fir_Q(Q), fq = fir_Q(I) + fir_I(Q); the demodulator; the envelopes on W_fi's and on W_gi's activation grid; the
@@ -18,33 +18,27 @@
 // gradients with lane = time step, the reverse recurrence with lane = unit (transposed blocks in registers, every layer's activation pass mask;
 // the weight gradients of W_fh, W_gh, W_fi, W_gi accumulate in the registers of the lane that owns the row), the demodulator's gradient with
 // lane = time step, dL/dx as a gather over the 16 steps that see a sample (the first 15 steps of the later chunk are kept as a halo; each sample
-// passes the masks of BOTH banks' activation quantisers), the FIR weight gradients with lane = (filter, tap).  The weight quantisers' pass masks
-// are applied at write-out from the unquantised weights; the 24 scale columns are exact zeros.
+// passes the masks of BOTH banks' activation quantisers), the FIR weight gradients with lane = (filter, tap).
 // Deviation: where a filter output is exactly 0 + 0j — no measure-zero event with inputs on a grid — the reference's gradient is NaN (0 * inf
 // through sqrt); here that term is dropped, as in bojanet_s16.hip.
-#include "odpd_seq.h"
-#include "odpd_quant.h"
+#include "odpd_qcell.h"
 
 #pragma clang fp contract(off)
 
 namespace odpd {
 namespace {
+using namespace qcell;
 constexpr int kQP = 6, kQM = 16, kQE = 2 * kQP;     // filters, taps, envelopes
 constexpr int kQC = 64;                             // steps per chunk
 constexpr int kQX = kQC + 16;                       // staged samples: index i <-> time t0 - 16 + i; also the row of dL/dfi, dL/dfq (64 .. 78: the later chunk's first steps)
 constexpr int kQP16 = 17, kQP32 = 33;               // row pitches of the [time][unit] buffers: conflict-free for lane = unit and for lane = time
 constexpr int kQL = 8;                              // 0 fir_I  1 fir_Q  2 W_fi  3 W_fh  4 W_gi  5 W_gh  6 W_out_I  7 W_out_Q (named_parameters order)
-struct BjqLayout { int H, ow[kQL], ob[kQL], oq[kQL], P; };      // weight, bias (= oq without one), the three scales
+struct BjqLayout : QcLayout<kQL> { int H; };
 __host__ __device__ inline int bjq_nin(int l, int H) { return l < 2 ? kQM : (l == 2 || l == 4) ? kQE : H; }
 __host__ __device__ inline int bjq_nout(int l, int H) { return l < 2 ? kQP : l < 6 ? H : 1; }
 __host__ __device__ inline BjqLayout bjq_layout(int H) {
-    BjqLayout L; L.H = H; int o = 0;
-    for (int l = 0; l < kQL; ++l) {
-        L.ow[l] = o; o += bjq_nout(l, H) * bjq_nin(l, H);
-        L.ob[l] = o; if (l == 2 || l == 4 || l >= 6) o += bjq_nout(l, H);
-        L.oq[l] = o; o += 3;
-    }
-    L.P = o;
+    BjqLayout L; L.H = H;
+    qc_fill_layout(L, 0, [H](int l) { return QcLinear{bjq_nout(l, H), bjq_nin(l, H), l == 2 || l == 4 || l >= 6}; });
     return L;
 }
 constexpr int kQHist = ((kQC + 1) * kQP16 + 3) & ~3;
@@ -53,29 +47,7 @@ __host__ __device__ inline int bjq_bwd_floats(int P) {
     return 2 * pad4(P) + 4 * kQX + kQE * kQC + 2 * kQC * kQE + 2 * kQP32 * kQC + kQHist + kQP16 * kQC + kQE * kQC + kQE * kQX + 2 * kQC + 64;
 }
 
-__device__ __forceinline__ float bjq_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-struct BjqQ { q16::Quant a[kQL]; };
-// stage the parameters, form the activation quantisers, quantise the eight weight matrices in the staged copy
-__device__ __forceinline__ void bjq_setup(float* pl, const SeqArgs& a, const BjqLayout& L, BjqQ& Q, int lane) {
-    stage_params(pl, a.params, L.P);
-    wave_lds_fence();
-    q16::Quant qw[kQL];
-#pragma unroll
-    for (int l = 0; l < kQL; ++l) {
-        Q.a[l] = q16::make_quant(pl[L.oq[l] + 1], a.bits_a);
-        Q.a[l].s = bjq_uni(Q.a[l].s); Q.a[l].inv = bjq_uni(Q.a[l].inv);
-        qw[l] = q16::make_quant(pl[L.oq[l]], a.bits_w);
-    }
-    wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < kQL; ++l) {
-        const int n = L.ob[l] - L.ow[l];
-        for (int i = lane; i < n; i += 64) pl[L.ow[l] + i] = q16::qapply(pl[L.ow[l] + i], qw[l]);
-    }
-    wave_lds_fence();
-}
+struct BjqQ { q16::Quant a[kQL]; };      // the layers' activation quantisers (wave-uniform)
 // the chunk's samples with their halo, zero outside the frame (bojanet.py:72-73), on the four grids they are read on
 __device__ __forceinline__ void bjq_stage_x(float4* xq, const float2* xg, int t0, int T, const BjqQ& Q, int lane) {
     for (int i = lane; i < kQX; i += 64) {
@@ -148,14 +120,7 @@ __device__ __forceinline__ float bjq_recur(const BjqQ& Q, const float (&w)[16], 
     for (int tt = 0; tt < len; ++tt) {
         if (role == 0) { vq[col] = q16::qapply(h, Q.a[3]); vq[16 + col] = q16::qapply(h, Q.a[5]); }
         wave_lds_fence();
-        float acc = 0.0f;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const float4 v = *reinterpret_cast<const float4*>(vr + 4 * q4);
-            acc = __builtin_fmaf(w[4 * q4], v.x, acc); acc = __builtin_fmaf(w[4 * q4 + 1], v.y, acc);
-            acc = __builtin_fmaf(w[4 * q4 + 2], v.z, acc); acc = __builtin_fmaf(w[4 * q4 + 3], v.w, acc);
-        }
-        const float pre = xs[tt * kQP32 + xo] + acc;
+        const float pre = xs[tt * kQP32 + xo] + qc_dot(w, vr, 0.0f);
         const float v = is_f ? sigmoidf_(pre) : tanhf_(pre), o = xor16(v);
         const float f = is_f ? v : o, g = is_f ? o : v;
         h = valid ? f * h + (1.0f - f) * g : 0.0f;
@@ -181,7 +146,7 @@ __global__ __launch_bounds__(64) void bjq_fwd_kernel(SeqArgs a) {
     float* hist = xs + kQP32 * kQC;                                  // [65][17]
     float* vq = hist + kQHist;                                       // [2][16] q_fh(h), q_gh(h)
     BjqQ Q;
-    bjq_setup(pl, a, L, Q, lane);
+    qc_setup<true>(pl, a, L, Q.a, lane);
     const bool valid = col < H;
     float w[16];
 #pragma unroll
@@ -245,7 +210,7 @@ __global__ __launch_bounds__(64) void bjq_bwd_kernel(SeqArgs a) {
     float* dyb = dfiq + kQE * kQX;                                   // [64][2]
     float* vb = dyb + 2 * kQC;                                       // [4][16] d_f, d_g, q_fh(h(t-1)), q_gh(h(t-1))
     BjqQ Q;
-    bjq_setup(pl, a, L, Q, lane);
+    qc_setup<true>(pl, a, L, Q.a, lane);
     const bool valid = col < H;
     float w[16], wT[16];
 #pragma unroll
@@ -331,31 +296,13 @@ __global__ __launch_bounds__(64) void bjq_bwd_kernel(SeqArgs a) {
                         xs[tt * kQP32 + col] = dfp; xs[tt * kQP32 + 16 + col] = dgp;
                     }
                     wave_lds_fence();
-                    float part = 0.0f;
-#pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        const float4 v = *reinterpret_cast<const float4*>(dv + 4 * q4);
-                        part = __builtin_fmaf(wT[4 * q4], v.x, part); part = __builtin_fmaf(wT[4 * q4 + 1], v.y, part);
-                        part = __builtin_fmaf(wT[4 * q4 + 2], v.z, part); part = __builtin_fmaf(wT[4 * q4 + 3], v.w, part);
-                    }
-                    part *= q16::qpass(hp, qa);
+                    const float part = qc_dot(wT, dv, 0.0f) * q16::qpass(hp, qa);
                     const float both = part + xor16(part);      // (the swap outside the select: every lane takes part in it)
                     carry = valid ? __builtin_fmaf(gh, f, both) : 0.0f;
                     if constexpr (NW) {      // the rows of unit col: d (x) q(h(t-1)), d (x) q(e), bias
                         const float d = is_f ? dfp : dgp;
-#pragma unroll
-                        for (int q4 = 0; q4 < 4; ++q4) {
-                            const float4 v = *reinterpret_cast<const float4*>(qh + 4 * q4);
-                            gr[4 * q4] = __builtin_fmaf(d, v.x, gr[4 * q4]); gr[4 * q4 + 1] = __builtin_fmaf(d, v.y, gr[4 * q4 + 1]);
-                            gr[4 * q4 + 2] = __builtin_fmaf(d, v.z, gr[4 * q4 + 2]); gr[4 * q4 + 3] = __builtin_fmaf(d, v.w, gr[4 * q4 + 3]);
-                        }
-                        const float* er = qe + ((is_f ? 0 : kQC) + tt) * kQE;
-#pragma unroll
-                        for (int q4 = 0; q4 < kQE / 4; ++q4) {
-                            const float4 v = *reinterpret_cast<const float4*>(er + 4 * q4);
-                            ge[4 * q4] = __builtin_fmaf(d, v.x, ge[4 * q4]); ge[4 * q4 + 1] = __builtin_fmaf(d, v.y, ge[4 * q4 + 1]);
-                            ge[4 * q4 + 2] = __builtin_fmaf(d, v.z, ge[4 * q4 + 2]); ge[4 * q4 + 3] = __builtin_fmaf(d, v.w, ge[4 * q4 + 3]);
-                        }
+                        qc_axpy(gr, d, qh);
+                        qc_axpy(ge, d, qe + ((is_f ? 0 : kQC) + tt) * kQE);
                         db += d;
                     }
                     wave_lds_fence();
@@ -429,12 +376,10 @@ __global__ __launch_bounds__(64) void bjq_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            float vi = dwi[j], vq_ = dwq[j];
-            for (int o = 32; o > 0; o >>= 1) { vi += __shfl_xor(vi, o); vq_ += __shfl_xor(vq_, o); }
+            const float vi = wave_sum64(dwi[j]), vq_ = wave_sum64(dwq[j]);
             if (lane == 0 && j < H) { gw[L.ow[6] + j] = vi; gw[L.ow[7] + j] = vq_; }
         }
         if (lane == 0) { gw[L.ob[6]] = tb0; gw[L.ob[7]] = tb1; }
@@ -449,32 +394,15 @@ __global__ __launch_bounds__(64) void bjq_bwd_kernel(SeqArgs a) {
         gw[L.ow[0] + fp0 * kQM + fm] = aI0; gw[L.ow[1] + fp0 * kQM + fm] = aQ0;
         if (lane < 32) { gw[L.ow[0] + fp1 * kQM + fm] = aI1; gw[L.ow[1] + fp1 * kQM + fm] = aQ1; }
         wave_lds_fence();
-        // weight quantisers' pass masks from the unquantised weights; scale columns exact zeros
-        q16::Quant qw[kQL];
-#pragma unroll
-        for (int l = 0; l < kQL; ++l) qw[l] = q16::make_quant(a.params[L.oq[l]], a.bits_w);
-        for (int i = lane; i < L.P + kLossCols; i += 64) {
-            float v = i < L.P ? gw[i] : 0.0f;
-#pragma unroll
-            for (int l = 0; l < kQL; ++l) {
-                if (i >= L.ow[l] && i < L.ob[l]) v *= q16::qpass(a.params[i], qw[l]);
-                if (i >= L.oq[l] && i < L.oq[l] + 3) v = 0.0f;
-            }
-            prow[i] = v;
-        }
+        qc_write_partials(a, L, gw, lane);
     }
 }
 
-template <typename K> int bjq_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 bool bojanet_q_ok(const odpd_model_t* m) {
     return m->backbone == ODPD_BOJANET && (m->flags & ODPD_FLAG_QUANT_CELL) && !(m->flags & (ODPD_FLAG_TWO_LAYERS | ODPD_FLAG_INIT_STATE)) &&
-           m->bits_w > 0 && m->bits_w <= 16 && m->bits_a > 0 && m->bits_a <= 16 && m->hidden >= 1 && m->hidden <= 16;
+           qc_bits_ok(m) && m->hidden >= 1 && m->hidden <= 16;
 }
 int64_t bojanet_q_param_count(const odpd_model_t* m) { return bjq_layout(m->hidden).P; }      // 2H^2 + 28H + 194 + 24
 int64_t bojanet_q_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * ((T + kQC - 1) / kQC) * 16; }      // h at the start of every chunk
@@ -484,7 +412,7 @@ int bojanet_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (a.T < kQM - 1) return ODPD_EINVAL;       // the reference cuts its 15-sample zero pad from the frame itself (bojanet.py:72-77)
     const size_t lds = (size_t)bjq_fwd_floats(bjq_layout(m->hidden).P) * sizeof(float);
     const int cap = 6 * device_cus(), grid = a.B < cap ? a.B : cap;
-    return a.ckpt ? bjq_launch(st, bjq_fwd_kernel<true>, grid, lds, a) : bjq_launch(st, bjq_fwd_kernel<false>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, bjq_fwd_kernel<true>, grid, lds, a) : launch_seq(st, bjq_fwd_kernel<false>, grid, lds, a);
 }
 int bojanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!bojanet_q_ok(m)) return ODPD_EUNSUPPORTED;
@@ -492,9 +420,9 @@ int bojanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)bjq_bwd_floats(bjq_layout(m->hidden).P) * sizeof(float);
     const int grid = bojanet_q_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return bjq_launch(st, bjq_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return bjq_launch(st, bjq_bwd_kernel<true, false>, grid, lds, a);
-    return bjq_launch(st, bjq_bwd_kernel<false, true>, grid, lds, a);
+    if (nw && dx) return launch_seq(st, bjq_bwd_kernel<true, true>, grid, lds, a);
+    if (nw) return launch_seq(st, bjq_bwd_kernel<true, false>, grid, lds, a);
+    return launch_seq(st, bjq_bwd_kernel<false, true>, grid, lds, a);
 }
 
 }  // namespace odpd

@@ -305,12 +305,6 @@ __global__ __launch_bounds__(64) void wide_deltajanet_bwd_kernel(SeqArgs a) {
     }
 }
 
-template <typename K>
-int dj_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 // deltajanet of 33 .. 64 hidden units; with a quantised head (bits_w > 0): every hidden size up to 64
@@ -327,8 +321,8 @@ int deltajanet_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a)
     const size_t lds = (size_t)dj_fwd_floats(dj_params(m)) * sizeof(float);
     const int grid = deltajanet_wide_rows(m, a.B);
     if (m->bits_w > 0)
-        return a.ckpt ? dj_launch(st, wide_deltajanet_fwd_kernel<true, true>, grid, lds, a) : dj_launch(st, wide_deltajanet_fwd_kernel<false, true>, grid, lds, a);
-    return a.ckpt ? dj_launch(st, wide_deltajanet_fwd_kernel<true, false>, grid, lds, a) : dj_launch(st, wide_deltajanet_fwd_kernel<false, false>, grid, lds, a);
+        return a.ckpt ? launch_seq(st, wide_deltajanet_fwd_kernel<true, true>, grid, lds, a) : launch_seq(st, wide_deltajanet_fwd_kernel<false, true>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, wide_deltajanet_fwd_kernel<true, false>, grid, lds, a) : launch_seq(st, wide_deltajanet_fwd_kernel<false, false>, grid, lds, a);
 }
 int deltajanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!deltajanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
@@ -337,13 +331,13 @@ int deltajanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a)
     const int grid = deltajanet_wide_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
     if (m->bits_w > 0) {
-        if (nw && dx) return dj_launch(st, wide_deltajanet_bwd_kernel<true, true, true>, grid, lds, a);
-        if (nw) return dj_launch(st, wide_deltajanet_bwd_kernel<true, false, true>, grid, lds, a);
-        return dj_launch(st, wide_deltajanet_bwd_kernel<false, true, true>, grid, lds, a);
+        if (nw && dx) return launch_seq(st, wide_deltajanet_bwd_kernel<true, true, true>, grid, lds, a);
+        if (nw) return launch_seq(st, wide_deltajanet_bwd_kernel<true, false, true>, grid, lds, a);
+        return launch_seq(st, wide_deltajanet_bwd_kernel<false, true, true>, grid, lds, a);
     }
-    if (nw && dx) return dj_launch(st, wide_deltajanet_bwd_kernel<true, true, false>, grid, lds, a);
-    if (nw) return dj_launch(st, wide_deltajanet_bwd_kernel<true, false, false>, grid, lds, a);
-    return dj_launch(st, wide_deltajanet_bwd_kernel<false, true, false>, grid, lds, a);
+    if (nw && dx) return launch_seq(st, wide_deltajanet_bwd_kernel<true, true, false>, grid, lds, a);
+    if (nw) return launch_seq(st, wide_deltajanet_bwd_kernel<true, false, false>, grid, lds, a);
+    return launch_seq(st, wide_deltajanet_bwd_kernel<false, true, false>, grid, lds, a);
 }
 
 }  // namespace odpd

@@ -5,14 +5,14 @@
 // functional and stay float; no module is named fc_out, so the 16-bit output quantiser never runs (train mode = eval mode).  Selected by
 // ODPD_FLAG_QUANT_CELL on ODPD_DVRJANET with bits_w, bits_a > 0; num_dvr_units (1 .. 8) rides in the descriptor's thx.
 //
-// ONE sequence per single-wave workgroup (the form of bojanet_q.hip), in chunks of 64 steps.  The parameters are staged in LDS with the nine weight
-// matrices quantised IN PLACE.  Per chunk:
+// ONE sequence per single-wave workgroup (the form of bojanet_q.hip), in chunks of 64 steps.  Parameter layout, setup (the parameters staged in
+// LDS with the nine weight matrices quantised IN PLACE) and write-out: odpd_qcell.h.  Per chunk:
 //   front       lane = time step: |x| = sqrt(I*I + Q*Q) (two rounded products, one add: the reference's order, no FMA), theta = atan2f(Q, I), both on
 //               the grid of the layer that reads them (q_ax(|x|), q_pθ(theta));
 //   recurrence  lane = (role, unit), role = lane / 16; each lane keeps two weight rows in registers, block A | block B:
 //                   role 0  W_ph | W_ccos[:, :H]      role 1  W_ah | W_csin[:, :H]      role 2  W_f | W_ccos[:, H:]      role 3  - | W_csin[:, H:]
 //               round 1: hs = h_I + h_Q on the grids of W_ph, W_ah, W_f, h_I on W_ccos's and h_Q on W_csin's grid are broadcast through LDS; th~, the
-//               DVR sum, f and the first halves of the two candidate rows; sin / cos by the straight-line routine of dvrjanet_s16.hip;
+//               DVR sum, f and the first halves of the two candidate rows; sin / cos by the straight-line sincosf_ (odpd_device.h);
 //               round 2: a~ cos th~ on W_ccos's grid, a~ sin th~ on W_csin's grid broadcast; roles 2 / 3 continue the row sums of roles 0 / 1 (one
 //               sum over the 2H inputs, k ascending), tanh; f, g_cos, g_sin broadcast; h' = fl(f h) + fl(fl(1 - f) g) on every lane;
 //   head        lane = time step: q_o1(h_I), q_o2(h_Q), both read-outs.
@@ -23,33 +23,25 @@
 // Backward: the chunks last to first from a checkpoint of (h_I, h_Q) per chunk — front and recurrence again (f, g_cos, g_sin, the DVR input, cos, sin
 // of every step parked in LDS), the read-outs' gradients with lane = time step, the reverse recurrence with lane = (role, unit) (the transposes of
 // the same two blocks in registers, every layer's activation pass mask; the weight gradients of the lane's two rows accumulate in its registers),
-// dL/dtheta and dL/d|x| through both input layers' masks and on to dL/dx with lane = time step.  Sums are in a fixed order, no atomics.  The weight
-// quantisers' pass masks are applied at write-out from the unquantised weights; the 27 scale columns are exact zeros.
+// dL/dtheta and dL/d|x| through both input layers' masks and on to dL/dx with lane = time step.  Sums are in a fixed order, no atomics.
 // Deviation: at a sample of exactly 0 + 0j the reference's dL/dx is NaN (0 * inf through sqrt, 0 / 0 through atan2); here it is 0.
-#include "odpd_seq.h"
-#include "odpd_quant.h"
+#include "odpd_qcell.h"
 
 #pragma clang fp contract(off)
 
 namespace odpd {
 namespace {
+using namespace qcell;
 constexpr int kVC = 64;                             // steps per chunk
 constexpr int kVP = 17;                             // row pitch of the [time][unit] buffers: conflict-free for lane = unit and for lane = time
 constexpr int kVL = 9;                              // 0 W_ph  1 W_pθ  2 W_ah  3 W_ax  4 W_f  5 W_ccos  6 W_csin  7 W_o1  8 W_o2 (named_parameters order)
 constexpr int kVK = 8;                              // DVR units at most
-struct DvqLayout { int H, K, ocs, ow[kVL], ob[kVL], oq[kVL], P; };      // cs; per layer: weight, bias (= oq without one), the three scales
+struct DvqLayout : QcLayout<kVL> { int H, K, ocs; };      // cs sits in front of the layers
 __host__ __device__ inline int dvq_nin(int l, int H) { return (l == 1 || l == 3) ? 1 : (l == 5 || l == 6) ? 2 * H : H; }
 __host__ __device__ inline int dvq_nout(int l, int H) { return l >= 7 ? 1 : H; }
 __host__ __device__ inline DvqLayout dvq_layout(int H, int K) {
-    DvqLayout L; L.H = H; L.K = K; int o = 0;
-    L.ocs = o; o += K;
-#pragma unroll
-    for (int l = 0; l < kVL; ++l) {
-        L.ow[l] = o; o += dvq_nout(l, H) * dvq_nin(l, H);
-        L.ob[l] = o; if (l >= 4) o += dvq_nout(l, H);
-        L.oq[l] = o; o += 3;
-    }
-    L.P = o;
+    DvqLayout L; L.H = H; L.K = K; L.ocs = 0;
+    qc_fill_layout(L, K, [H](int l) { return QcLinear{dvq_nout(l, H), dvq_nin(l, H), l >= 4}; });
     return L;
 }
 constexpr int kVHist = ((kVC + 1) * kVP + 3) & ~3;
@@ -58,55 +50,21 @@ constexpr int kVSmall = 8 * 16 + 48;                // the broadcast vectors of 
 __host__ __device__ inline int dvq_fwd_floats(int P) { return pad4(P) + 2 * kVC + 2 * kVHist + kVSmall; }
 __host__ __device__ inline int dvq_bwd_floats(int P) { return 2 * pad4(P) + 2 * kVC + 2 * kVHist + 8 * kVRec + kVSmall + 48 + 32 + 96; }
 
-__device__ __forceinline__ float dvq_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-// sin and cos to ~1 ulp for |x| < 2^15: the routine of dvrjanet_s16.hip (three-term Cody-Waite reduction to [-pi/4, pi/4], single-precision minimax
-// polynomials; straight-line code, no slow path)
-__device__ __forceinline__ void dvq_sincos(float x, float& s, float& c) {
-    const float k = __builtin_rintf(x * 0.6366197723675814f);
-    float r = __builtin_fmaf(k, -1.5703125f, x);
-    r = __builtin_fmaf(k, -4.837512969970703125e-4f, r);
-    r = __builtin_fmaf(k, -7.54978995489188e-8f, r);
-    const float z = r * r;
-    const float ps = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * r, r);
-    const float pc = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f),
-                                    z * z, __builtin_fmaf(z, -0.5f, 1.0f));
-    const int j = (int)k;
-    const float sv = (j & 1) ? pc : ps, cv = (j & 1) ? ps : pc;
-    s = (j & 2) ? -sv : sv;
-    c = ((j + 1) & 2) ? -cv : cv;
-}
 // what a lane of the recurrence holds besides its rows: the activation quantisers, the DVR coefficients and knots (wave-uniform), its own scalars
 struct DvqQ {
     q16::Quant a[kVL];
     float cs[kVK], knot[kVK];
     int K;
 };
-// stage the parameters, form the activation quantisers, quantise the nine weight matrices in the staged copy
+// the shared setup, then the DVR coefficients (cs is no layer's weight: the staged copy keeps it as it is) and knots
 __device__ __forceinline__ void dvq_setup(float* pl, const SeqArgs& a, const DvqLayout& L, DvqQ& Q, int lane) {
-    stage_params(pl, a.params, L.P);
-    wave_lds_fence();
-    q16::Quant qw[kVL];
-#pragma unroll
-    for (int l = 0; l < kVL; ++l) {
-        Q.a[l] = q16::make_quant(pl[L.oq[l] + 1], a.bits_a);
-        Q.a[l].s = dvq_uni(Q.a[l].s); Q.a[l].inv = dvq_uni(Q.a[l].inv);
-        qw[l] = q16::make_quant(pl[L.oq[l]], a.bits_w);
-    }
+    qc_setup<true>(pl, a, L, Q.a, lane);
     Q.K = L.K;
 #pragma unroll
     for (int k = 0; k < kVK; ++k) {
-        Q.cs[k] = k < L.K ? dvq_uni(pl[L.ocs + (k < L.K ? k : 0)]) : 0.0f;
+        Q.cs[k] = k < L.K ? qc_uni(pl[L.ocs + (k < L.K ? k : 0)]) : 0.0f;
         Q.knot[k] = (float)((double)(k + 1) / (double)L.K);      // (dvrjanet.py:38: the Python float k / num_k, rounded when it meets the fp32 tensor)
     }
-    wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < kVL; ++l) {
-        const int n = L.ob[l] - L.ow[l];
-        for (int i = lane; i < n; i += 64) pl[L.ow[l] + i] = q16::qapply(pl[L.ow[l] + i], qw[l]);
-    }
-    wave_lds_fence();
 }
 // a lane's choice among layout offsets / quantisers, made on values that are already loaded (a choice between two loads of the layout can come out
 // as one load from a chosen address, which puts the whole layout into scratch)
@@ -130,23 +88,6 @@ __device__ __forceinline__ float dvq_dvr(const DvqQ& Q, float v, float& sg) {
             sg += d > 0.0f ? Q.cs[k] : d < 0.0f ? -Q.cs[k] : 0.0f;
         }
     return at;
-}
-__device__ __forceinline__ float dvq_dot(const float (&w)[16], const float* v, float acc) {
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 x = *reinterpret_cast<const float4*>(v + 4 * q4);
-        acc = __builtin_fmaf(w[4 * q4], x.x, acc); acc = __builtin_fmaf(w[4 * q4 + 1], x.y, acc);
-        acc = __builtin_fmaf(w[4 * q4 + 2], x.z, acc); acc = __builtin_fmaf(w[4 * q4 + 3], x.w, acc);
-    }
-    return acc;
-}
-__device__ __forceinline__ void dvq_axpy(float (&g)[16], float d, const float* v) {
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 x = *reinterpret_cast<const float4*>(v + 4 * q4);
-        g[4 * q4] = __builtin_fmaf(d, x.x, g[4 * q4]); g[4 * q4 + 1] = __builtin_fmaf(d, x.y, g[4 * q4 + 1]);
-        g[4 * q4 + 2] = __builtin_fmaf(d, x.z, g[4 * q4 + 2]); g[4 * q4 + 3] = __builtin_fmaf(d, x.w, g[4 * q4 + 3]);
-    }
 }
 // the rows of lane (role, col): block A | block B of the table above (tr: their transposes — column col of the block)
 __device__ __forceinline__ void dvq_rows(const float* pl, const DvqLayout& L, int role, int col, bool tr, float (&wA)[16], float (&wB)[16]) {
@@ -182,13 +123,13 @@ __device__ __forceinline__ void dvq_recur(const DvqQ& Q, const float (&wA)[16], 
         vq[role * 16 + col] = q16::qapply(hs, qa);
         if (role < 2) vq[(4 + role) * 16 + col] = q16::qapply(role == 0 ? hI : hQ, qb);
         wave_lds_fence();
-        const float accA = dvq_dot(wA, vq + role * 16, 0.0f);
+        const float accA = qc_dot(wA, vq + role * 16, 0.0f);
         float accB = 0.0f;
-        if (role < 2) accB = dvq_dot(wB, vq + (4 + role) * 16, 0.0f);
+        if (role < 2) accB = qc_dot(wB, vq + (4 + role) * 16, 0.0f);
         // role 0: th~ and its sin / cos; role 1: the DVR input and sum; role 2: f
         const float pre = sc * io[(role & 1) * kVC + tt] + accA;
         float si, co, sg;
-        dvq_sincos(pre, si, co);
+        sincosf_(pre, si, co);
         const float at = dvq_dvr(Q, pre, sg);
         const float f0 = sigmoidf_(accA + bA);
         const float co1 = xor16(co), si1 = xor16(si);      // role 1 receives role 0's
@@ -200,7 +141,7 @@ __device__ __forceinline__ void dvq_recur(const DvqQ& Q, const float (&wA)[16], 
         const float part = __shfl_xor(accB, 32);            // roles 2 / 3 continue the sums of roles 0 / 1
         wave_lds_fence();
         if (role >= 2) {
-            const float g0 = tanhf_(dvq_dot(wB, vq + (4 + role) * 16, part) + bB);
+            const float g0 = tanhf_(qc_dot(wB, vq + (4 + role) * 16, part) + bB);
             if (role == 2) { ex[col] = f0; ex[16 + col] = g0; }
             else ex[32 + col] = g0;
         }
@@ -375,9 +316,9 @@ __global__ __launch_bounds__(64) void dvq_bwd_kernel(SeqArgs a, int K) {
                 wave_lds_fence();
                 const float dB = (role & 1) ? dps : dpc;
                 // round 1: block B's transpose on dL/d(g_cos pre) / dL/d(g_sin pre); role 2: W_f's on dL/d(f pre)
-                const float mB = dvq_dot(tB, db + ((role & 1) ? 32 : 16), 0.0f) * q16::qpass(vb, qb);
+                const float mB = qc_dot(tB, db + ((role & 1) ? 32 : 16), 0.0f) * q16::qpass(vb, qb);
                 float mA = 0.0f;
-                if (role == 2) mA = dvq_dot(tA, db, 0.0f) * q16::qpass(hs, qa);
+                if (role == 2) mA = qc_dot(tA, db, 0.0f) * q16::qpass(hs, qa);
                 const float dvs = xor16(mB);                          // role 2 holds dL/d(a~ cos), receives dL/d(a~ sin) from role 3
                 const float dat = mB * co + dvs * si;
                 const float dth = at * (dvs * co - mB * si), dap = dat * sg;
@@ -392,7 +333,7 @@ __global__ __launch_bounds__(64) void dvq_bwd_kernel(SeqArgs a, int K) {
                 }
                 wave_lds_fence();
                 // round 2: W_ph's transpose on dL/dth~ (role 0), W_ah's on dL/d(DVR input) (role 1)
-                if (role < 2) mA = dvq_dot(tA, dv + role * 16, 0.0f) * q16::qpass(hs, qa);
+                if (role < 2) mA = qc_dot(tA, dv + role * 16, 0.0f) * q16::qpass(hs, qa);
                 comb[role * 16 + col] = mA;
                 if (role < 2) comb[(4 + role) * 16 + col] = mB;
                 wave_lds_fence();
@@ -401,8 +342,8 @@ __global__ __launch_bounds__(64) void dvq_bwd_kernel(SeqArgs a, int K) {
                 cQ = valid ? __builtin_fmaf(gQ, f, dhs + comb[80 + col]) : 0.0f;
                 if constexpr (NW) {      // the lane's rows: d (x) q(input), its input-column entry, its biases
                     const float dA = role == 2 ? dpf : role < 2 ? dv[role * 16 + col] : 0.0f;
-                    dvq_axpy(gA, dA, vq + role * 16);
-                    dvq_axpy(gB, dB, vq + (4 + role) * 16);
+                    qc_axpy(gA, dA, vq + role * 16);
+                    qc_axpy(gB, dB, vq + (4 + role) * 16);
                     gsc = __builtin_fmaf(dA, io[(role & 1) * kVC + tt], gsc);
                     gbA += dA; gbB += dB;
                 }
@@ -432,18 +373,15 @@ __global__ __launch_bounds__(64) void dvq_bwd_kernel(SeqArgs a, int K) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            float v1 = dw1[j], v2 = dw2[j];
-            for (int o = 32; o > 0; o >>= 1) { v1 += __shfl_xor(v1, o); v2 += __shfl_xor(v2, o); }
+            const float v1 = wave_sum64(dw1[j]), v2 = wave_sum64(dw2[j]);
             if (lane == 0 && j < H) { gw[L.ow[7] + j] = v1; gw[L.ow[8] + j] = v2; }
         }
 #pragma unroll
         for (int k = 0; k < kVK; ++k) {
-            float v = role == 2 ? dcs[k] : 0.0f;
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            const float v = wave_sum64(role == 2 ? dcs[k] : 0.0f);
             if (lane == 0 && k < L.K) gw[L.ocs + k] = v;
         }
         if (lane == 0) { gw[L.ob[7]] = tb0; gw[L.ob[8]] = tb1; }
@@ -462,27 +400,10 @@ __global__ __launch_bounds__(64) void dvq_bwd_kernel(SeqArgs a, int K) {
             if (role >= 2) gw[obb + col] = gbB;
         }
         wave_lds_fence();
-        // weight quantisers' pass masks from the unquantised weights; scale columns exact zeros
-        q16::Quant qw[kVL];
-#pragma unroll
-        for (int l = 0; l < kVL; ++l) qw[l] = q16::make_quant(a.params[L.oq[l]], a.bits_w);
-        for (int i = lane; i < L.P + kLossCols; i += 64) {
-            float v = i < L.P ? gw[i] : 0.0f;
-#pragma unroll
-            for (int l = 0; l < kVL; ++l) {
-                if (i >= L.ow[l] && i < L.ob[l]) v *= q16::qpass(a.params[i], qw[l]);
-                if (i >= L.oq[l] && i < L.oq[l] + 3) v = 0.0f;
-            }
-            prow[i] = v;
-        }
+        qc_write_partials(a, L, gw, lane);
     }
 }
 
-template <typename Kn> int dvq_launch(hipStream_t st, Kn k, int grid, size_t lds, const SeqArgs& a, int K) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a, K);
-    return (int)hipGetLastError();
-}
 // num_dvr_units rides in thx as an exact small integer (thx / thh are otherwise the delta backbones' thresholds); 0: not one
 inline int dvq_units(const odpd_model_t* m) {
     const int K = (int)m->thx;
@@ -492,7 +413,7 @@ inline int dvq_units(const odpd_model_t* m) {
 
 bool dvrjanet_q_ok(const odpd_model_t* m) {
     return m->backbone == ODPD_DVRJANET && (m->flags & ODPD_FLAG_QUANT_CELL) && !(m->flags & (ODPD_FLAG_TWO_LAYERS | ODPD_FLAG_INIT_STATE)) &&
-           m->bits_w > 0 && m->bits_w <= 16 && m->bits_a > 0 && m->bits_a <= 16 && m->hidden >= 1 && m->hidden <= 16 && dvq_units(m) > 0;
+           qc_bits_ok(m) && m->hidden >= 1 && m->hidden <= 16 && dvq_units(m) > 0;
 }
 int64_t dvrjanet_q_param_count(const odpd_model_t* m) { return dvq_layout(m->hidden, dvq_units(m)).P; }      // K + 7H^2 + 7H + 2 + 27
 int64_t dvrjanet_q_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * ((T + kVC - 1) / kVC) * 32; }      // (h_I, h_Q) at the start of every chunk
@@ -502,7 +423,7 @@ int dvrjanet_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const int K = dvq_units(m);
     const size_t lds = (size_t)dvq_fwd_floats(dvq_layout(m->hidden, K).P) * sizeof(float);
     const int cap = 8 * device_cus(), grid = a.B < cap ? a.B : cap;
-    return a.ckpt ? dvq_launch(st, dvq_fwd_kernel<true>, grid, lds, a, K) : dvq_launch(st, dvq_fwd_kernel<false>, grid, lds, a, K);
+    return a.ckpt ? launch_seq(st, dvq_fwd_kernel<true>, grid, lds, a, K) : launch_seq(st, dvq_fwd_kernel<false>, grid, lds, a, K);
 }
 int dvrjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!dvrjanet_q_ok(m)) return ODPD_EUNSUPPORTED;
@@ -511,9 +432,9 @@ int dvrjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)dvq_bwd_floats(dvq_layout(m->hidden, K).P) * sizeof(float);
     const int grid = dvrjanet_q_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return dvq_launch(st, dvq_bwd_kernel<true, true>, grid, lds, a, K);
-    if (nw) return dvq_launch(st, dvq_bwd_kernel<true, false>, grid, lds, a, K);
-    return dvq_launch(st, dvq_bwd_kernel<false, true>, grid, lds, a, K);
+    if (nw && dx) return launch_seq(st, dvq_bwd_kernel<true, true>, grid, lds, a, K);
+    if (nw) return launch_seq(st, dvq_bwd_kernel<true, false>, grid, lds, a, K);
+    return launch_seq(st, dvq_bwd_kernel<false, true>, grid, lds, a, K);
 }
 
 }  // namespace odpd

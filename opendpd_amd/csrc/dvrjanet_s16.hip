@@ -102,23 +102,6 @@ __device__ __forceinline__ void v16_inputs(float2 xv, float& mag, float& theta) 
     mag = __builtin_amdgcn_sqrtf(__builtin_fmaf(xv.x, xv.x, xv.y * xv.y));
     theta = atan2f(xv.y, xv.x);
 }
-// sin and cos to ~1 ulp for |x| < 2^15 (the phases here are a few radians): three-term Cody-Waite reduction to [-pi/4, pi/4] and
-// the single-precision minimax polynomials; straight-line code (the device library's sincosf carries a Payne-Hanek slow path that
-// costs the backward kernel its registers)
-__device__ __forceinline__ void v16_sincos(float x, float& s, float& c) {
-    const float k = __builtin_rintf(x * 0.6366197723675814f);
-    float r = __builtin_fmaf(k, -1.5703125f, x);
-    r = __builtin_fmaf(k, -4.837512969970703125e-4f, r);
-    r = __builtin_fmaf(k, -7.54978995489188e-8f, r);
-    const float z = r * r;
-    const float ps = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * r, r);
-    const float pc = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f),
-                                    z * z, __builtin_fmaf(z, -0.5f, 1.0f));
-    const int j = (int)k;
-    const float sv = (j & 1) ? pc : ps, cv = (j & 1) ? ps : pc;
-    s = (j & 2) ? -sv : sv;
-    c = ((j + 1) & 2) ? -cv : cv;
-}
 // a table pointer the compiler may only use once `dep` exists: keeps the LDS operand loads of a later step from being hoisted above
 // the recurrence (all four steps' operands issued up front is what costs the registers)
 __device__ __forceinline__ TabPtr v16_after(TabPtr p, float dep) {
@@ -149,7 +132,7 @@ __device__ __forceinline__ void v16_cell_fwd(TabPtr tl, const V16Uni& U, float m
 #pragma unroll
     for (int k = 0; k < kDvrMaxK; ++k)
         ODPD_EACH4 at[i] = __builtin_fmaf(__builtin_fabsf(ap[i] - U.knot[k]), U.cs[k], at[i]);
-    ODPD_EACH4 { float sv, cv; v16_sincos(th[i], sv, cv); si[i] = sv; co[i] = cv; }
+    ODPD_EACH4 { float sv, cv; sincosf_(th[i], sv, cv); si[i] = sv; co[i] = cv; }
     f = sigmoid4_prescaled(pf);
     f32x4 pc = as_f32x4(tab_ld(tl, (V16::SC + 3) * 64)), ps = as_f32x4(tab_ld(tl, (V16::SC + 4) * 64));
     pc = v16_mv(tl, V16::FW + 3, hI, pc);
@@ -284,7 +267,7 @@ __device__ __forceinline__ void v16_bwd_block(TabPtr tl0, const V16Uni& U, V16Gr
                 float thv = th_s[si][i], apv = ap_s[si][i];
                 asm volatile("" : "+v"(thv), "+v"(apv) : "v"(dvc[i]));
                 float sv, cv;
-                v16_sincos(thv, sv, cv);
+                sincosf_(thv, sv, cv);
                 const float dat = __builtin_fmaf(dvc[i], cv, dvs[i] * sv);
                 float slope = 0.0f, av = 0.0f;
 #pragma unroll
@@ -563,7 +546,7 @@ __global__ __launch_bounds__(64) void dvr_gp_train_kernel(SeqArgs a, int K, DvrK
 #pragma unroll
                 for (int k = 0; k < kDvrMaxK; ++k) at = __builtin_fmaf(__builtin_fabsf(ap - U.knot[k]), U.cs[k], at);
                 float si, co;
-                v16_sincos(th, si, co);
+                sincosf_(th, si, co);
                 const float vc = at * co, vs = at * si;
                 const float opnd = vsel(rm.m[0], hI, vsel(rm.m[1], vc, vsel(rm.m[2], hQ, vs)));
                 float pb = rotdot(0.0f, wB, opnd);
@@ -745,7 +728,7 @@ __global__ __launch_bounds__(64) void dvr_gp_eval_kernel(SeqArgs a, int K, DvrKn
 #pragma unroll
                     for (int k = 0; k < kDvrMaxK; ++k) at = __builtin_fmaf(__builtin_fabsf(ap - U.knot[k]), U.cs[k], at);
                     float si, co;
-                    v16_sincos(th, si, co);
+                    sincosf_(th, si, co);
                     const float opnd = vsel(rm.m[0], hI, vsel(rm.m[1], at * co, vsel(rm.m[2], hQ, at * si)));
                     float pb = rotdot(0.0f, wB, opnd);
                     pb += xor16(pb);

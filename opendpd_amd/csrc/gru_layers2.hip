@@ -494,12 +494,6 @@ bool gru2_cfg(const odpd_model_t* m, int& FM) {
     }
 }
 int gru2_P(const odpd_model_t* m, int FM) { return gru2_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), FM == FEAT_DGRU6).P; }
-template <typename K>
-int gru2_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 // float gru / dgru / qgru / qgru_amp1 with two recurrent layers (ODPD_FLAG_TWO_LAYERS) of <= 32 hidden units
@@ -520,7 +514,7 @@ int gru2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)gru2_fwd_floats(gru2_P(m, FM), FM == FEAT_DGRU6) * sizeof(float);
     const int grid = gru2_rows(m, a.B);
 #define ODPD_GRU2_FWD(FM_, DG_) \
-    if (FM == FM_) return a.ckpt ? gru2_launch(st, gru2_fwd_kernel<FM_, DG_, true>, grid, lds, a) : gru2_launch(st, gru2_fwd_kernel<FM_, DG_, false>, grid, lds, a);
+    if (FM == FM_) return a.ckpt ? launch_seq(st, gru2_fwd_kernel<FM_, DG_, true>, grid, lds, a) : launch_seq(st, gru2_fwd_kernel<FM_, DG_, false>, grid, lds, a);
     ODPD_GRU2_FWD(FEAT_RAW2, false) ODPD_GRU2_FWD(FEAT_DGRU6, true) ODPD_GRU2_FWD(FEAT_Q4, false) ODPD_GRU2_FWD(FEAT_A4, false)
 #undef ODPD_GRU2_FWD
     return ODPD_EUNSUPPORTED;
@@ -534,9 +528,9 @@ int gru2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
 #define ODPD_GRU2_BWD(FM_, DG_)                                                                       \
     if (FM == FM_) {                                                                                  \
-        if (nw && dx) return gru2_launch(st, gru2_bwd_kernel<FM_, DG_, true, true>, grid, lds, a);    \
-        if (nw) return gru2_launch(st, gru2_bwd_kernel<FM_, DG_, true, false>, grid, lds, a);         \
-        return gru2_launch(st, gru2_bwd_kernel<FM_, DG_, false, true>, grid, lds, a);                 \
+        if (nw && dx) return launch_seq(st, gru2_bwd_kernel<FM_, DG_, true, true>, grid, lds, a);     \
+        if (nw) return launch_seq(st, gru2_bwd_kernel<FM_, DG_, true, false>, grid, lds, a);          \
+        return launch_seq(st, gru2_bwd_kernel<FM_, DG_, false, true>, grid, lds, a);                  \
     }
     ODPD_GRU2_BWD(FEAT_RAW2, false) ODPD_GRU2_BWD(FEAT_DGRU6, true) ODPD_GRU2_BWD(FEAT_Q4, false) ODPD_GRU2_BWD(FEAT_A4, false)
 #undef ODPD_GRU2_BWD

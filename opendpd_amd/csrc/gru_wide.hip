@@ -78,12 +78,6 @@ bool wide_cfg(const odpd_model_t* m, int& FM, bool& DG) {
     }
 }
 int wide_P(const odpd_model_t* m, int FM, bool DG) { return gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P; }
-template <typename K>
-int wide_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 // float gru / dgru / qgru / qgru_amp1 of 33 .. 64 hidden units
@@ -99,7 +93,7 @@ int gru_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)wide_fwd_floats(wide_P(m, FM, DG), DG, m->hidden) * sizeof(float);
     const int grid = gru_wide_rows(m, a.B);
 #define ODPD_WIDE_FWD(FM_, DG_) \
-    if (FM == FM_) return a.ckpt ? wide_launch(st, wide_gru_fwd_kernel<FM_, DG_, true>, grid, lds, a) : wide_launch(st, wide_gru_fwd_kernel<FM_, DG_, false>, grid, lds, a);
+    if (FM == FM_) return a.ckpt ? launch_seq(st, wide_gru_fwd_kernel<FM_, DG_, true>, grid, lds, a) : launch_seq(st, wide_gru_fwd_kernel<FM_, DG_, false>, grid, lds, a);
     ODPD_WIDE_FWD(FEAT_RAW2, false) ODPD_WIDE_FWD(FEAT_DGRU6, true) ODPD_WIDE_FWD(FEAT_Q4, false) ODPD_WIDE_FWD(FEAT_A4, false)
 #undef ODPD_WIDE_FWD
     return ODPD_EUNSUPPORTED;
@@ -113,9 +107,9 @@ int gru_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
 #define ODPD_WIDE_BWD(FM_, DG_)                                                                              \
     if (FM == FM_) {                                                                                         \
-        if (nw && dx) return wide_launch(st, wide_gru_bwd_kernel<FM_, DG_, true, true>, grid, lds, a);       \
-        if (nw) return wide_launch(st, wide_gru_bwd_kernel<FM_, DG_, true, false>, grid, lds, a);            \
-        return wide_launch(st, wide_gru_bwd_kernel<FM_, DG_, false, true>, grid, lds, a);                    \
+        if (nw && dx) return launch_seq(st, wide_gru_bwd_kernel<FM_, DG_, true, true>, grid, lds, a);        \
+        if (nw) return launch_seq(st, wide_gru_bwd_kernel<FM_, DG_, true, false>, grid, lds, a);             \
+        return launch_seq(st, wide_gru_bwd_kernel<FM_, DG_, false, true>, grid, lds, a);                     \
     }
     ODPD_WIDE_BWD(FEAT_RAW2, false) ODPD_WIDE_BWD(FEAT_DGRU6, true) ODPD_WIDE_BWD(FEAT_Q4, false) ODPD_WIDE_BWD(FEAT_A4, false)
 #undef ODPD_WIDE_BWD
@@ -134,7 +128,7 @@ int gru_state_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)wide_fwd_floats(wide_P(m, FM, DG), DG, m->hidden) * sizeof(float);
     const int grid = gru_wide_rows(m, a.B);
 #define ODPD_STATE_FWD(FM_, DG_) \
-    if (FM == FM_) return a.ckpt ? wide_launch(st, wide_gru_fwd_state_kernel<FM_, DG_, true>, grid, lds, a) : wide_launch(st, wide_gru_fwd_state_kernel<FM_, DG_, false>, grid, lds, a);
+    if (FM == FM_) return a.ckpt ? launch_seq(st, wide_gru_fwd_state_kernel<FM_, DG_, true>, grid, lds, a) : launch_seq(st, wide_gru_fwd_state_kernel<FM_, DG_, false>, grid, lds, a);
     ODPD_STATE_FWD(FEAT_RAW2, false) ODPD_STATE_FWD(FEAT_DGRU6, true) ODPD_STATE_FWD(FEAT_Q4, false) ODPD_STATE_FWD(FEAT_A4, false)
 #undef ODPD_STATE_FWD
     return ODPD_EUNSUPPORTED;
@@ -148,10 +142,10 @@ int gru_state_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;      // (neither: dL/dh0 alone)
 #define ODPD_STATE_BWD(FM_, DG_)                                                                                   \
     if (FM == FM_) {                                                                                               \
-        if (nw && dx) return wide_launch(st, wide_gru_bwd_state_kernel<FM_, DG_, true, true>, grid, lds, a);       \
-        if (nw) return wide_launch(st, wide_gru_bwd_state_kernel<FM_, DG_, true, false>, grid, lds, a);            \
-        if (dx) return wide_launch(st, wide_gru_bwd_state_kernel<FM_, DG_, false, true>, grid, lds, a);            \
-        return wide_launch(st, wide_gru_bwd_state_kernel<FM_, DG_, false, false>, grid, lds, a);                   \
+        if (nw && dx) return launch_seq(st, wide_gru_bwd_state_kernel<FM_, DG_, true, true>, grid, lds, a);        \
+        if (nw) return launch_seq(st, wide_gru_bwd_state_kernel<FM_, DG_, true, false>, grid, lds, a);             \
+        if (dx) return launch_seq(st, wide_gru_bwd_state_kernel<FM_, DG_, false, true>, grid, lds, a);             \
+        return launch_seq(st, wide_gru_bwd_state_kernel<FM_, DG_, false, false>, grid, lds, a);                    \
     }
     ODPD_STATE_BWD(FEAT_RAW2, false) ODPD_STATE_BWD(FEAT_DGRU6, true) ODPD_STATE_BWD(FEAT_Q4, false) ODPD_STATE_BWD(FEAT_A4, false)
 #undef ODPD_STATE_BWD

@@ -303,12 +303,6 @@ __global__ __launch_bounds__(64) void wide_pgjanet_bwd_kernel(SeqArgs a) {
     }
 }
 
-template <typename K>
-int jw_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 // pgjanet of 17 .. 32 hidden units
@@ -319,7 +313,7 @@ int pgjanet_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)jw_fwd_floats(janet_layout(m->hidden).P) * sizeof(float);
     const int grid = pgjanet_wide_rows(m, a.B);
-    return a.ckpt ? jw_launch(st, wide_pgjanet_fwd_kernel<true>, grid, lds, a) : jw_launch(st, wide_pgjanet_fwd_kernel<false>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, wide_pgjanet_fwd_kernel<true>, grid, lds, a) : launch_seq(st, wide_pgjanet_fwd_kernel<false>, grid, lds, a);
 }
 int pgjanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
@@ -327,9 +321,9 @@ int pgjanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)jw_bwd_floats(janet_layout(m->hidden).P) * sizeof(float);
     const int grid = pgjanet_wide_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return jw_launch(st, wide_pgjanet_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return jw_launch(st, wide_pgjanet_bwd_kernel<true, false>, grid, lds, a);
-    return jw_launch(st, wide_pgjanet_bwd_kernel<false, true>, grid, lds, a);
+    if (nw && dx) return launch_seq(st, wide_pgjanet_bwd_kernel<true, true>, grid, lds, a);
+    if (nw) return launch_seq(st, wide_pgjanet_bwd_kernel<true, false>, grid, lds, a);
+    return launch_seq(st, wide_pgjanet_bwd_kernel<false, true>, grid, lds, a);
 }
 
 }  // namespace odpd

@@ -280,12 +280,6 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
     }
 }
 
-template <typename K>
-int lstm2_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 // float lstm with two recurrent layers (ODPD_FLAG_TWO_LAYERS) of <= 32 hidden units
@@ -299,7 +293,7 @@ int lstm2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm2_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)lstm2_fwd_floats(lstm2_layout(m->hidden).P) * sizeof(float);
     const int grid = lstm2_rows(m, a.B);
-    return a.ckpt ? lstm2_launch(st, lstm2_fwd_kernel<true>, grid, lds, a) : lstm2_launch(st, lstm2_fwd_kernel<false>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, lstm2_fwd_kernel<true>, grid, lds, a) : launch_seq(st, lstm2_fwd_kernel<false>, grid, lds, a);
 }
 int lstm2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm2_ok(m)) return ODPD_EUNSUPPORTED;
@@ -307,9 +301,9 @@ int lstm2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)lstm2_bwd_floats(lstm2_layout(m->hidden).P) * sizeof(float);
     const int grid = lstm2_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return lstm2_launch(st, lstm2_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return lstm2_launch(st, lstm2_bwd_kernel<true, false>, grid, lds, a);
-    return lstm2_launch(st, lstm2_bwd_kernel<false, true>, grid, lds, a);
+    if (nw && dx) return launch_seq(st, lstm2_bwd_kernel<true, true>, grid, lds, a);
+    if (nw) return launch_seq(st, lstm2_bwd_kernel<true, false>, grid, lds, a);
+    return launch_seq(st, lstm2_bwd_kernel<false, true>, grid, lds, a);
 }
 
 }  // namespace odpd

@@ -46,12 +46,6 @@ __global__ __launch_bounds__(64) void wide_lstm_bwd_state_kernel(SeqArgs a) {
 #include "lstm_wide_bwd_body.h"
 }
 
-template <typename K>
-int lstmw_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 // lstm of 33 .. 64 hidden units, float or with a quantised head (bits_w > 0: fc_out as INT_Linear; vdlstm's quantised heads keep the 32-unit envelope)
@@ -65,7 +59,7 @@ int lstm_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)lstmw_fwd_floats(lstm_layout(m->hidden, 0, m->bits_w > 0).P) * sizeof(float);
     const int grid = lstm_wide_rows(m, a.B);
-    return a.ckpt ? lstmw_launch(st, wide_lstm_fwd_kernel<true>, grid, lds, a) : lstmw_launch(st, wide_lstm_fwd_kernel<false>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, wide_lstm_fwd_kernel<true>, grid, lds, a) : launch_seq(st, wide_lstm_fwd_kernel<false>, grid, lds, a);
 }
 int lstm_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm_wide_ok(m)) return ODPD_EUNSUPPORTED;
@@ -73,9 +67,9 @@ int lstm_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)lstmw_bwd_floats(lstm_layout(m->hidden, 0, m->bits_w > 0).P) * sizeof(float);
     const int grid = lstm_wide_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return lstmw_launch(st, wide_lstm_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return lstmw_launch(st, wide_lstm_bwd_kernel<true, false>, grid, lds, a);
-    return lstmw_launch(st, wide_lstm_bwd_kernel<false, true>, grid, lds, a);
+    if (nw && dx) return launch_seq(st, wide_lstm_bwd_kernel<true, true>, grid, lds, a);
+    if (nw) return launch_seq(st, wide_lstm_bwd_kernel<true, false>, grid, lds, a);
+    return launch_seq(st, wide_lstm_bwd_kernel<false, true>, grid, lds, a);
 }
 
 // the state route: float lstm of 1 .. 64 hidden units, one layer, from a caller-given initial state (a.h0 = h(-1) = c(-1))
@@ -87,7 +81,7 @@ int lstm_state_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!a.h0) return ODPD_EINVAL;
     const size_t lds = (size_t)lstmw_fwd_floats(lstm_layout(m->hidden, 0, false).P) * sizeof(float);
     const int grid = lstm_wide_rows(m, a.B);
-    return a.ckpt ? lstmw_launch(st, wide_lstm_fwd_state_kernel<true>, grid, lds, a) : lstmw_launch(st, wide_lstm_fwd_state_kernel<false>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, wide_lstm_fwd_state_kernel<true>, grid, lds, a) : launch_seq(st, wide_lstm_fwd_state_kernel<false>, grid, lds, a);
 }
 int lstm_state_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm_state_ok(m)) return ODPD_EUNSUPPORTED;
@@ -95,10 +89,10 @@ int lstm_state_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)lstmw_bwd_floats(lstm_layout(m->hidden, 0, false).P) * sizeof(float);
     const int grid = lstm_wide_rows(m, a.B);
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;      // (neither: dL/dh0 alone)
-    if (nw && dx) return lstmw_launch(st, wide_lstm_bwd_state_kernel<true, true>, grid, lds, a);
-    if (nw) return lstmw_launch(st, wide_lstm_bwd_state_kernel<true, false>, grid, lds, a);
-    if (dx) return lstmw_launch(st, wide_lstm_bwd_state_kernel<false, true>, grid, lds, a);
-    return lstmw_launch(st, wide_lstm_bwd_state_kernel<false, false>, grid, lds, a);
+    if (nw && dx) return launch_seq(st, wide_lstm_bwd_state_kernel<true, true>, grid, lds, a);
+    if (nw) return launch_seq(st, wide_lstm_bwd_state_kernel<true, false>, grid, lds, a);
+    if (dx) return launch_seq(st, wide_lstm_bwd_state_kernel<false, true>, grid, lds, a);
+    return launch_seq(st, wide_lstm_bwd_state_kernel<false, false>, grid, lds, a);
 }
 
 }  // namespace odpd

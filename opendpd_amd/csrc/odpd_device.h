@@ -90,6 +90,11 @@ __device__ __forceinline__ float sum_rows4(float v) {
     const HalfDup q = dup32(p.even + p.odd);
     return q.lo + q.hi;
 }
+// sum over all 64 lanes, every lane receives it: halves first (lane i + lane i ^ 32), then 16, 8, 4, 2, 1
+__device__ __forceinline__ float wave_sum64(float v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 // Row select without control flow: a ?: on the row index can come out as exec-mask branches inside a step loop, and an inline-asm
 // v_cndmask hides its VGPR write from the compiler's MFMA hazard handling (a following v_mfma read the stale operand).  So: per-lane
 // all-ones / zero masks, made opaque once at kernel start, and a bitwise blend (one v_bfi_b32).
@@ -345,6 +350,23 @@ __device__ __forceinline__ float tanhf_(float v) {
 __device__ __forceinline__ float hardswishf_(float v) {
     float r = __builtin_fminf(__builtin_fmaxf(v + 3.0f, 0.0f), 6.0f);
     return v * r * (1.0f / 6.0f);
+}
+// sin and cos to ~1 ulp for |x| < 2^15 (the phases here are a few radians): three-term Cody-Waite reduction to [-pi/4, pi/4] and
+// the single-precision minimax polynomials; straight-line code (the device library's sincosf carries a Payne-Hanek slow path that
+// costs the backward kernel its registers).  Explicit FMAs and single multiplies: the same code with FP contraction on or off.
+__device__ __forceinline__ void sincosf_(float x, float& s, float& c) {
+    const float k = __builtin_rintf(x * 0.6366197723675814f);
+    float r = __builtin_fmaf(k, -1.5703125f, x);
+    r = __builtin_fmaf(k, -4.837512969970703125e-4f, r);
+    r = __builtin_fmaf(k, -7.54978995489188e-8f, r);
+    const float z = r * r;
+    const float ps = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * r, r);
+    const float pc = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f),
+                                    z * z, __builtin_fmaf(z, -0.5f, 1.0f));
+    const int j = (int)k;
+    const float sv = (j & 1) ? pc : ps, cv = (j & 1) ? ps : pc;
+    s = (j & 2) ? -sv : sv;
+    c = ((j + 1) & 2) ? -cv : cv;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -200,6 +200,17 @@ static inline int allow_big_lds(K kernel, size_t lds) {
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)kMaxLds);
 }
+// launch `kernel` with `lds` bytes of dynamic LDS on `grid` workgroups of `block` threads; launch_seq: single-wave workgroups
+template <typename K, typename... Args>
+static inline int launch_lds(hipStream_t st, K kernel, int grid, int block, size_t lds, const Args&... args) {
+    if (int e = allow_big_lds(kernel, lds)) return e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, args...);
+    return (int)hipGetLastError();
+}
+template <typename K, typename... Args>
+static inline int launch_seq(hipStream_t st, K kernel, int grid, size_t lds, const Args&... args) {
+    return launch_lds(st, kernel, grid, 64, lds, args...);
+}
 static inline size_t reduce_scratch_bytes(int P, int waves) { return (size_t)waves * (P + kLossCols) * sizeof(float); }
 
 }  // namespace odpd

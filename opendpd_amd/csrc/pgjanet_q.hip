@@ -4,30 +4,26 @@
 // tanh / sigmoid calls are functional and stay float; no module is named fc_out, so the 16-bit output quantiser never runs.
 //
 // A plain kernel pair next to the float ones (janet_family.hip, janet_s16.hip, janet_wide.hip): ONE sequence per single-wave workgroup, LANE =
-// HIDDEN UNIT (hidden <= 32).  The parameters are staged in LDS with the six weight matrices quantised IN PLACE; per step the lane of unit k
+// HIDDEN UNIT (hidden <= 32).  Parameter layout, setup (the parameters staged in LDS with the six weight matrices quantised IN PLACE) and
+// write-out: odpd_qcell.h.  Per step the lane of unit k
 // writes q_l(h_k) for the five gate layers (and q_l(u_k) for W_f, W_g) to LDS, the lane of unit j runs its rows against those broadcasts (row
 // reads: lanes stride H + 1 / 2 H floats apart; transposed reads in the backward pass: consecutive lanes, consecutive addresses).  The
 // forward pass records (a_n, p1, p2, u, f, g, h') per step in HBM (`ckpt`: B x T x 8 x 64 floats) when a backward pass follows.  Backward:
 // reverse steps, the gate gradients broadcast through LDS, the transposed mat-vecs with every layer's activation pass mask, the weight
-// gradients accumulated in the registers of the lane that owns the rows (deposited in a second LDS copy of the parameter layout at the end), the weight
-// quantisers' pass masks applied at write-out from the unquantised weights, the 18 scale columns exact zeros.
-#include "odpd_seq.h"
-#include "odpd_quant.h"
+// gradients accumulated in the registers of the lane that owns the rows (deposited in a second LDS copy of the parameter layout at the end).
+#include "odpd_qcell.h"
 
 #pragma clang fp contract(off)
 
 namespace odpd {
 namespace {
+using namespace qcell;
 constexpr int kPC = 64, kPS = 33, kPNS = 8;
-struct PgqLayout { int H, ow[6], ob[6], oq[6], P; };      // 0 W_a  1 W_p1  2 W_p2  3 W_f  4 W_g  5 W_o
+struct PgqLayout : QcLayout<6> { int H; };      // 0 W_a  1 W_p1  2 W_p2  3 W_f  4 W_g  5 W_o
 __host__ __device__ inline int pgq_nin(int l, int H) { return l < 3 ? H + 1 : (l < 5 ? 2 * H : H); }
 __host__ __device__ inline PgqLayout pgq_layout(int H) {
-    PgqLayout L; L.H = H; int o = 0;
-    for (int l = 0; l < 6; ++l) {
-        const int nout = l < 5 ? H : 2;
-        L.ow[l] = o; o += nout * pgq_nin(l, H); L.ob[l] = o; o += nout; L.oq[l] = o; o += 3;
-    }
-    L.P = o;
+    PgqLayout L; L.H = H;
+    qc_fill_layout(L, 0, [H](int l) { return QcLinear{l < 5 ? H : 2, pgq_nin(l, H), true}; });
     return L;
 }
 __host__ __device__ inline int pgq_fwd_floats(int P) { return pad4(P) + kPC * 4 + 8 * 32 + kPC * kPS; }
@@ -39,24 +35,7 @@ __device__ __forceinline__ void pgq_stage_inputs(float* ftab, const float2* xg, 
     const float am = sqrtf(xv.x * xv.x + xv.y * xv.y);
     reinterpret_cast<float4*>(ftab)[lane] = make_float4(am, xv.x / am, xv.y / am, 0.0f);
 }
-struct PgqQ { q16::Quant a[6]; };
-// stage the parameters, form the activation quantisers, quantise the six weight matrices in the staged copy
-__device__ __forceinline__ void pgq_setup(float* pl, const SeqArgs& a, const PgqLayout& L, PgqQ& Q, int lane) {
-    stage_params(pl, a.params, L.P);
-    wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < 6; ++l) Q.a[l] = q16::make_quant(pl[L.oq[l] + 1], a.bits_a);
-    q16::Quant qw[6];
-#pragma unroll
-    for (int l = 0; l < 6; ++l) qw[l] = q16::make_quant(pl[L.oq[l]], a.bits_w);
-    wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < 6; ++l) {
-        const int n = (l < 5 ? L.H : 2) * pgq_nin(l, L.H);
-        for (int i = lane; i < n; i += 64) pl[L.ow[l] + i] = q16::qapply(pl[L.ow[l] + i], qw[l]);
-    }
-    wave_lds_fence();
-}
+struct PgqQ { q16::Quant a[6]; };      // the layers' activation quantisers
 
 // Forward.  HP = padded unit count (16: hidden <= 16, 32: hidden 17 .. 32).  The wave's two halves split a unit's five gate rows, all of them in
 // REGISTERS: lane j < 32 holds the a_n / p1 / p2 rows of unit j, lane 32 + j its f / g rows (h part and u part) and the state h_j.  A step is two
@@ -77,7 +56,7 @@ __global__ __launch_bounds__(64) void pgq_fwd_kernel(SeqArgs a) {
     float* vq = ftab + kPC * 4;                // [8][32]: q_l(h) for l = 0 .. 4, q_3(u), q_4(u)
     float* hist = vq + 8 * 32;                 // [64][33]: h of the chunk's steps
     PgqQ Q;
-    pgq_setup(pl, a, L, Q, lane);
+    qc_setup<false>(pl, a, L, Q.a, lane);
     const bool up = lane >= 32;
     const int j0 = lane & 31;
     const bool vo = j0 < H;
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(64) void pgq_bwd_kernel(SeqArgs a) {
     float* dyb = dxb + kPC * 2;                // [64][2]  dL/dy of the chunk's steps
     float* vb = dyb + kPC * 2;                 // [16][32] 0..4 q_l(h(t-1)), 5 q_3(u), 6 q_4(u), 7 d_f, 8 d_g, 9 d_a, 10 d_p1, 11 d_p2
     PgqQ Q;
-    pgq_setup(pl, a, L, Q, lane);
+    qc_setup<false>(pl, a, L, Q.a, lane);
     for (int i = lane; i < pad4(L.P); i += 64) gw[i] = 0.0f;
     for (int i = lane; i < 16 * 32; i += 64) vb[i] = 0.0f;
     const bool up = lane >= 32;
@@ -314,9 +293,7 @@ __global__ __launch_bounds__(64) void pgq_bwd_kernel(SeqArgs a) {
                     for (int l = 0; l < 3; ++l) {
                         dhp = __builtin_fmaf(q16::qpass(hp, Q.a[l]), dup32(ah[l]).lo, dhp);      // (the lower half's sum, on the upper half)
                         if constexpr (DX) {      // the scalar input's column: sum over the units
-                            float v = wsc[l] * dpre[l];
-                            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-                            dsc[l] = v * q16::qpass(sc[l], Q.a[l]);
+                            dsc[l] = wave_sum64(wsc[l] * dpre[l]) * q16::qpass(sc[l], Q.a[l]);
                         }
                     }
                 }
@@ -354,8 +331,7 @@ __global__ __launch_bounds__(64) void pgq_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
         if (vo && !up) {
 #pragma unroll
             for (int l = 0; l < 3; ++l) {
@@ -376,31 +352,14 @@ __global__ __launch_bounds__(64) void pgq_bwd_kernel(SeqArgs a) {
         }
         if (lane == 0) { gw[L.ob[5]] = tb0; gw[L.ob[5] + 1] = tb1; }
         wave_lds_fence();
-        // weight quantisers' pass masks from the unquantised weights; scale columns exact zeros
-        q16::Quant qw[6];
-#pragma unroll
-        for (int l = 0; l < 6; ++l) qw[l] = q16::make_quant(a.params[L.oq[l]], a.bits_w);
-        for (int i = lane; i < L.P + kLossCols; i += 64) {
-            float v = i < L.P ? gw[i] : 0.0f;
-#pragma unroll
-            for (int l = 0; l < 6; ++l) {
-                if (i >= L.ow[l] && i < L.ob[l]) v *= q16::qpass(a.params[i], qw[l]);
-                if (i >= L.oq[l] && i < L.oq[l] + 3) v = 0.0f;
-            }
-            prow[i] = v;
-        }
+        qc_write_partials(a, L, gw, lane);
     }
 }
 
-template <typename K> int pgq_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 bool pgjanet_q_ok(const odpd_model_t* m) {
-    return m->backbone == ODPD_PGJANET && m->bits_w > 0 && m->bits_w <= 16 && m->bits_a > 0 && m->bits_a <= 16 && m->hidden >= 1 && m->hidden <= 32 &&
+    return m->backbone == ODPD_PGJANET && qc_bits_ok(m) && m->hidden >= 1 && m->hidden <= 32 &&
            !(m->flags & ODPD_FLAG_TWO_LAYERS);
 }
 int64_t pgjanet_q_param_count(const odpd_model_t* m) { return pgq_layout(m->hidden).P; }
@@ -410,8 +369,8 @@ int pgjanet_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_q_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)pgq_fwd_floats(pgq_layout(m->hidden).P) * sizeof(float);
     const int grid = pgjanet_q_rows(m, a.B);
-    if (m->hidden <= 16) return a.ckpt ? pgq_launch(st, pgq_fwd_kernel<16, true>, grid, lds, a) : pgq_launch(st, pgq_fwd_kernel<16, false>, grid, lds, a);
-    return a.ckpt ? pgq_launch(st, pgq_fwd_kernel<32, true>, grid, lds, a) : pgq_launch(st, pgq_fwd_kernel<32, false>, grid, lds, a);
+    if (m->hidden <= 16) return a.ckpt ? launch_seq(st, pgq_fwd_kernel<16, true>, grid, lds, a) : launch_seq(st, pgq_fwd_kernel<16, false>, grid, lds, a);
+    return a.ckpt ? launch_seq(st, pgq_fwd_kernel<32, true>, grid, lds, a) : launch_seq(st, pgq_fwd_kernel<32, false>, grid, lds, a);
 }
 int pgjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_q_ok(m)) return ODPD_EUNSUPPORTED;
@@ -421,9 +380,9 @@ int pgjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
 #define ODPD_PGQ_BWD(HP_)                                                                           \
     {                                                                                              \
-        if (nw && dx) return pgq_launch(st, pgq_bwd_kernel<HP_, true, true>, grid, lds, a);        \
-        if (nw) return pgq_launch(st, pgq_bwd_kernel<HP_, true, false>, grid, lds, a);             \
-        return pgq_launch(st, pgq_bwd_kernel<HP_, false, true>, grid, lds, a);                     \
+        if (nw && dx) return launch_seq(st, pgq_bwd_kernel<HP_, true, true>, grid, lds, a);         \
+        if (nw) return launch_seq(st, pgq_bwd_kernel<HP_, true, false>, grid, lds, a);              \
+        return launch_seq(st, pgq_bwd_kernel<HP_, false, true>, grid, lds, a);                      \
     }
     if (m->hidden <= 16) ODPD_PGQ_BWD(16)
     ODPD_PGQ_BWD(32)

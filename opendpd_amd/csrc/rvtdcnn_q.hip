@@ -17,7 +17,7 @@
 #include <utility>
 
 #include "odpd_s16.h"
-#include "odpd_quant.h"
+#include "odpd_qcell.h"
 
 #pragma clang fp contract(off)
 
@@ -330,22 +330,17 @@ inline int rvq_grid(int B, int T) {
     const long long cap = 2LL * device_cus();
     return (int)(np < cap ? (np < 1 ? 1 : np) : cap);
 }
-template <typename K> int rvq_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kQT), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 bool rvtdcnn_q_ok(const odpd_model_t* m, int T) {
-    return m->backbone == ODPD_RVTDCNN && m->bits_w > 0 && m->bits_w <= 16 && m->bits_a > 0 && m->bits_a <= 16 && m->hidden >= 1 && m->hidden <= 32 && T >= 3;
+    return m->backbone == ODPD_RVTDCNN && qcell::qc_bits_ok(m) && m->hidden >= 1 && m->hidden <= 32 && T >= 3;
 }
 int64_t rvtdcnn_q_param_count(const odpd_model_t* m) { return rvq_layout(m->hidden).P; }
 int rvtdcnn_q_rows(const odpd_model_t*, int B, int T) { return rvq_grid(B, T); }
 int rvtdcnn_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!rvtdcnn_q_ok(m, a.T)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)pad4(rvq_layout(m->hidden).P) * sizeof(float);
-    return rvq_launch(st, rvq_kernel<0, false>, rvq_grid(a.B, a.T), lds, a);
+    return launch_lds(st, rvq_kernel<0, false>, rvq_grid(a.B, a.T), kQT, lds, a);
 }
 // dy -> partials and / or dx; `fused`: a.target instead of a.dy, loss in column P of the partial rows
 int rvtdcnn_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, bool fused) {
@@ -354,9 +349,9 @@ int rvtdcnn_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, bool 
     const int grid = rvq_grid(a.B, a.T);
     if (a.partials != nullptr) {
         const size_t lds = (size_t)(pad4(L.P) + 4 * pad4(L.P + kLossCols) + 4 * kQTile) * sizeof(float);
-        if (int e = fused ? rvq_launch(st, rvq_kernel<1, true>, grid, lds, a) : rvq_launch(st, rvq_kernel<1, false>, grid, lds, a)) return e;
+        if (int e = fused ? launch_lds(st, rvq_kernel<1, true>, grid, kQT, lds, a) : launch_lds(st, rvq_kernel<1, false>, grid, kQT, lds, a)) return e;
     }
-    if (a.dx != nullptr && !fused) return rvq_launch(st, rvq_kernel<2, false>, grid, (size_t)pad4(L.P) * sizeof(float), a);
+    if (a.dx != nullptr && !fused) return launch_lds(st, rvq_kernel<2, false>, grid, kQT, (size_t)pad4(L.P) * sizeof(float), a);
     return 0;
 }
 

@@ -387,9 +387,7 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
 template <typename K>
 int vdw_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_seq(st, k, grid, lds, a);
 }
 }  // namespace
 

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Train-step time of `--quant` dvrjanet (H 12, K 3, W8A8) on its kernels (csrc/dvrjanet_q.hip, through fused_train_step: forward, loss,
-backward, reduction, clip + AdamW) next to the ATen route on the same GPU (opendpd_amd.quant._quantise_aten called directly: one torch op per
-gate per time step, torch.optim.AdamW) and next to the float dvrjanet step.  Median and span of device-event timings after warm-up, the three
-alternating per round in one process.  usage (GPU box): PYTHONPATH=. python tools/dvrjanet_q_time.py [--out FILE]"""
+"""Train-step time of `--quant` bojanet (H 12, W8A8) or dvrjanet (H 12, K 3, W8A8) on its kernels (csrc/bojanet_q.hip, csrc/dvrjanet_q.hip, through
+fused_train_step: forward, loss, backward, reduction, clip + AdamW) next to the ATen route on the same GPU (opendpd_amd.quant._quantise_aten
+called directly: one torch op per gate per time step, torch.optim.AdamW) and next to the float step of the same backbone.  Median and span of
+device-event timings after warm-up, the three alternating per round in one process.
+usage (GPU box): PYTHONPATH=. python tools/qcell_time.py --backbone {bojanet,dvrjanet} [--out FILE] [--rounds N]"""
 import argparse
 import json
 import warnings
@@ -13,7 +14,8 @@ from opendpd_amd import CoreModel
 from opendpd_amd.quant import _quantise_aten, get_quant_model
 from opendpd_amd.train_funcs import FusedAdamW, fused_train_step
 
-H, K, BITS, CLIP, LR = 12, 3, 8, 200.0, 5e-4
+H, BITS, CLIP, LR = 12, 8, 200.0, 5e-4
+MODEL_ARGS = {"bojanet": {}, "dvrjanet": {"num_dvr_units": 3}}
 
 
 class _Proj:
@@ -38,31 +40,33 @@ def median(v):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--backbone", choices=sorted(MODEL_ARGS), required=True)
     ap.add_argument("--out", default="")
     ap.add_argument("--rounds", type=int, default=9)
     a = ap.parse_args()
     if not torch.cuda.is_available():
-        raise SystemExit("dvrjanet_q_time.py measures on a HIP device; none found")
+        raise SystemExit("qcell_time.py measures on a HIP device; none found")
+    bb, kw = a.backbone, MODEL_ARGS[a.backbone]
     rows = []
-    print("| B x T | kernels (dvrjanet_q.hip): step ms, median (min .. max) | ATen route: step ms | float dvrjanet: step ms | ATen / kernels | "
+    print(f"| B x T | kernels ({bb}_q.hip): step ms, median (min .. max) | ATen route: step ms | float {bb}: step ms | ATen / kernels | "
           "kernels / float |\n|---|---|---|---|---|---|")
     for B, T in ((256, 200), (4096, 200)):
         g = torch.Generator(device="cuda").manual_seed(B)
         x = 0.3 * torch.randn(B, T, 2, device="cuda", generator=g) + 0.1
         t = 0.3 * torch.randn(B, T, 2, device="cuda", generator=g)
         torch.manual_seed(0)
-        fnet = CoreModel(2, H, 1, "dvrjanet", num_dvr_units=K).cuda()
+        fnet = CoreModel(2, H, 1, bb, **kw).cuda()
         sd = {k: v.clone() for k, v in fnet.state_dict().items()}
         q = get_quant_model(_Proj, fnet)
         assert q.backbone.native
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            src = CoreModel(2, H, 1, "dvrjanet", num_dvr_units=K).cuda()
+            src = CoreModel(2, H, 1, bb, **kw).cuda()
             src.load_state_dict(sd)
             at = _quantise_aten(src, BITS, BITS, "", torch.device("cuda"))
         assert not at.backbone.native
         at.load_state_dict(q.state_dict())
-        fl = CoreModel(2, H, 1, "dvrjanet", num_dvr_units=K).cuda()
+        fl = CoreModel(2, H, 1, bb, **kw).cuda()
         fl.load_state_dict(sd)
         qopt, fopt = FusedAdamW(q, lr=LR), FusedAdamW(fl, lr=LR)
         topt = torch.optim.AdamW(at.parameters(), lr=LR)
@@ -86,7 +90,7 @@ def main():
                 ms[name].append(one(lambda: [fn() for _ in range(n)]) / n)
         med = {k: median(v) for k, v in ms.items()}
         spread = {k: (min(v), max(v)) for k, v in ms.items()}
-        rows.append(dict(B=B, T=T, H=H, K=K, bits=BITS, median_ms=med, min_max_ms=spread))
+        rows.append(dict(backbone=bb, B=B, T=T, H=H, **kw, bits=BITS, median_ms=med, min_max_ms=spread, samples_ms=ms))
         span = {k: f"{med[k]:.3f} ({spread[k][0]:.3f} .. {spread[k][1]:.3f})" for k in med}
         print(f"| {B} x {T} | {span['kernels']} | {span['aten']} | {span['float']} | {med['aten'] / med['kernels']:.0f} x | "
               f"{med['kernels'] / med['float']:.2f} x |", flush=True)
