@@ -1,5 +1,5 @@
-// apnrru_s16.hip — APNRRU (backbones/apnrru.py:5-152) in the S16 mapping (see gru_s16.hip / odpd_s16.h; the FIR / halo / dL/dx machinery
-// is bojanet_s16.hip's): a wave = 16 sequences, lane (n = sequence, q = quad) owns slots 4q + e of TWO 16-slot tiles that hold the cell's
+// apnrru_s16.hip — APNRRU (backbones/apnrru.py:5-152) in the S16 mapping (see gru_s16.hip / odpd_s16.h; the frame chunk with its halo and the
+// dL/dx hand-over are shared with bojanet_s16.hip: odpd_f4s16.h): a wave = 16 sequences, lane (n = sequence, q = quad) owns slots 4q + e of TWO 16-slot tiles that hold the cell's
 // state vector s = [h_I (H), h_Q (H), h_A (3)], n = 2H + 3 <= 31:
 //     tile 0: slots 0..H-1 = h_I,  slot 15 = h_A[0],  slot 14 = h_A[2]          tile 1: slots 0..H-1 = h_Q,  slot 15 = h_A[1]
 // so that the complex rotations of the state (h <- h r before the cell, h <- conj(r) s' after it) pair tile 0 with tile 1 on the SAME lane
@@ -10,14 +10,14 @@
 //   y = (A - Bq, Bq + A), A = w_I . h_I, Bq = w_Q . h_Q.
 // BPTT from checkpoints of the state every kCkptStride steps; dL/dx through the FIR bank (transposed, accumulated in an LDS frame chunk
 // with halo), the raw sample and r.  Frames shorter than 15 samples are refused like the reference's framing (:68-72).
-#include "odpd_s16.h"
+#include "odpd_f4s16.h"
 
 namespace odpd {
 namespace {
 
 constexpr int kApnF = 3, kApnM = 16, kApnNode = 16;
-constexpr int kApnHalo = 16;
-constexpr int kApnRow = kApnHalo + kChunk + 1;      // float2 row stride of a staged frame chunk: index i <-> time t0 - 16 + i
+constexpr int kApnHalo = kApnM;                     // staged samples before the chunk (odpd_f4s16.h; row stride kHaloRow)
+static_assert(kApnHalo == kHalo, "the FIR bank's reach is the shared halo");
 struct ApnLayout { int H, n, o_bi, o_bq, o_c, o_z, o_wu, o_bu, o_wh, o_bh, o_woi, o_woq, P; };
 __host__ __device__ inline ApnLayout apn_layout(int H) {
     ApnLayout L; L.H = H; L.n = 2 * H + 3; int o = 0;
@@ -84,60 +84,10 @@ __device__ __forceinline__ float4 a16_entry(const float* pl, const ApnLayout& L,
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ void a16_build_table(float* tab, const float* pl, const ApnLayout& L, int lane, int wave, int nwb) {
-    float4* t4 = reinterpret_cast<float4*>(tab);
-    for (int grp = wave; grp < A16::NG; grp += nwb) t4[grp * 64 + lane] = a16_entry(pl, L, grp, lane & 15, lane >> 4);
-    __syncthreads();
-}
-__device__ __forceinline__ float a16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ f32x4 a16_mv(TabPtr tl, int grp, const f32x4& v, f32x4 acc) {
-    f32x4 a1[1] = {acc};
-    const f32x4 v1[1] = {v};
-    s16n_matvec<1>(tl, grp, v1, a1);
-    return a1[0];
-}
-
-// frame chunk with its halo: 16 sequences x 48 samples, times t0 - 16 .. t0 + 31 (zeros before the frame: apnrru.py:68-69)
-__device__ __forceinline__ void a16_stage_in(float2* lds, const float* g, int b0, int B, int T, int t0, int len, int lane) {
-    const float2* g2 = reinterpret_cast<const float2*>(g);
-    constexpr int W = kApnHalo + kChunk;
-#pragma unroll
-    for (int j = 0; j < 16 * W / 64; ++j) {
-        const int e = lane + 64 * j, m = e / W, i = e % W, t = t0 - kApnHalo + i;
-        float2 v = make_float2(0.0f, 0.0f);
-        if (b0 + m >= B || t >= t0 + len) v = make_float2(0.5f, 0.25f);     // idle sequence slots / steps: a finite signal with |x| > 0
-        else if (t >= 0) v = g2[(size_t)(b0 + m) * T + t];
-        lds[m * kApnRow + i] = v;
-    }
-}
-__device__ __forceinline__ void a16_stage_out(const float2* lds, float* g, int b0, int B, int T, int t0, int len, int lane) {
-    float2* g2 = reinterpret_cast<float2*>(g);
-#pragma unroll
-    for (int j = 0; j < 16 * kChunk / 64; ++j) {
-        const int e = lane + 64 * j, m = e / kChunk, tt = e % kChunk;
-        if (tt < len && b0 + m < B) g2[(size_t)(b0 + m) * T + t0 + tt] = lds[m * kApnRow + kApnHalo + tt];
-    }
-}
-// dL/dx chunk hand-over (backward runs the chunks last to first): what the finished chunk put before its own t0 (indices 1..15)
-// belongs to the end of the next (earlier) one (indices 33..47); everything else restarts at 0
-__device__ __forceinline__ void a16_dx_carry(float2* lds, int lane, bool first) {
-    float2 c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int e = lane + 64 * j, m = e >> 4, i = e & 15;
-        c[j] = first ? make_float2(0.0f, 0.0f) : lds[m * kApnRow + i];
-    }
-    wave_lds_fence();
-    for (int e = lane; e < 16 * kApnRow; e += 64) lds[e] = make_float2(0.0f, 0.0f);
-    wave_lds_fence();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int e = lane + 64 * j, m = e >> 4, i = e & 15;
-        if (i) lds[m * kApnRow + kChunk + i] = c[j];
-    }
-    wave_lds_fence();
+// per-wave LDS floats of the two kernels: frame chunk with halo (x, and dL/dx), y or dL/dy, transpose tiles
+__host__ __device__ constexpr int a16_fwd_wave_floats() { return 2 * 16 * kHaloRow + 2 * 16 * kChunkPad; }
+__host__ __device__ constexpr int a16_bwd_wave_floats(bool NW, bool DX) {
+    return (DX ? 2 : 1) * 2 * 16 * kHaloRow + 2 * 16 * kChunkPad + (NW ? A16::kTiles * kTileFloats : 0);
 }
 
 struct A16Phase { float I, Q, im, rr, ri; };      // r = conj(x) / |x| = (rr, ri)
@@ -175,13 +125,13 @@ __device__ __forceinline__ void a16_rotate(const f32x4& a, const f32x4& b, float
 // the RRU cell on the normalised state sp: v1, v, sigmoid(C sp) and s' = sigmoid(C sp) + Z v
 __device__ __forceinline__ void a16_cell(TabPtr tl, float Cn, const f32x4& feat, const f32x4 (&sp)[2], f32x4& v1, f32x4 (&v)[2], f32x4 (&sg)[2], f32x4 (&sn)[2]) {
     f32x4 p1 = as_f32x4(tab_ld(tl, A16::BU * 64));
-    p1 = a16_mv(tl, A16::WUX, feat, p1);
-    p1 = a16_mv(tl, A16::WUS + 0, sp[0], p1);
-    p1 = a16_mv(tl, A16::WUS + 1, sp[1], p1);
+    p1 = s16_mv(tl, A16::WUX, feat, p1);
+    p1 = s16_mv(tl, A16::WUS + 0, sp[0], p1);
+    p1 = s16_mv(tl, A16::WUS + 1, sp[1], p1);
     v1 = tanh4_precise(p1);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
-        const f32x4 p2 = a16_mv(tl, A16::WH + mt, v1, as_f32x4(tab_ld(tl, (A16::BH + mt) * 64)));
+        const f32x4 p2 = s16_mv(tl, A16::WH + mt, v1, as_f32x4(tab_ld(tl, (A16::BH + mt) * 64)));
         v[mt] = tanh4_precise(p2);
         sg[mt] = sigmoid4_prescaled(mul4(splat4(Cn), sp[mt]));
         sn[mt] = fma4(as_f32x4(tab_ld(tl, (A16::Z + mt) * 64)), v[mt], sg[mt]);
@@ -192,7 +142,7 @@ __device__ __forceinline__ void a16_cell(TabPtr tl, float Cn, const f32x4& feat,
 // forward
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 1) void apn16_fwd_kernel(SeqArgs a) {
-    constexpr int S = kCkptStride, kWave = 2 * 16 * kApnRow + 2 * 16 * kChunkPad;
+    constexpr int S = kCkptStride, kWave = a16_fwd_wave_floats();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -200,15 +150,15 @@ __global__ __launch_bounds__(512, 1) void apn16_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    a16_build_table(tab, pl, L, lane, wave, nwb);
+    s16_build_table<A16::NG, a16_entry>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
-    const float Cn = a16_uni(pl[L.o_c]) * kNegLog2e;
+    const float Cn = uni_(pl[L.o_c]) * kNegLog2e;
     float rot[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) rot[e] = 4 * q + e < a.H ? 1.0f : 0.0f;
     float* wbase = tab + s16_tab_floats(A16::NG) + (size_t)wave * kWave;
     float2* xs = reinterpret_cast<float2*>(wbase);
-    float2* ys = xs + 16 * kApnRow;
+    float2* ys = xs + 16 * kHaloRow;
     const int nwaves = gridDim.x * nwb;
     for (int grp = blockIdx.x * nwb + wave; grp < a.ngroups; grp += nwaves) {
         const int b0 = grp * 16;
@@ -217,11 +167,11 @@ __global__ __launch_bounds__(512, 1) void apn16_fwd_kernel(SeqArgs a) {
         for (int t0 = 0; t0 < a.T; t0 += kChunk) {
             const int len = min(kChunk, a.T - t0);
             wave_lds_fence();
-            a16_stage_in(xs, a.x, b0, a.B, a.T, t0, len, lane);
+            halo_stage_in<kApnHalo, true>(xs, a.x, b0, a.B, a.T, t0, len, lane);      // (idle slots AND steps past the frame: a finite signal with |x| > 0)
             wave_lds_fence();
             for (int tt = 0; tt < len; ++tt) {
                 const TabPtr tk = opaque(tl);
-                const float2* xrow = xs + n * kApnRow;
+                const float2* xrow = xs + n * kHaloRow;
                 const A16Phase P = a16_phase(xrow[tt + kApnHalo]);
                 const f32x4 feat = a16_features(a16_fir_fwd(tk, xrow, tt, q), P);
                 f32x4 sp[2], v1, v[2], sg[2], sn[2];
@@ -265,7 +215,7 @@ __device__ __forceinline__ void a16_bwd_block(TabPtr tl0, float C, const float (
     constexpr int S = kCkptStride;
     const float Cn = C * kNegLog2e;
     f32x4 sa_s[S], sb_s[S], v1_s[S], va_s[S], vb_s[S], ff_s[S];        // state before the step (both tiles), v1, v (both tiles), FIR outputs
-    const float2* xrow = xs + n * kApnRow;
+    const float2* xrow = xs + n * kHaloRow;
 #pragma unroll
     for (int si = 0; si < S; ++si) {
         if (FULL || si < nstep) {
@@ -332,14 +282,14 @@ __device__ __forceinline__ void a16_bwd_block(TabPtr tl0, float C, const float (
                 }
                 if constexpr (NW) G.dbh[mt] = add4(G.dbh[mt], dpre2[mt]);
             }
-            f32x4 dv1 = a16_mv(tl, A16::WHT + 0, dpre2[0], z4);
-            dv1 = a16_mv(tl, A16::WHT + 1, dpre2[1], dv1);
+            f32x4 dv1 = s16_mv(tl, A16::WHT + 0, dpre2[0], z4);
+            dv1 = s16_mv(tl, A16::WHT + 1, dpre2[1], dv1);
             f32x4 dpre1;
             ODPD_EACH4 dpre1[i] = dv1[i] * __builtin_fmaf(-v1[i], v1[i], 1.0f);
             if constexpr (NW) G.dbu = add4(G.dbu, dpre1);
-            dsp[0] = a16_mv(tl, A16::WUST + 0, dpre1, dsp[0]);
-            dsp[1] = a16_mv(tl, A16::WUST + 1, dpre1, dsp[1]);
-            const f32x4 dfe = a16_mv(tl, A16::WUXT, dpre1, z4);          // d feat on the lanes q = 0, 1 (rows 8..15 of the table are empty)
+            dsp[0] = s16_mv(tl, A16::WUST + 0, dpre1, dsp[0]);
+            dsp[1] = s16_mv(tl, A16::WUST + 1, dpre1, dsp[1]);
+            const f32x4 dfe = s16_mv(tl, A16::WUXT, dpre1, z4);          // d feat on the lanes q = 0, 1 (rows 8..15 of the table are empty)
             // the rotation into the normalised frame: sp = s r
             ODPD_EACH4 {
                 const bool r = rot[i] != 0.0f;
@@ -365,8 +315,8 @@ __device__ __forceinline__ void a16_bwd_block(TabPtr tl0, float C, const float (
                 const float w = __builtin_fmaf(drt, P.Q, dit * P.I) * (P.im * P.im * P.im);
 #pragma unroll
                 for (int tile_i = 0; tile_i < 2; ++tile_i) {
-                    const f32x4 dw = a16_mv(tl, A16::FIRT + tile_i, dF, z4);
-                    float2* d = dxs + n * kApnRow + tt + 1 + 8 * tile_i + 2 * q;
+                    const f32x4 dw = s16_mv(tl, A16::FIRT + tile_i, dF, z4);
+                    float2* d = dxs + n * kHaloRow + tt + 1 + 8 * tile_i + 2 * q;
                     float2 u0 = d[0], u1 = d[1];
                     u0.x += dw[0]; u0.y += dw[1]; u1.x += dw[2]; u1.y += dw[3];
                     if (tile_i == 1 && q == 3) { u1.x = __builtin_fmaf(P.Q, w, u1.x); u1.y = __builtin_fmaf(-P.I, w, u1.y); }     // lag 0 = this sample
@@ -387,7 +337,7 @@ __device__ __forceinline__ void a16_bwd_block(TabPtr tl0, float C, const float (
                     G.wh[0] = mfma4(dT[0][c], sT[0][c], G.wh[0]); G.wh[1] = mfma4(dT[1][c], sT[0][c], G.wh[1]);       // W_h : dpre2 (x) v1
                     G.wus[0] = mfma4(dT[2][c], sT[1][c], G.wus[0]); G.wus[1] = mfma4(dT[2][c], sT[2][c], G.wus[1]);   // W_u|s: dpre1 (x) sp
                     G.wux = mfma4(dT[2][c], sT[3][c], G.wux);                                                          // W_u|x: dpre1 (x) feat
-                    const float* xr = xf + 2 * ((4 * q + c) * kApnRow + tt + 1 + (n >> 1)) + (n & 1);               // FIR: dF (x) window
+                    const float* xr = xf + 2 * ((4 * q + c) * kHaloRow + tt + 1 + (n >> 1)) + (n & 1);               // FIR: dF (x) window
                     G.fir[0] = mfma4(dT[3][c], xr[0], G.fir[0]);
                     G.fir[1] = mfma4(dT[3][c], xr[16], G.fir[1]);
                 }
@@ -433,7 +383,7 @@ __device__ __forceinline__ void a16_write_row(float* prow, float* raw, const Apn
 template <bool NW, bool DX>
 __global__ __launch_bounds__(256, 1) void apn16_bwd_kernel(SeqArgs a) {
     constexpr int S = kCkptStride;
-    constexpr int kWave = (DX ? 2 : 1) * 2 * 16 * kApnRow + 2 * 16 * kChunkPad + (NW ? A16::kTiles * kTileFloats : 0);
+    constexpr int kWave = a16_bwd_wave_floats(NW, DX);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -441,17 +391,17 @@ __global__ __launch_bounds__(256, 1) void apn16_bwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    a16_build_table(tab, pl, L, lane, wave, nwb);
+    s16_build_table<A16::NG, a16_entry>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
-    const float C = a16_uni(pl[L.o_c]);
+    const float C = uni_(pl[L.o_c]);
     float rot[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) rot[e] = 4 * q + e < a.H ? 1.0f : 0.0f;
     float* wbase = tab + s16_tab_floats(A16::NG) + (size_t)wave * kWave;
     float2* xs = reinterpret_cast<float2*>(wbase);
-    float2* dys = xs + 16 * kApnRow;
+    float2* dys = xs + 16 * kHaloRow;
     float2* dxs = dys + 16 * kChunkPad;
-    float* tiles = reinterpret_cast<float*>(dxs + (DX ? 16 * kApnRow : 0));
+    float* tiles = reinterpret_cast<float*>(dxs + (DX ? 16 * kHaloRow : 0));
     A16Grad G;
     G.zero();
     const int nwaves = gridDim.x * nwb;
@@ -468,14 +418,14 @@ __global__ __launch_bounds__(256, 1) void apn16_bwd_kernel(SeqArgs a) {
                     if (cur_chunk >= 0) {
                         const int pt0 = cur_chunk * kChunk;
                         wave_lds_fence();
-                        a16_stage_out(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
+                        halo_stage_out<kApnHalo>(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
                     }
                     wave_lds_fence();
-                    a16_dx_carry(dxs, lane, cur_chunk < 0);
+                    halo_dx_carry<kApnHalo>(dxs, lane, cur_chunk < 0);
                 }
                 wave_lds_fence();
                 const int len = min(kChunk, a.T - t0);
-                a16_stage_in(xs, a.x, b0, a.B, a.T, t0, len, lane);
+                halo_stage_in<kApnHalo, true>(xs, a.x, b0, a.B, a.T, t0, len, lane);
                 stage_in<16>(dys, a.dy, b0, a.B, a.T, t0, len, lane, make_float2(0.0f, 0.0f));
                 wave_lds_fence();
                 cur_chunk = chunk;
@@ -489,7 +439,7 @@ __global__ __launch_bounds__(256, 1) void apn16_bwd_kernel(SeqArgs a) {
             if (cur_chunk >= 0) {
                 const int pt0 = cur_chunk * kChunk;
                 wave_lds_fence();
-                a16_stage_out(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
+                halo_stage_out<kApnHalo>(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
                 wave_lds_fence();
             }
         }
@@ -499,34 +449,18 @@ __global__ __launch_bounds__(256, 1) void apn16_bwd_kernel(SeqArgs a) {
         __syncthreads();
         a16_write_row(smem + wave * P4, smem + nwb * P4 + wave * 512, L, G, lane, n, q);
         __syncthreads();
-        float* prow = a.partials + (size_t)blockIdx.x * P4;
-        for (int i = threadIdx.x; i < P4; i += blockDim.x) {
-            float v = smem[i];
-            for (int wv = 1; wv < nwb; ++wv) v += smem[wv * P4 + i];
-            prow[i] = v;
-        }
+        s16_reduce_rows(smem, a.partials + (size_t)blockIdx.x * P4, P4, nwb);
     }
 }
 
-LaunchShape a16_shape(int ngroups, int waves) {
-    LaunchShape ls;
-    ls.waves = waves;
-    const int need = (ngroups + waves - 1) / waves, cus = device_cus();
-    ls.grid = need < cus ? need : cus;
-    return ls;
-}
 template <bool NW, bool DX>
 int a16_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
-    const LaunchShape ls = a16_shape(a.ngroups, 4);
-    size_t lds = ((size_t)pad4(P) + s16_tab_floats(A16::NG) +
-                  (size_t)ls.waves * ((DX ? 2 : 1) * 2 * 16 * kApnRow + 2 * 16 * kChunkPad + (NW ? A16::kTiles * kTileFloats : 0))) * sizeof(float);
+    const LaunchShape ls = s16_group_shape(a.ngroups, 4);
+    size_t lds = ((size_t)pad4(P) + s16_tab_floats(A16::NG) + (size_t)ls.waves * a16_bwd_wave_floats(NW, DX)) * sizeof(float);
     const size_t red = (size_t)ls.waves * (P + kLossCols + 512) * sizeof(float);
     if (NW && lds < red) lds = red;
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = apn16_bwd_kernel<NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, apn16_bwd_kernel<NW, DX>, ls.grid, 64 * ls.waves, lds, a);
 }
 
 
@@ -934,11 +868,7 @@ __global__ __launch_bounds__(64) void apn_gp_eval_kernel(SeqArgs a) {
 }
 
 static size_t apn_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + agp_buf(T).total) * sizeof(float); }
-static int apn_gp_blocks_per_cu(int P, int T) {
-    const size_t lds = apn_gp_lds_bytes(P, T);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int apn_gp_blocks_per_cu(int H, int T) { return gp_blocks_per_cu(apn_gp_lds_bytes(apn_layout(H).P, T), 4); }
 
 }  // namespace
 
@@ -948,7 +878,7 @@ int64_t apnrru_param_count(const odpd_model_t* m) {
 }
 int apnrru_rows(const odpd_model_t* m, int B) {
     if (!apnrru_ok(m)) return ODPD_EUNSUPPORTED;
-    return a16_shape((B + 15) / 16, 4).grid;
+    return s16_group_shape((B + 15) / 16, 4).grid;
 }
 int64_t apnrru_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!apnrru_ok(m)) return ODPD_EUNSUPPORTED;
@@ -957,21 +887,12 @@ int64_t apnrru_ckpt_floats(const odpd_model_t* m, int B, int T) {
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, the frame's state in LDS
 bool apnrru_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if (!apnrru_ok(m) || T < kApnM - 1) return false;
-    const int per_cu = apn_gp_blocks_per_cu(apn_layout(m->hidden).P, T);
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && per_cu > 0;
     // up to five rounds of workgroups (measured: profiles/r03/gp_train_bench_f4.txt): the alternative is the forward / loss / backward chain of the S16 kernels
-    return (long)B <= 5L * device_cus() * per_cu;
+    return gp_batch_fits(B, apn_gp_blocks_per_cu(m->hidden, T), 5);
 }
-int apnrru_gp_rows(const odpd_model_t* m, int B, int T) {
-    const long cap = (long)device_cus() * apn_gp_blocks_per_cu(apn_layout(m->hidden).P, T);
-    return B < cap ? B : (int)cap;
-}
+int apnrru_gp_rows(const odpd_model_t* m, int B, int T) { return gp_rows(B, apn_gp_blocks_per_cu(m->hidden, T)); }
 int apnrru_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    const size_t lds = apn_gp_lds_bytes(apn_layout(m->hidden).P, a.T);
-    if (int e = allow_big_lds(apn_gp_train_kernel, lds)) return e;
-    hipLaunchKernelGGL(apn_gp_train_kernel, dim3(apnrru_gp_rows(m, a.B, a.T)), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_seq(st, apn_gp_train_kernel, apnrru_gp_rows(m, a.B, a.T), apn_gp_lds_bytes(apn_layout(m->hidden).P, a.T), a);
 }
 // mode 1 forward, 2 backward
 int apnrru_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int mode) {
@@ -980,27 +901,14 @@ int apnrru_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int 
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
     const int P = apn_layout(m->hidden).P;
-    if (mode == 1 && !a.ckpt && a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0) {
-        // sequences that each get a SIMD of their own (inference: no checkpoints)
-        const size_t lds = ((size_t)pad4(P) + kAevFloats) * sizeof(float);
-        if (int e = allow_big_lds(apn_gp_eval_kernel, lds)) return e;
-        hipLaunchKernelGGL(apn_gp_eval_kernel, dim3(a.B), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    }
+    if (gp_eval_fits(a, mode)) return launch_seq(st, apn_gp_eval_kernel, a.B, ((size_t)pad4(P) + kAevFloats) * sizeof(float), a);
     if (mode == 1) {
-        const LaunchShape ls = a16_shape(a.ngroups, a.ngroups <= 4 * device_cus() ? 4 : 8);
-        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(A16::NG) + (size_t)ls.waves * (2 * 16 * kApnRow + 2 * 16 * kChunkPad)) * sizeof(float);
-        auto k = apn16_fwd_kernel;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
+        const LaunchShape ls = s16_fwd_shape(a.ngroups);
+        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(A16::NG) + (size_t)ls.waves * a16_fwd_wave_floats()) * sizeof(float);
+        return launch_lds(st, apn16_fwd_kernel, ls.grid, 64 * ls.waves, lds, a);
     }
     if (!a.ckpt && a.nck > 1) return ODPD_EINVAL;
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    if (nw && dx) return a16_launch_bwd<true, true>(st, a, P);
-    if (nw) return a16_launch_bwd<true, false>(st, a, P);
-    return a16_launch_bwd<false, true>(st, a, P);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return a16_launch_bwd<decltype(nw)::value, decltype(dx)::value>(st, a, P); });
 }
 
 }  // namespace odpd

@@ -13,14 +13,14 @@
 // with the LDS window, dL/dx the transposed bank accumulated into an LDS frame chunk with the same halo (carried across chunks).
 // The reference's phase re-rotation cannot be built beyond hidden 18 (its concatenation, :41-53); the kernels take hidden <= 16.
 // Deviation: where a filter output is exactly 0 the reference's gradient is NaN (0 * inf through sqrt); here that term is dropped.
-#include "odpd_s16.h"
+#include "odpd_f4s16.h"
 
 namespace odpd {
 namespace {
 
 constexpr int kBojP = 6, kBojM = 16;
-constexpr int kBojHalo = 16;                        // staged samples before the chunk (15 used: taps reach back to t - 15)
-constexpr int kBojRow = kBojHalo + kChunk + 1;      // float2 row stride of a staged frame chunk: index i <-> time t0 - 16 + i
+constexpr int kBojHalo = kBojM;                     // staged samples before the chunk (odpd_f4s16.h; row stride kHaloRow)
+static_assert(kBojHalo == kHalo, "the FIR bank's reach is the shared halo");
 struct BojLayout { int H, o_bi, o_bq, o_wfi, o_bfi, o_wfh, o_wgi, o_bgi, o_wgh, o_woi, o_boi, o_woq, o_boq, P; };
 __host__ __device__ inline BojLayout boj_layout(int H) {
     BojLayout L; L.H = H; int o = 0;
@@ -89,60 +89,10 @@ __device__ __forceinline__ float4 b16_entry(const float* pl, const BojLayout& L,
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ void b16_build_table(float* tab, const float* pl, const BojLayout& L, int lane, int wave, int nwb) {
-    float4* t4 = reinterpret_cast<float4*>(tab);
-    for (int grp = wave; grp < B16::NG; grp += nwb) t4[grp * 64 + lane] = b16_entry(pl, L, grp, lane & 15, lane >> 4);
-    __syncthreads();
-}
-__device__ __forceinline__ float b16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ f32x4 b16_mv(TabPtr tl, int grp, const f32x4& v, f32x4 acc) {
-    f32x4 a1[1] = {acc};
-    const f32x4 v1[1] = {v};
-    s16n_matvec<1>(tl, grp, v1, a1);
-    return a1[0];
-}
-
-// frame chunk with its halo: 16 sequences x 48 samples, times t0 - 16 .. t0 + 31 (zeros before the frame: bojanet.py:72-73)
-__device__ __forceinline__ void b16_stage_in(float2* lds, const float* g, int b0, int B, int T, int t0, int len, int lane) {
-    const float2* g2 = reinterpret_cast<const float2*>(g);
-    constexpr int W = kBojHalo + kChunk;
-#pragma unroll
-    for (int j = 0; j < 16 * W / 64; ++j) {
-        const int e = lane + 64 * j, m = e / W, i = e % W, t = t0 - kBojHalo + i;
-        float2 v = make_float2(0.0f, 0.0f);
-        if (b0 + m >= B) v = make_float2(0.5f, 0.25f);                  // idle sequence slots: any finite, non-degenerate signal
-        else if (t >= 0 && t < t0 + len) v = g2[(size_t)(b0 + m) * T + t];
-        lds[m * kBojRow + i] = v;
-    }
-}
-__device__ __forceinline__ void b16_stage_out(const float2* lds, float* g, int b0, int B, int T, int t0, int len, int lane) {
-    float2* g2 = reinterpret_cast<float2*>(g);
-#pragma unroll
-    for (int j = 0; j < 16 * kChunk / 64; ++j) {
-        const int e = lane + 64 * j, m = e / kChunk, tt = e % kChunk;
-        if (tt < len && b0 + m < B) g2[(size_t)(b0 + m) * T + t0 + tt] = lds[m * kBojRow + kBojHalo + tt];
-    }
-}
-// dL/dx chunk hand-over (backward runs the chunks last to first): what the finished chunk put before its own t0 (indices 1..15)
-// belongs to the end of the next (earlier) one (indices 33..47); everything else restarts at 0
-__device__ __forceinline__ void b16_dx_carry(float2* lds, int lane, bool first) {
-    float2 c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int e = lane + 64 * j, m = e >> 4, i = e & 15;
-        c[j] = first ? make_float2(0.0f, 0.0f) : lds[m * kBojRow + i];
-    }
-    wave_lds_fence();
-    for (int e = lane; e < 16 * kBojRow; e += 64) lds[e] = make_float2(0.0f, 0.0f);
-    wave_lds_fence();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int e = lane + 64 * j, m = e >> 4, i = e & 15;
-        if (i) lds[m * kBojRow + kChunk + i] = c[j];
-    }
-    wave_lds_fence();
+// per-wave LDS floats of the two kernels: frame chunk with halo (x, and dL/dx), y or dL/dy, transpose tiles
+__host__ __device__ constexpr int b16_fwd_wave_floats() { return 2 * 16 * kHaloRow + 2 * 16 * kChunkPad; }
+__host__ __device__ constexpr int b16_bwd_wave_floats(bool NW, bool DX) {
+    return (DX ? 2 : 1) * 2 * 16 * kHaloRow + 2 * 16 * kChunkPad + (NW ? B16::kTiles * kTileFloats : 0);
 }
 
 struct B16Front { f32x4 ev, cs; float m0a, m0b, ia, ib; };     // [mag_a, mag_a^2, mag_b, mag_b^2], [cos_a, sin_a, cos_b, sin_b]
@@ -170,8 +120,8 @@ __device__ __forceinline__ B16Front b16_demod(const f32x4& ff) {
 }
 __device__ __forceinline__ void b16_cell(TabPtr tl, const f32x4& ev, f32x4& h, f32x4& f, f32x4& g) {
     f32x4 pf = as_f32x4(tab_ld(tl, (B16::SC + 0) * 64)), pg = as_f32x4(tab_ld(tl, (B16::SC + 1) * 64));
-    pf = b16_mv(tl, B16::WFI, ev, pf); pg = b16_mv(tl, B16::WGI, ev, pg);
-    pf = b16_mv(tl, B16::FH, h, pf); pg = b16_mv(tl, B16::GH, h, pg);
+    pf = s16_mv(tl, B16::WFI, ev, pf); pg = s16_mv(tl, B16::WGI, ev, pg);
+    pf = s16_mv(tl, B16::FH, h, pf); pg = s16_mv(tl, B16::GH, h, pg);
     f = sigmoid4_prescaled(pf); g = tanh4_precise(pg);
     h = fma4(f, sub4(h, g), g);
 }
@@ -187,7 +137,7 @@ __device__ __forceinline__ void b16_rotate(TabPtr tl, const f32x4& cs, f32x4& co
 // forward
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 1) void boj16_fwd_kernel(SeqArgs a) {
-    constexpr int S = kCkptStride, kWave = 2 * 16 * kBojRow + 2 * 16 * kChunkPad;
+    constexpr int S = kCkptStride, kWave = b16_fwd_wave_floats();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -195,12 +145,12 @@ __global__ __launch_bounds__(512, 1) void boj16_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    b16_build_table(tab, pl, L, lane, wave, nwb);
+    s16_build_table<B16::NG, b16_entry>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
-    const float boi = b16_uni(pl[L.o_boi]), boq = b16_uni(pl[L.o_boq]);
+    const float boi = uni_(pl[L.o_boi]), boq = uni_(pl[L.o_boq]);
     float* wbase = tab + s16_tab_floats(B16::NG) + (size_t)wave * kWave;
     float2* xs = reinterpret_cast<float2*>(wbase);
-    float2* ys = xs + 16 * kBojRow;
+    float2* ys = xs + 16 * kHaloRow;
     const int nwaves = gridDim.x * nwb;
     for (int grp = blockIdx.x * nwb + wave; grp < a.ngroups; grp += nwaves) {
         const int b0 = grp * 16;
@@ -209,11 +159,11 @@ __global__ __launch_bounds__(512, 1) void boj16_fwd_kernel(SeqArgs a) {
         for (int t0 = 0; t0 < a.T; t0 += kChunk) {
             const int len = min(kChunk, a.T - t0);
             wave_lds_fence();
-            b16_stage_in(xs, a.x, b0, a.B, a.T, t0, len, lane);
+            halo_stage_in<kBojHalo, false>(xs, a.x, b0, a.B, a.T, t0, len, lane);      // (steps past the frame: zeros, like the time before it)
             wave_lds_fence();
             for (int tt = 0; tt < len; ++tt) {
                 const TabPtr tk = opaque(tl);
-                const B16Front F = b16_demod(b16_fir_fwd(tk, xs + n * kBojRow, tt, q));
+                const B16Front F = b16_demod(b16_fir_fwd(tk, xs + n * kHaloRow, tt, q));
                 f32x4 f, g, cosx, sinx;
                 b16_cell(tk, F.ev, h, f, g);
                 b16_rotate(tk, F.cs, cosx, sinx);
@@ -254,7 +204,7 @@ __device__ __forceinline__ void b16_bwd_block(TabPtr tl0, B16Grad& G, const floa
     for (int si = 0; si < S; ++si) {
         if (FULL || si < nstep) {
             const TabPtr tk = opaque(tl0);
-            ff_s[si] = b16_fir_fwd(tk, xs + n * kBojRow, tloc + si, q);
+            ff_s[si] = b16_fir_fwd(tk, xs + n * kHaloRow, tloc + si, q);
             const B16Front F = b16_demod(ff_s[si]);
             hp_s[si] = h;
             b16_cell(tk, F.ev, h, f_s[si], g_s[si]);
@@ -293,14 +243,14 @@ __device__ __forceinline__ void b16_bwd_block(TabPtr tl0, B16Grad& G, const floa
                 G.dbf = add4(G.dbf, dfp); G.dbg = add4(G.dbg, dgp);
             }
             // phases back onto the filters: [dcos_a, dsin_a, dcos_b, dsin_b]
-            f32x4 dcs = b16_mv(tl, B16::SELTC, dcx, z4);
-            dcs = b16_mv(tl, B16::SELTS, dsx, dcs);
-            nh = b16_mv(tl, B16::TRFH, dfp, nh);
-            nh = b16_mv(tl, B16::TRGH, dgp, nh);
+            f32x4 dcs = s16_mv(tl, B16::SELTC, dcx, z4);
+            dcs = s16_mv(tl, B16::SELTS, dsx, dcs);
+            nh = s16_mv(tl, B16::TRFH, dfp, nh);
+            nh = s16_mv(tl, B16::TRGH, dgp, nh);
             dh = nh;
             // envelopes: [dmag_a, dmag^2_a, dmag_b, dmag^2_b]
-            f32x4 de = b16_mv(tl, B16::WFIT, dfp, z4);
-            de = b16_mv(tl, B16::WGIT, dgp, de);
+            f32x4 de = s16_mv(tl, B16::WFIT, dfp, z4);
+            de = s16_mv(tl, B16::WGIT, dgp, de);
             // demodulator (bojanet.py:30-39): mag = m0 + eps, mag^2, sin = fq / mag, cos = fi / mag
             f32x4 dF;
             {
@@ -315,8 +265,8 @@ __device__ __forceinline__ void b16_bwd_block(TabPtr tl0, B16Grad& G, const floa
                 // transposed bank: the 32 window positions of this step, two per tile and lane: taps 8 tile + 2q, + 1
 #pragma unroll
                 for (int tile_i = 0; tile_i < 2; ++tile_i) {
-                    const f32x4 dw = b16_mv(tl, B16::FIRT + tile_i, dF, z4);
-                    float2* d = dxs + n * kBojRow + tt + 1 + 8 * tile_i + 2 * q;
+                    const f32x4 dw = s16_mv(tl, B16::FIRT + tile_i, dF, z4);
+                    float2* d = dxs + n * kHaloRow + tt + 1 + 8 * tile_i + 2 * q;
                     float2 v0 = d[0], v1 = d[1];
                     v0.x += dw[0]; v0.y += dw[1]; v1.x += dw[2]; v1.y += dw[3];
                     d[0] = v0; d[1] = v1;
@@ -338,7 +288,7 @@ __device__ __forceinline__ void b16_bwd_block(TabPtr tl0, B16Grad& G, const floa
                 for (int c = 0; c < 4; ++c) {
                     G.wfi = mfma4(dT[0][c], sT[0][c], G.wfi); G.wgi = mfma4(dT[1][c], sT[0][c], G.wgi);
                     G.wfh = mfma4(dT[0][c], sT[1][c], G.wfh); G.wgh = mfma4(dT[1][c], sT[1][c], G.wgh);
-                    const float* xr = xf + 2 * ((4 * q + c) * kBojRow + tt + 1 + (n >> 1)) + (n & 1);
+                    const float* xr = xf + 2 * ((4 * q + c) * kHaloRow + tt + 1 + (n >> 1)) + (n & 1);
                     G.fir[0] = mfma4(dT[2][c], xr[0], G.fir[0]);
                     G.fir[1] = mfma4(dT[2][c], xr[16], G.fir[1]);
                 }
@@ -377,7 +327,7 @@ __device__ __forceinline__ void b16_write_row(float* prow, float* raw, const Boj
 template <bool NW, bool DX>
 __global__ __launch_bounds__(256, 1) void boj16_bwd_kernel(SeqArgs a) {
     constexpr int S = kCkptStride;
-    constexpr int kWave = (DX ? 2 : 1) * 2 * 16 * kBojRow + 2 * 16 * kChunkPad + (NW ? B16::kTiles * kTileFloats : 0);
+    constexpr int kWave = b16_bwd_wave_floats(NW, DX);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -385,13 +335,13 @@ __global__ __launch_bounds__(256, 1) void boj16_bwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    b16_build_table(tab, pl, L, lane, wave, nwb);
+    s16_build_table<B16::NG, b16_entry>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
     float* wbase = tab + s16_tab_floats(B16::NG) + (size_t)wave * kWave;
     float2* xs = reinterpret_cast<float2*>(wbase);
-    float2* dys = xs + 16 * kBojRow;
+    float2* dys = xs + 16 * kHaloRow;
     float2* dxs = dys + 16 * kChunkPad;
-    float* tiles = reinterpret_cast<float*>(dxs + (DX ? 16 * kBojRow : 0));
+    float* tiles = reinterpret_cast<float*>(dxs + (DX ? 16 * kHaloRow : 0));
     B16Grad G;
     G.zero();
     const int nwaves = gridDim.x * nwb;
@@ -408,14 +358,14 @@ __global__ __launch_bounds__(256, 1) void boj16_bwd_kernel(SeqArgs a) {
                     if (cur_chunk >= 0) {
                         const int pt0 = cur_chunk * kChunk;
                         wave_lds_fence();
-                        b16_stage_out(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
+                        halo_stage_out<kBojHalo>(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
                     }
                     wave_lds_fence();
-                    b16_dx_carry(dxs, lane, cur_chunk < 0);
+                    halo_dx_carry<kBojHalo>(dxs, lane, cur_chunk < 0);
                 }
                 wave_lds_fence();
                 const int len = min(kChunk, a.T - t0);
-                b16_stage_in(xs, a.x, b0, a.B, a.T, t0, len, lane);
+                halo_stage_in<kBojHalo, false>(xs, a.x, b0, a.B, a.T, t0, len, lane);
                 stage_in<16>(dys, a.dy, b0, a.B, a.T, t0, len, lane, make_float2(0.0f, 0.0f));
                 wave_lds_fence();
                 cur_chunk = chunk;
@@ -429,7 +379,7 @@ __global__ __launch_bounds__(256, 1) void boj16_bwd_kernel(SeqArgs a) {
             if (cur_chunk >= 0) {
                 const int pt0 = cur_chunk * kChunk;
                 wave_lds_fence();
-                b16_stage_out(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
+                halo_stage_out<kBojHalo>(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
                 wave_lds_fence();
             }
         }
@@ -439,34 +389,18 @@ __global__ __launch_bounds__(256, 1) void boj16_bwd_kernel(SeqArgs a) {
         __syncthreads();
         b16_write_row(smem + wave * P4, smem + nwb * P4 + wave * 512, L, G, lane, n, q);
         __syncthreads();
-        float* prow = a.partials + (size_t)blockIdx.x * P4;
-        for (int i = threadIdx.x; i < P4; i += blockDim.x) {
-            float v = smem[i];
-            for (int wv = 1; wv < nwb; ++wv) v += smem[wv * P4 + i];
-            prow[i] = v;
-        }
+        s16_reduce_rows(smem, a.partials + (size_t)blockIdx.x * P4, P4, nwb);
     }
 }
 
-LaunchShape b16_shape(int ngroups, int waves) {
-    LaunchShape ls;
-    ls.waves = waves;
-    const int need = (ngroups + waves - 1) / waves, cus = device_cus();
-    ls.grid = need < cus ? need : cus;
-    return ls;
-}
 template <bool NW, bool DX>
 int b16_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
-    const LaunchShape ls = b16_shape(a.ngroups, 4);
-    size_t lds = ((size_t)pad4(P) + s16_tab_floats(B16::NG) +
-                  (size_t)ls.waves * ((DX ? 2 : 1) * 2 * 16 * kBojRow + 2 * 16 * kChunkPad + (NW ? B16::kTiles * kTileFloats : 0))) * sizeof(float);
+    const LaunchShape ls = s16_group_shape(a.ngroups, 4);
+    size_t lds = ((size_t)pad4(P) + s16_tab_floats(B16::NG) + (size_t)ls.waves * b16_bwd_wave_floats(NW, DX)) * sizeof(float);
     const size_t red = (size_t)ls.waves * (P + kLossCols + 512) * sizeof(float);
     if (NW && lds < red) lds = red;
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = boj16_bwd_kernel<NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, boj16_bwd_kernel<NW, DX>, ls.grid, 64 * ls.waves, lds, a);
 }
 
 
@@ -867,11 +801,7 @@ __global__ __launch_bounds__(64) void boj_gp_eval_kernel(SeqArgs a) {
 }
 
 static size_t boj_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + bgp_buf(T).total) * sizeof(float); }
-static int boj_gp_blocks_per_cu(int P, int T) {
-    const size_t lds = boj_gp_lds_bytes(P, T);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int boj_gp_blocks_per_cu(int H, int T) { return gp_blocks_per_cu(boj_gp_lds_bytes(boj_layout(H).P, T), 4); }
 
 }  // namespace
 
@@ -881,7 +811,7 @@ int64_t bojanet_param_count(const odpd_model_t* m) {
 }
 int bojanet_rows(const odpd_model_t* m, int B) {
     if (!bojanet_ok(m)) return ODPD_EUNSUPPORTED;
-    return b16_shape((B + 15) / 16, 4).grid;
+    return s16_group_shape((B + 15) / 16, 4).grid;
 }
 int64_t bojanet_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!bojanet_ok(m)) return ODPD_EUNSUPPORTED;
@@ -890,21 +820,12 @@ int64_t bojanet_ckpt_floats(const odpd_model_t* m, int B, int T) {
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, the frame's state in LDS
 bool bojanet_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if (!bojanet_ok(m) || T < kBojM - 1) return false;
-    const int per_cu = boj_gp_blocks_per_cu(boj_layout(m->hidden).P, T);
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && per_cu > 0;
     // up to five rounds of workgroups (measured: profiles/r03/gp_train_bench_f4.txt): the alternative is the forward / loss / backward chain of the S16 kernels
-    return (long)B <= 5L * device_cus() * per_cu;
+    return gp_batch_fits(B, boj_gp_blocks_per_cu(m->hidden, T), 5);
 }
-int bojanet_gp_rows(const odpd_model_t* m, int B, int T) {
-    const long cap = (long)device_cus() * boj_gp_blocks_per_cu(boj_layout(m->hidden).P, T);
-    return B < cap ? B : (int)cap;
-}
+int bojanet_gp_rows(const odpd_model_t* m, int B, int T) { return gp_rows(B, boj_gp_blocks_per_cu(m->hidden, T)); }
 int bojanet_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    const size_t lds = boj_gp_lds_bytes(boj_layout(m->hidden).P, a.T);
-    if (int e = allow_big_lds(boj_gp_train_kernel, lds)) return e;
-    hipLaunchKernelGGL(boj_gp_train_kernel, dim3(bojanet_gp_rows(m, a.B, a.T)), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_seq(st, boj_gp_train_kernel, bojanet_gp_rows(m, a.B, a.T), boj_gp_lds_bytes(boj_layout(m->hidden).P, a.T), a);
 }
 // mode 1 forward, 2 backward
 int bojanet_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int mode) {
@@ -913,27 +834,14 @@ int bojanet_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
     const int P = boj_layout(m->hidden).P;
-    if (mode == 1 && !a.ckpt && a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0) {
-        // sequences that each get a SIMD of their own (inference: no checkpoints)
-        const size_t lds = ((size_t)pad4(P) + kBevFloats) * sizeof(float);
-        if (int e = allow_big_lds(boj_gp_eval_kernel, lds)) return e;
-        hipLaunchKernelGGL(boj_gp_eval_kernel, dim3(a.B), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    }
+    if (gp_eval_fits(a, mode)) return launch_seq(st, boj_gp_eval_kernel, a.B, ((size_t)pad4(P) + kBevFloats) * sizeof(float), a);
     if (mode == 1) {
-        const LaunchShape ls = b16_shape(a.ngroups, a.ngroups <= 4 * device_cus() ? 4 : 8);
-        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(B16::NG) + (size_t)ls.waves * (2 * 16 * kBojRow + 2 * 16 * kChunkPad)) * sizeof(float);
-        auto k = boj16_fwd_kernel;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
+        const LaunchShape ls = s16_fwd_shape(a.ngroups);
+        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(B16::NG) + (size_t)ls.waves * b16_fwd_wave_floats()) * sizeof(float);
+        return launch_lds(st, boj16_fwd_kernel, ls.grid, 64 * ls.waves, lds, a);
     }
     if (!a.ckpt && a.nck > 1) return ODPD_EINVAL;
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    if (nw && dx) return b16_launch_bwd<true, true>(st, a, P);
-    if (nw) return b16_launch_bwd<true, false>(st, a, P);
-    return b16_launch_bwd<false, true>(st, a, P);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return b16_launch_bwd<decltype(nw)::value, decltype(dx)::value>(st, a, P); });
 }
 
 }  // namespace odpd

@@ -44,7 +44,7 @@ __device__ __forceinline__ void load_delta_w(DeltaW<TRES>& w, const float* pl, c
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         w.wout[c] = vo ? pl[L.o_w_out + c * H + o] : 0.0f;
-        w.bout[c] = TRES ? 0.0f : __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl[L.o_b_out + c])));
+        w.bout[c] = TRES ? 0.0f : uni_(pl[L.o_b_out + c]);
     }
     const int cc = col < 3 ? col : 2;
 #pragma unroll
@@ -942,17 +942,11 @@ static int delta_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
 
 // the gate-parallel backward kernel: one sequence per single-wave workgroup, the frame's parked state in LDS
 static size_t delta_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + delta_gp_buffer_floats(T)) * sizeof(float); }
-static int delta_gp_blocks_per_cu(int P, int T) {
-    const size_t lds = delta_gp_lds_bytes(P, T);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int delta_gp_blocks_per_cu(int P, int T) { return gp_blocks_per_cu(delta_gp_lds_bytes(P, T), 4); }
 static bool delta_bwd_uses_gp(const odpd_model_t* m, int B, int T) {
     if (m->hidden > 16 || delta_uses_s16(m, B) || tuning().s16_min_batch == 0) return false;
     const int P = delta_layout(m->hidden, m->backbone == ODPD_TRES_DELTAGRU).P;
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && delta_gp_blocks_per_cu(P, T) > 0;
-    return (long)B <= (long)device_cus() * delta_gp_blocks_per_cu(P, T);      // every sequence resident at once
+    return gp_batch_fits(B, delta_gp_blocks_per_cu(P, T), 1);      // every sequence resident at once
 }
 static int delta_gp_rows(const odpd_model_t* m, int B, int T) {
     const int P = delta_layout(m->hidden, m->backbone == ODPD_TRES_DELTAGRU).P;
@@ -978,10 +972,8 @@ static bool jan_gp_ok(const odpd_model_t* m) {
 }
 static bool jan_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if (!jan_gp_ok(m)) return false;
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && delta_gp_blocks_per_cu(jan_P(m), T) > 0;
     // up to three frames per workgroup in turn: still ahead of the 16-sequence waves there (768 x 200: 0.31 vs 0.44 ms, profiles/r03/gp_train_bench.txt)
-    return (long)B <= 3L * device_cus() * delta_gp_blocks_per_cu(jan_P(m), T);
+    return gp_batch_fits(B, delta_gp_blocks_per_cu(jan_P(m), T), 3);
 }
 static int jan_gp_rows(const odpd_model_t* m, int B, int T) {
     const long cap = (long)device_cus() * (kMaxLds / delta_gp_lds_bytes(jan_P(m), T));

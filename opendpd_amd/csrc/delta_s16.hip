@@ -92,21 +92,18 @@ __device__ __forceinline__ float4 d16_entry(const float* pl, const DeltaLayout& 
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 
-__device__ __forceinline__ float d16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 __device__ __forceinline__ float d16_hsg(float v) { return v < -3.0f ? 0.0f : (v <= 3.0f ? __builtin_fmaf(v, 1.0f / 3.0f, 0.5f) : 1.0f); }
 
 template <bool TRES>
 struct D16Scalars {                 // per-sequence parameters, uniform across lanes
     float bout[2], w1[18], w2[6];
     __device__ __forceinline__ void load(const float* pl, const DeltaLayout& L) {
-        bout[0] = TRES ? 0.0f : d16_uni(pl[L.o_b_out]);
-        bout[1] = TRES ? 0.0f : d16_uni(pl[L.o_b_out + 1]);
+        bout[0] = TRES ? 0.0f : uni_(pl[L.o_b_out]);
+        bout[1] = TRES ? 0.0f : uni_(pl[L.o_b_out + 1]);
 #pragma unroll
-        for (int i = 0; i < 18; ++i) w1[i] = TRES ? d16_uni(pl[L.o_tcn0 + i]) : 0.0f;
+        for (int i = 0; i < 18; ++i) w1[i] = TRES ? uni_(pl[L.o_tcn0 + i]) : 0.0f;
 #pragma unroll
-        for (int i = 0; i < 6; ++i) w2[i] = TRES ? d16_uni(pl[L.o_tcn2 + i]) : 0.0f;
+        for (int i = 0; i < 6; ++i) w2[i] = TRES ? uni_(pl[L.o_tcn2 + i]) : 0.0f;
     }
 };
 

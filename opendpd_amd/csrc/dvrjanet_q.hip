@@ -62,7 +62,7 @@ __device__ __forceinline__ void dvq_setup(float* pl, const SeqArgs& a, const Dvq
     Q.K = L.K;
 #pragma unroll
     for (int k = 0; k < kVK; ++k) {
-        Q.cs[k] = k < L.K ? qc_uni(pl[L.ocs + (k < L.K ? k : 0)]) : 0.0f;
+        Q.cs[k] = k < L.K ? uni_(pl[L.ocs + (k < L.K ? k : 0)]) : 0.0f;
         Q.knot[k] = (float)((double)(k + 1) / (double)L.K);      // (dvrjanet.py:38: the Python float k / num_k, rounded when it meets the fp32 tensor)
     }
 }

@@ -9,7 +9,7 @@
 // K = num_dvr_units (odpd_model_t::bits_w, <= 8 here).  sin / cos / atan2 are the device library's accurate functions (the
 // reference's are torch's).  The f rows are stored pre-multiplied by -log2(e).  BPTT: checkpoint of (h_I, h_Q) every kCkptStride
 // steps + block recompute; dL/dx through theta and |x|.  One mapping for every batch size (there is no row-rotated DVRJANET kernel).
-#include "odpd_s16.h"
+#include "odpd_f4s16.h"
 
 namespace odpd {
 namespace {
@@ -69,14 +69,9 @@ __device__ __forceinline__ float4 v16_entry(const float* pl, const DvrLayout& L,
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ void v16_build_table(float* tab, const float* pl, const DvrLayout& L, int lane, int wave, int nwb) {
-    float4* t4 = reinterpret_cast<float4*>(tab);
-    for (int grp = wave; grp < V16::NG; grp += nwb) t4[grp * 64 + lane] = v16_entry(pl, L, grp, lane & 15, lane >> 4);
-    __syncthreads();
-}
-__device__ __forceinline__ float v16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
+// per-wave LDS floats of the two kernels: x, y or dL/dy (, dL/dx), transpose tiles
+__host__ __device__ constexpr int v16_fwd_wave_floats() { return 2 * 2 * 16 * kChunkPad; }
+__host__ __device__ constexpr int v16_bwd_wave_floats(bool NW, bool DX) { return (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? V16::kTiles * kTileFloats : 0); }
 // the DVR knots k/K, k = 1..K (dvrjanet.py:38-40: |x - k/num_k| c_k), formed on the host and passed by value (scalar registers)
 struct DvrKnots { float v[kDvrMaxK]; };
 inline DvrKnots dvr_knots(int K) {
@@ -92,10 +87,10 @@ struct V16Uni {
         K = L.K;
 #pragma unroll
         for (int k = 0; k < kDvrMaxK; ++k) {
-            cs[k] = v16_uni(pl[L.o_cs + (k < L.K ? k : 0)]) * (k < L.K ? 1.0f : 0.0f);      // unused units: coefficient 0
+            cs[k] = uni_(pl[L.o_cs + (k < L.K ? k : 0)]) * (k < L.K ? 1.0f : 0.0f);      // unused units: coefficient 0
             knot[k] = kn.v[k];
         }
-        bo1 = v16_uni(pl[L.o_bo1]); bo2 = v16_uni(pl[L.o_bo2]);
+        bo1 = uni_(pl[L.o_bo1]); bo2 = uni_(pl[L.o_bo2]);
     }
 };
 __device__ __forceinline__ void v16_inputs(float2 xv, float& mag, float& theta) {
@@ -113,21 +108,15 @@ __device__ __forceinline__ f32x4 v16_tied(f32x4 v, float dep) {      // the same
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(dep));
     return f32x4{a, b, c, d};
 }
-__device__ __forceinline__ f32x4 v16_mv(TabPtr tl, int grp, const f32x4& v, f32x4 acc) {
-    f32x4 a1[1] = {acc};
-    const f32x4 v1[1] = {v};
-    s16n_matvec<1>(tl, grp, v1, a1);
-    return a1[0];
-}
 
 // forward step.  Padded units (>= H) have all-zero operands: th = ap = 0, f = 1/2, g = 0 -> both states stay 0; their a cos(th)
 // is not 0 but only meets zero table columns.
 __device__ __forceinline__ void v16_cell_fwd(TabPtr tl, const V16Uni& U, float mag, float theta, f32x4& hI, f32x4& hQ, f32x4& th,
                                              f32x4& ap, f32x4& at, f32x4& co, f32x4& si, f32x4& f, f32x4& gc, f32x4& gs) {
     const f32x4 hs = add4(hI, hQ);
-    th = v16_mv(tl, V16::FW + 0, hs, mul4(as_f32x4(tab_ld(tl, (V16::SC + 0) * 64)), splat4(theta)));
-    ap = v16_mv(tl, V16::FW + 1, hs, mul4(as_f32x4(tab_ld(tl, (V16::SC + 1) * 64)), splat4(mag)));
-    const f32x4 pf = v16_mv(tl, V16::FW + 2, hs, as_f32x4(tab_ld(tl, (V16::SC + 2) * 64)));
+    th = s16_mv(tl, V16::FW + 0, hs, mul4(as_f32x4(tab_ld(tl, (V16::SC + 0) * 64)), splat4(theta)));
+    ap = s16_mv(tl, V16::FW + 1, hs, mul4(as_f32x4(tab_ld(tl, (V16::SC + 1) * 64)), splat4(mag)));
+    const f32x4 pf = s16_mv(tl, V16::FW + 2, hs, as_f32x4(tab_ld(tl, (V16::SC + 2) * 64)));
     at = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < kDvrMaxK; ++k)
@@ -135,10 +124,10 @@ __device__ __forceinline__ void v16_cell_fwd(TabPtr tl, const V16Uni& U, float m
     ODPD_EACH4 { float sv, cv; sincosf_(th[i], sv, cv); si[i] = sv; co[i] = cv; }
     f = sigmoid4_prescaled(pf);
     f32x4 pc = as_f32x4(tab_ld(tl, (V16::SC + 3) * 64)), ps = as_f32x4(tab_ld(tl, (V16::SC + 4) * 64));
-    pc = v16_mv(tl, V16::FW + 3, hI, pc);
-    pc = v16_mv(tl, V16::FW + 4, mul4(at, co), pc);
-    ps = v16_mv(tl, V16::FW + 5, hQ, ps);
-    ps = v16_mv(tl, V16::FW + 6, mul4(at, si), ps);
+    pc = s16_mv(tl, V16::FW + 3, hI, pc);
+    pc = s16_mv(tl, V16::FW + 4, mul4(at, co), pc);
+    ps = s16_mv(tl, V16::FW + 5, hQ, ps);
+    ps = s16_mv(tl, V16::FW + 6, mul4(at, si), ps);
     gc = tanh4_precise(pc); gs = tanh4_precise(ps);
     hI = fma4(f, sub4(hI, gc), gc);              // f h + (1 - f) g
     hQ = fma4(f, sub4(hQ, gs), gs);
@@ -148,7 +137,7 @@ __device__ __forceinline__ void v16_cell_fwd(TabPtr tl, const V16Uni& U, float m
 // forward
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 1) void dvr16_fwd_kernel(SeqArgs a, int K, DvrKnots kn) {
-    constexpr int S = kCkptStride, kWave = 2 * 2 * 16 * kChunkPad;
+    constexpr int S = kCkptStride, kWave = v16_fwd_wave_floats();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(512, 1) void dvr16_fwd_kernel(SeqArgs a, int K, Dvr
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    v16_build_table(tab, pl, L, lane, wave, nwb);
+    s16_build_table<V16::NG, v16_entry>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
     V16Uni U;
     U.load(pl, L, kn);
@@ -256,9 +245,9 @@ __device__ __forceinline__ void v16_bwd_block(TabPtr tl0, const V16Uni& U, V16Gr
                 G.dwo[1] = fma4(splat4(dyv.y), fma4(f, sub4(hQp, gs), gs), G.dwo[1]);
                 G.db[0] = add4(G.db[0], dfp); G.db[1] = add4(G.db[1], dgc); G.db[2] = add4(G.db[2], dgs);
             }
-            nI = v16_mv(tl, V16::TR + 3, dgc, nI);
-            nQ = v16_mv(tl, V16::TR + 5, dgs, nQ);
-            const f32x4 dvc = v16_mv(tl, V16::TR + 4, dgc, z4), dvs = v16_mv(tl, V16::TR + 6, dgs, z4);
+            nI = s16_mv(tl, V16::TR + 3, dgc, nI);
+            nQ = s16_mv(tl, V16::TR + 5, dgs, nQ);
+            const f32x4 dvc = s16_mv(tl, V16::TR + 4, dgc, z4), dvs = s16_mv(tl, V16::TR + 6, dgs, z4);
             // through a cos(th), a sin(th) and the DVR
             // (cos, sin, a and the |ap - k/K| are re-formed here, tied to this step's gradients: left free, the compiler forms all four
             // steps' worth right after the recompute and runs out of registers)
@@ -295,9 +284,9 @@ __device__ __forceinline__ void v16_bwd_block(TabPtr tl0, const V16Uni& U, V16Gr
                 const float im = fast_rcp(mag_s[si]), gm = gmag * im, gt = gth * im * im;
                 if (q == 0) dxs[n * kChunkPad + tt] = make_float2(__builtin_fmaf(gm, xv.x, -gt * xv.y), __builtin_fmaf(gm, xv.y, gt * xv.x));
             }
-            f32x4 dhs = v16_mv(tl, V16::TR + 0, dth, z4);
-            dhs = v16_mv(tl, V16::TR + 1, dap, dhs);
-            dhs = v16_mv(tl, V16::TR + 2, dfp, dhs);          // (only the forward copy of W_f carries -log2(e))
+            f32x4 dhs = s16_mv(tl, V16::TR + 0, dth, z4);
+            dhs = s16_mv(tl, V16::TR + 1, dap, dhs);
+            dhs = s16_mv(tl, V16::TR + 2, dfp, dhs);          // (only the forward copy of W_f carries -log2(e))
             dhI = add4(nI, dhs); dhQ = add4(nQ, dhs);
             if constexpr (NW) {
                 // weight gradients: dM_r += d_r^T (x) src_r
@@ -363,7 +352,7 @@ __device__ __forceinline__ void v16_write_row(float* prow, const DvrLayout& L, V
 template <bool NW, bool DX>
 __global__ __launch_bounds__(256, 1) void dvr16_bwd_kernel(SeqArgs a, int K, DvrKnots kn) {
     constexpr int S = kCkptStride;
-    constexpr int kWave = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? V16::kTiles * kTileFloats : 0);
+    constexpr int kWave = v16_bwd_wave_floats(NW, DX);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -371,7 +360,7 @@ __global__ __launch_bounds__(256, 1) void dvr16_bwd_kernel(SeqArgs a, int K, Dvr
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    v16_build_table(tab, pl, L, lane, wave, nwb);
+    s16_build_table<V16::NG, v16_entry>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
     V16Uni U;
     U.load(pl, L, kn);
@@ -425,33 +414,17 @@ __global__ __launch_bounds__(256, 1) void dvr16_bwd_kernel(SeqArgs a, int K, Dvr
         __syncthreads();
         v16_write_row(smem + wave * P4, L, G, lane, n, q);
         __syncthreads();
-        float* prow = a.partials + (size_t)blockIdx.x * P4;
-        for (int i = threadIdx.x; i < P4; i += blockDim.x) {
-            float v = smem[i];
-            for (int wv = 1; wv < nwb; ++wv) v += smem[wv * P4 + i];
-            prow[i] = v;
-        }
+        s16_reduce_rows(smem, a.partials + (size_t)blockIdx.x * P4, P4, nwb);
     }
 }
 
-LaunchShape v16_shape(int ngroups, int waves) {
-    LaunchShape ls;
-    ls.waves = waves;
-    const int need = (ngroups + waves - 1) / waves, cus = device_cus();
-    ls.grid = need < cus ? need : cus;
-    return ls;
-}
 template <bool NW, bool DX>
 int v16_launch_bwd(hipStream_t st, const SeqArgs& a, int P, int K) {
-    const LaunchShape ls = v16_shape(a.ngroups, 4);
-    size_t lds = ((size_t)pad4(P) + s16_tab_floats(V16::NG) +
-                  (size_t)ls.waves * ((DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? V16::kTiles * kTileFloats : 0))) * sizeof(float);
+    const LaunchShape ls = s16_group_shape(a.ngroups, 4);
+    size_t lds = ((size_t)pad4(P) + s16_tab_floats(V16::NG) + (size_t)ls.waves * v16_bwd_wave_floats(NW, DX)) * sizeof(float);
     if (NW && lds < reduce_scratch_bytes(P, ls.waves)) lds = reduce_scratch_bytes(P, ls.waves);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = dvr16_bwd_kernel<NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a, K, dvr_knots(K));
-    return (int)hipGetLastError();
+    return launch_lds(st, dvr16_bwd_kernel<NW, DX>, ls.grid, 64 * ls.waves, lds, a, K, dvr_knots(K));
 }
 
 
@@ -757,11 +730,7 @@ __global__ __launch_bounds__(64) void dvr_gp_eval_kernel(SeqArgs a, int K, DvrKn
 }
 
 static size_t dvr_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + vgp_buffer_floats(T)) * sizeof(float); }
-static int dvr_gp_blocks_per_cu(int P, int T) {
-    const size_t lds = dvr_gp_lds_bytes(P, T);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int dvr_gp_blocks_per_cu(const odpd_model_t* m, int T) { return gp_blocks_per_cu(dvr_gp_lds_bytes(dvr_layout(m->hidden, m->bits_w).P, T), 4); }
 
 }  // namespace
 
@@ -771,7 +740,7 @@ int64_t dvrjanet_param_count(const odpd_model_t* m) {
 }
 int dvrjanet_rows(const odpd_model_t* m, int B) {
     if (!dvrjanet_ok(m)) return ODPD_EUNSUPPORTED;
-    return v16_shape((B + 15) / 16, 4).grid;
+    return s16_group_shape((B + 15) / 16, 4).grid;
 }
 int64_t dvrjanet_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!dvrjanet_ok(m)) return ODPD_EUNSUPPORTED;
@@ -780,22 +749,13 @@ int64_t dvrjanet_ckpt_floats(const odpd_model_t* m, int B, int T) {
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, the frame's step records in LDS
 bool dvrjanet_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if (!dvrjanet_ok(m)) return false;
-    const int per_cu = dvr_gp_blocks_per_cu(dvr_layout(m->hidden, m->bits_w).P, T);
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && per_cu > 0;
     // up to five rounds of workgroups (measured: profiles/r03/gp_train_bench_f4.txt): the alternative is the forward / loss / backward chain of the S16 kernels
-    return (long)B <= 5L * device_cus() * per_cu;
+    return gp_batch_fits(B, dvr_gp_blocks_per_cu(m, T), 5);
 }
-int dvrjanet_gp_rows(const odpd_model_t* m, int B, int T) {
-    const long cap = (long)device_cus() * dvr_gp_blocks_per_cu(dvr_layout(m->hidden, m->bits_w).P, T);
-    return B < cap ? B : (int)cap;
-}
+int dvrjanet_gp_rows(const odpd_model_t* m, int B, int T) { return gp_rows(B, dvr_gp_blocks_per_cu(m, T)); }
 int dvrjanet_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const int K = m->bits_w;
-    const size_t lds = dvr_gp_lds_bytes(dvr_layout(m->hidden, K).P, a.T);
-    if (int e = allow_big_lds(dvr_gp_train_kernel, lds)) return e;
-    hipLaunchKernelGGL(dvr_gp_train_kernel, dim3(dvrjanet_gp_rows(m, a.B, a.T)), dim3(64), lds, st, a, K, dvr_knots(K));
-    return (int)hipGetLastError();
+    return launch_seq(st, dvr_gp_train_kernel, dvrjanet_gp_rows(m, a.B, a.T), dvr_gp_lds_bytes(dvr_layout(m->hidden, K).P, a.T), a, K, dvr_knots(K));
 }
 // mode 1 forward, 2 backward
 int dvrjanet_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int mode) {
@@ -803,27 +763,14 @@ int dvrjanet_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, in
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
     const int K = m->bits_w, P = dvr_layout(m->hidden, K).P;
-    if (mode == 1 && !a.ckpt && a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0) {
-        // sequences that each get a SIMD of their own (inference: no checkpoints)
-        const size_t lds = ((size_t)pad4(P) + kVevFloats) * sizeof(float);
-        if (int e = allow_big_lds(dvr_gp_eval_kernel, lds)) return e;
-        hipLaunchKernelGGL(dvr_gp_eval_kernel, dim3(a.B), dim3(64), lds, st, a, K, dvr_knots(K));
-        return (int)hipGetLastError();
-    }
+    if (gp_eval_fits(a, mode)) return launch_seq(st, dvr_gp_eval_kernel, a.B, ((size_t)pad4(P) + kVevFloats) * sizeof(float), a, K, dvr_knots(K));
     if (mode == 1) {
-        const LaunchShape ls = v16_shape(a.ngroups, a.ngroups <= 4 * device_cus() ? 4 : 8);
-        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(V16::NG) + (size_t)ls.waves * (2 * 2 * 16 * kChunkPad)) * sizeof(float);
-        auto k = dvr16_fwd_kernel;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a, K, dvr_knots(K));
-        return (int)hipGetLastError();
+        const LaunchShape ls = s16_fwd_shape(a.ngroups);
+        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(V16::NG) + (size_t)ls.waves * v16_fwd_wave_floats()) * sizeof(float);
+        return launch_lds(st, dvr16_fwd_kernel, ls.grid, 64 * ls.waves, lds, a, K, dvr_knots(K));
     }
     if (!a.ckpt && a.nck > 1) return ODPD_EINVAL;
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    if (nw && dx) return v16_launch_bwd<true, true>(st, a, P, K);
-    if (nw) return v16_launch_bwd<true, false>(st, a, P, K);
-    return v16_launch_bwd<false, true>(st, a, P, K);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return v16_launch_bwd<decltype(nw)::value, decltype(dx)::value>(st, a, P, K); });
 }
 
 }  // namespace odpd

@@ -59,7 +59,7 @@ __device__ __forceinline__ void load_gru_w(GruW<R, F, DG>& w, const float* pl, c
     for (int c = 0; c < 2; ++c) {
         w.wout[c] = vo ? pl[L.o_w_out + c * OW + o] : 0.0f;
         // uniform across lanes: keep it in an SGPR
-        w.bout[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl[L.o_b_out + c])));
+        w.bout[c] = uni_(pl[L.o_b_out + c]);
         w.woutf[c] = (DG && row == 0 && col < 6) ? pl[L.o_w_out + c * OW + H + col] : 0.0f;
     }
     w.bhid = (DG && vo) ? pl[L.o_b_hid + o] : 0.0f;
@@ -1463,19 +1463,13 @@ static size_t gp_lds_bytes(int P, int R, bool DG, int T, bool pg) {
     return ((size_t)pad4(P) + buf) * sizeof(float);
 }
 // workgroups of a CU that the frame's LDS-resident BPTT state allows (at most one per SIMD)
-static int gp_blocks_per_cu(int P, int R, bool DG, int T, bool pg) {
-    const size_t lds = gp_lds_bytes(P, R, DG, T, pg);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int gp_blocks_per_cu(int P, int R, bool DG, int T, bool pg) { return odpd::gp_blocks_per_cu(gp_lds_bytes(P, R, DG, T, pg), 4); }
 // the variant that parks the gates is taken while every sequence of the batch still gets its own SIMD
 static bool gp_parks_gates(int P, int R, bool DG, int B, int T) { return (long)B <= (long)device_cus() * gp_blocks_per_cu(P, R, DG, T, true); }
 bool gru_train_uses_gp(const odpd_model_t* m, int B, int T) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || gru_uses_s16n(m, B) || gru_train_uses_s16(m, B, T)) return false;
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && gp_blocks_per_cu(P, R, DG, T, false) > 0;
-    return (long)B <= (long)device_cus() * gp_blocks_per_cu(P, R, DG, T, false);        // one sequence per SIMD, all resident at once
+    return gp_batch_fits(B, gp_blocks_per_cu(P, R, DG, T, false), 1);        // one sequence per SIMD, all resident at once
 }
 // the split backward (dL/dy given) on the same kernel: hidden <= 16, every sequence resident at once
 static bool gru_bwd_uses_gp(const odpd_model_t* m, int B, int T) {

@@ -50,7 +50,7 @@ __device__ __forceinline__ void load_janet_w(JanetW& w, const float* pl, const J
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         w.wo[c] = vo ? pl[L.o_wo + c * H + o] : 0.f;
-        w.bo[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl[L.o_bo + c])));
+        w.bo[c] = uni_(pl[L.o_bo + c]);
     }
 }
 
@@ -586,18 +586,11 @@ static LaunchShape janet_bwd_shape(int ngroups) { return persistent_shape(ngroup
 
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, the frame's parked state in LDS
 static size_t janet_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + janet_gp_buffer_floats(T)) * sizeof(float); }
-static int janet_gp_blocks_per_cu(int P, int T) {
-    const size_t lds = janet_gp_lds_bytes(P, T);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int janet_gp_blocks_per_cu(int P, int T) { return gp_blocks_per_cu(janet_gp_lds_bytes(P, T), 4); }
 bool janet_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if (m->backbone != ODPD_PGJANET || m->hidden > 16 || janet_uses_s16(m, B)) return false;
-    const int P = janet_layout(m->hidden).P;
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && janet_gp_blocks_per_cu(P, T) > 0;
     // up to two rounds of workgroups: the alternative is the forward / loss / backward chain of the row-rotated kernels
-    return (long)B <= 2L * device_cus() * janet_gp_blocks_per_cu(P, T);
+    return gp_batch_fits(B, janet_gp_blocks_per_cu(janet_layout(m->hidden).P, T), 2);
 }
 int janet_gp_rows(const odpd_model_t* m, int B, int T) {
     const int P = janet_layout(m->hidden).P;

@@ -8,7 +8,7 @@
 // The f rows (weights and bias) are stored pre-multiplied by -log2(e).  BPTT: checkpoint of h every kCkptStride steps
 // (one float4 per lane and unit tile) + block recompute; dL/dx (frozen PA of a cascade) through the three scalar input
 // columns and the polar features.  Used from the batch size that fills the chip with 16-sequence waves.
-#include "odpd_s16.h"
+#include "odpd_f4s16.h"
 
 namespace odpd {
 
@@ -65,9 +65,6 @@ __device__ __forceinline__ float4 j16_entry(const float* pl, const JanetLayout& 
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 
-__device__ __forceinline__ float j16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 __device__ __forceinline__ void j16_inputs(float2 xv, float& amp, float& ct, float& st) {
     const float a2 = __builtin_fmaf(xv.x, xv.x, xv.y * xv.y);
     amp = __builtin_amdgcn_sqrtf(a2);
@@ -113,22 +110,20 @@ __device__ __forceinline__ void j16_cell_fwd(TabPtr tl, float amp, float ct, flo
     }
 }
 
-template <int NT>
-__device__ __forceinline__ void j16_build_table(float* tab, const float* pl, const JanetLayout& L, int lane, int wave, int nwb) {
-    float4* t4 = reinterpret_cast<float4*>(tab);
-    for (int grp = wave; grp < J16<NT>::NG; grp += nwb) t4[grp * 64 + lane] = j16_entry<NT>(pl, L, grp, lane & 15, lane >> 4);
-    __syncthreads();
-}
 
 // -------------------------------------------------------------------------------------------------
 // forward
 // -------------------------------------------------------------------------------------------------
 // (r06: 16-step chunks — the kernel's 96 registers allow four waves per SIMD, its 94 KB workgroup let one onto a CU)
 constexpr int kJ16FwdChunk = 16;
+// per-wave LDS floats of the two kernels: x, y or dL/dy (, dL/dx), transpose tiles
+__host__ __device__ constexpr int j16_fwd_wave_floats() { return 2 * 2 * 16 * (kJ16FwdChunk + 1); }
+template <int NT>
+__host__ __device__ constexpr int j16_bwd_wave_floats(bool NW, bool DX) { return (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? J16<NT>::kTiles * kTileFloats : 0); }
 template <int NT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void janet16_fwd_kernel(SeqArgs a) {
     using T = J16<NT>;
-    constexpr int S = kCkptStride, CH = kJ16FwdChunk, kWave = 2 * 2 * 16 * (CH + 1);
+    constexpr int S = kCkptStride, CH = kJ16FwdChunk, kWave = j16_fwd_wave_floats();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -136,9 +131,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    j16_build_table<NT>(tab, pl, L, lane, wave, nwb);
+    s16_build_table<T::NG, j16_entry<NT>>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
-    const float bo0 = j16_uni(pl[L.o_bo]), bo1 = j16_uni(pl[L.o_bo + 1]);
+    const float bo0 = uni_(pl[L.o_bo]), bo1 = uni_(pl[L.o_bo + 1]);
     float* wbase = tab + s16_tab_floats(T::NG) + (size_t)wave * kWave;
     float2* xs = reinterpret_cast<float2*>(wbase);
     float2* ys = xs + 16 * (CH + 1);
@@ -372,7 +367,7 @@ template <int NT, bool NW, bool DX>
 __global__ __launch_bounds__(256, 1) void janet16_bwd_kernel(SeqArgs a) {
     using T = J16<NT>;
     constexpr int S = kCkptStride;
-    constexpr int kWave = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? T::kTiles * kTileFloats : 0);
+    constexpr int kWave = j16_bwd_wave_floats<NT>(NW, DX);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -380,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void janet16_bwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* tab = smem + pad4(L.P);
-    j16_build_table<NT>(tab, pl, L, lane, wave, nwb);
+    s16_build_table<T::NG, j16_entry<NT>>(tab, pl, L, lane, wave, nwb);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
     float* wbase = tab + s16_tab_floats(T::NG) + (size_t)wave * kWave;
     float2* xs = reinterpret_cast<float2*>(wbase);
@@ -435,12 +430,7 @@ __global__ __launch_bounds__(256, 1) void janet16_bwd_kernel(SeqArgs a) {
         __syncthreads();
         j16_write_row<NT>(smem + wave * P4, L, G, lane, n, q);
         __syncthreads();
-        float* prow = a.partials + (size_t)blockIdx.x * P4;
-        for (int i = threadIdx.x; i < P4; i += blockDim.x) {
-            float v = smem[i];
-            for (int wv = 1; wv < nwb; ++wv) v += smem[wv * P4 + i];
-            prow[i] = v;
-        }
+        s16_reduce_rows(smem, a.partials + (size_t)blockIdx.x * P4, P4, nwb);
     }
 }
 
@@ -453,16 +443,9 @@ bool janet_uses_s16(const odpd_model_t* m, int B) {
     if (min_batch < 0) min_batch = 16L * 4 * device_cus();
     return B >= min_batch;
 }
-static LaunchShape j16_shape(int ngroups, int waves) {
-    LaunchShape ls;
-    ls.waves = waves;
-    const int need = (ngroups + waves - 1) / waves, cus = device_cus();
-    ls.grid = need < cus ? need : cus;
-    return ls;
-}
 int janet_s16_rows(const odpd_model_t* m, int B) {
     (void)m;
-    return j16_shape((B + 15) / 16, 4).grid;
+    return s16_group_shape((B + 15) / 16, 4).grid;
 }
 int64_t janet_s16_ckpt_floats(const odpd_model_t* m, int B, int T) {
     (void)m;
@@ -471,15 +454,11 @@ int64_t janet_s16_ckpt_floats(const odpd_model_t* m, int B, int T) {
 template <bool NW, bool DX>
 static int j16_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
     using T = J16<1>;
-    const LaunchShape ls = j16_shape(a.ngroups, 4);
-    size_t lds = ((size_t)pad4(P) + s16_tab_floats(T::NG) +
-                  (size_t)ls.waves * ((DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? T::kTiles * kTileFloats : 0))) * sizeof(float);
+    const LaunchShape ls = s16_group_shape(a.ngroups, 4);
+    size_t lds = ((size_t)pad4(P) + s16_tab_floats(T::NG) + (size_t)ls.waves * j16_bwd_wave_floats<1>(NW, DX)) * sizeof(float);
     if (NW && lds < reduce_scratch_bytes(P, ls.waves)) lds = reduce_scratch_bytes(P, ls.waves);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = janet16_bwd_kernel<1, NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, janet16_bwd_kernel<1, NW, DX>, ls.grid, 64 * ls.waves, lds, a);
 }
 int janet_s16_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int mode) {
     using T = J16<1>;
@@ -487,22 +466,15 @@ int janet_s16_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, i
     a.ngroups = (a.B + 15) / 16;
     const int P = janet_layout(m->hidden).P;
     if (mode == 1) {
-        LaunchShape ls = j16_shape(a.ngroups, a.ngroups <= 4 * device_cus() ? 4 : 8);
-        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(T::NG) + (size_t)ls.waves * (2 * 2 * 16 * (kJ16FwdChunk + 1))) * sizeof(float);
+        LaunchShape ls = s16_fwd_shape(a.ngroups);
+        const size_t lds = ((size_t)pad4(P) + s16_tab_floats(T::NG) + (size_t)ls.waves * j16_fwd_wave_floats()) * sizeof(float);
         if (ls.waves == 8 && 2 * lds <= kMaxLds) {      // two eight-wave workgroups per CU = four waves per SIMD
             const int need = (a.ngroups + 7) / 8, cap = 2 * device_cus();
             ls.grid = need < cap ? need : cap;
         }
-        auto k = janet16_fwd_kernel<1>;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
+        return launch_lds(st, janet16_fwd_kernel<1>, ls.grid, 64 * ls.waves, lds, a);
     }
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    if (nw && dx) return j16_launch_bwd<true, true>(st, a, P);
-    if (nw) return j16_launch_bwd<true, false>(st, a, P);
-    return j16_launch_bwd<false, true>(st, a, P);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return j16_launch_bwd<decltype(nw)::value, decltype(dx)::value>(st, a, P); });
 }
 
 }  // namespace odpd

@@ -75,16 +75,13 @@ __device__ __forceinline__ void load_lstm_w(LstmW<R, VD>& w, const float* pl, co
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         w.wout[c] = (!VD && vo) ? pl[L.o_w_out + c * H + o] : 0.0f;
-        w.bout[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl[L.o_b_out + c])));
+        w.bout[c] = uni_(pl[L.o_b_out + c]);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         w.wl1[k] = (VD && vo) ? pl[L.o_w_l1 + k * H + o] : 0.0f;
         w.wl2[k] = (VD && vo) ? pl[L.o_w_l2 + k * H + o] : 0.0f;
     }
-}
-__device__ __forceinline__ float uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
 // window of the VDLSTM input at one step
@@ -1203,21 +1200,15 @@ static int lstm_launch_bwd_mode(hipStream_t st, const SeqArgs& a, int P) {
 static size_t lstm_gp_lds_bytes(int P, bool vd, int T, bool pg) {
     return ((size_t)pad4(P) + (vd ? lstm_gp_buffer_floats<true>(T, pg) : lstm_gp_buffer_floats<false>(T, pg))) * sizeof(float);
 }
-static int lstm_gp_blocks_per_cu(int P, bool vd, int T, bool pg) {
-    const size_t lds = lstm_gp_lds_bytes(P, vd, T, pg);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 4 ? n : 4;
-}
+static int lstm_gp_blocks_per_cu(int P, bool vd, int T, bool pg) { return gp_blocks_per_cu(lstm_gp_lds_bytes(P, vd, T, pg), 4); }
 static bool lstm_gp_parks_gates(int P, bool vd, int B, int T) { return (long)B <= (long)device_cus() * lstm_gp_blocks_per_cu(P, vd, T, true); }
 bool lstm_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if ((m->backbone != ODPD_LSTM && m->backbone != ODPD_VDLSTM) || m->hidden > 16 || lstm_train_uses_s16(m, B)) return false;
     const bool vd = m->backbone == ODPD_VDLSTM;
     if (vd && T < kHalo) return false;
     const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && lstm_gp_blocks_per_cu(P, vd, T, false) > 0;
     // up to two rounds of workgroups: the alternative here is the forward / loss / backward chain of the row-rotated kernels
-    return (long)B <= 2L * device_cus() * lstm_gp_blocks_per_cu(P, vd, T, false);
+    return gp_batch_fits(B, lstm_gp_blocks_per_cu(P, vd, T, false), 2);
 }
 int lstm_gp_rows(const odpd_model_t* m, int B, int T) {
     const bool vd = m->backbone == ODPD_VDLSTM;

@@ -25,8 +25,7 @@
         const q16::Quant qw = q16::make_quant(pl[L.o_q_out], a.bits_w), qa = q16::make_quant(pl[L.o_q_out + 1], a.bits_a);
         wm0 = q16::qpass(wo0, qw); wm1 = q16::qpass(wo1, qw);
         wo0 = q16::qapply(wo0, qw); wo1 = q16::qapply(wo1, qw);
-        auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-        qa_inv = uni(qa.inv); qa_s = uni(qa.s); qa_qn = uni(qa.qn); qa_qp = uni(qa.qp);
+        qa_inv = uni_(qa.inv); qa_s = uni_(qa.s); qa_qn = uni_(qa.qn); qa_qp = uni_(qa.qp);
     }
     f32x16 acc[4][4];                          // dW_hh: gate g, the state rotated by 16 r lanes
 #pragma unroll

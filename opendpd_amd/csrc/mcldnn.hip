@@ -16,7 +16,7 @@
 // end), then through the features.  The workgroup DEcomposes its dA, db, dW_fc into the gradients of the three convolutions, W_ih, the
 // biases and the two linear layers (the chain rule through A = W_ih M(w_1, w_1d, w_2)) before it writes its row of partials, so the rows
 // are ordinary parameter-gradient rows.  Frames shorter than 4 samples are refused like the reference's framing (mcldnn.py:115-118).
-#include "odpd_s16.h"
+#include "odpd_f4s16.h"
 
 namespace odpd {
 namespace {
@@ -136,19 +136,10 @@ __device__ __forceinline__ float4 m16_entry(const MclComp& K, const float* pl, c
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ void m16_build_table(float* tab, const MclComp& K, const float* pl, const MclLayout& L, int lane, int wave, int nwb) {
-    float4* t4 = reinterpret_cast<float4*>(tab);
-    for (int grp = wave; grp < M16::NG; grp += nwb) t4[grp * 64 + lane] = m16_entry(K, pl, L, grp, lane & 15, lane >> 4);
-    __syncthreads();
-}
-__device__ __forceinline__ float m16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ f32x4 m16_mv(TabPtr tl, int grp, const f32x4& v, f32x4 acc) {
-    f32x4 a1[1] = {acc};
-    const f32x4 v1[1] = {v};
-    s16n_matvec<1>(tl, grp, v1, a1);
-    return a1[0];
+// per-wave LDS floats of the two kernels: feature table of the chunk (and its gradient), y or dL/dy, transpose tiles
+__host__ __device__ constexpr int m16_fwd_wave_floats() { return 16 * kMclRowF + 2 * 16 * kChunkPad; }
+__host__ __device__ constexpr int m16_bwd_wave_floats(bool NW, bool DX) {
+    return (DX ? 2 : 1) * 16 * kMclRowF + 2 * 16 * kChunkPad + (NW ? M16::kTiles * kTileFloats : 0);
 }
 __device__ __forceinline__ f32x4 m16_swap(const f32x4& v) { return f32x4{swap16(v[0]), swap16(v[1]), swap16(v[2]), swap16(v[3])}; }
 
@@ -182,8 +173,8 @@ __device__ __forceinline__ M16Cell m16_gates(TabPtr tl, const float (&pv)[7], co
         for (int e = 0; e < 4; ++e)
             if (4 * g2 + e < 7) { p0 = mfma4(w0[e], pv[4 * g2 + e], p0); p1 = mfma4(w1[e], pv[4 * g2 + e], p1); }
     }
-    p0 = m16_mv(tl, M16::WHH + 0, h, p0);
-    p1 = m16_mv(tl, M16::WHH + 1, h, p1);
+    p0 = s16_mv(tl, M16::WHH + 0, h, p0);
+    p1 = s16_mv(tl, M16::WHH + 1, h, p1);
     M16Cell c;
     c.s0 = sigmoid4_prescaled(p0);
     const f32x4 sg = sigmoid4_prescaled(p1), th = tanh4_precise(p1);
@@ -204,7 +195,7 @@ __device__ __forceinline__ void m16_update(const M16Cell& g, bool odd, f32x4& c,
 // forward
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 1) void mcl16_fwd_kernel(SeqArgs a) {
-    constexpr int S = kCkptStride, kWave = 16 * kMclRowF + 2 * 16 * kChunkPad;
+    constexpr int S = kCkptStride, kWave = m16_fwd_wave_floats();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -216,9 +207,9 @@ __global__ __launch_bounds__(512, 1) void mcl16_fwd_kernel(SeqArgs a) {
     ubase += (4 - ((ubase - smem) & 3)) & 3;
     stage_params(ubase, a.params, L.P);
     mcl_compose(K, ubase, L);
-    m16_build_table(tab, K, ubase, L, lane, wave, nwb);
+    s16_build_table<M16::NG, m16_entry>(tab, ubase, L, lane, wave, nwb, K);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
-    const float bf0 = m16_uni(K.bfc[0]), bf1 = m16_uni(K.bfc[1]);
+    const float bf0 = uni_(K.bfc[0]), bf1 = uni_(K.bfc[1]);
     float* fl = ubase + (size_t)wave * kWave;
     float2* ys = reinterpret_cast<float2*>(fl + 16 * kMclRowF);
     const int nwaves = gridDim.x * nwb;
@@ -319,13 +310,13 @@ __device__ __forceinline__ void m16_bwd_block(TabPtr tl0, bool odd, M16Grad& G, 
                 D1[i] = odd ? dfo1[i] : dig[i] * s0[i] * __builtin_fmaf(-s1[i], s1[i], 1.0f);          // g
             }
             if constexpr (NW) { G.db[0] = add4(G.db[0], D0); G.db[1] = add4(G.db[1], D1); }
-            dh = m16_mv(tl, M16::WHHT + 0, D0, z4);
-            dh = m16_mv(tl, M16::WHHT + 1, D1, dh);
+            dh = s16_mv(tl, M16::WHHT + 0, D0, z4);
+            dh = s16_mv(tl, M16::WHHT + 1, D1, dh);
             if constexpr (DX) {
 #pragma unroll
                 for (int ot = 0; ot < 2; ++ot) {
-                    f32x4 dp = m16_mv(tl, M16::ATT + 2 * ot + 0, D0, z4);
-                    dp = m16_mv(tl, M16::ATT + 2 * ot + 1, D1, dp);
+                    f32x4 dp = s16_mv(tl, M16::ATT + 2 * ot + 0, D0, z4);
+                    dp = s16_mv(tl, M16::ATT + 2 * ot + 1, D1, dp);
                     float* d = dfl + n * kMclRowF + 5 * tt + 16 * ot + 4 * q;
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -450,7 +441,7 @@ __device__ __forceinline__ float m16_param_grad(int i, const float* raw, const f
 template <bool NW, bool DX>
 __global__ __launch_bounds__(256, 1) void mcl16_bwd_kernel(SeqArgs a) {
     constexpr int S = kCkptStride;
-    constexpr int kWave = (DX ? 2 : 1) * 16 * kMclRowF + 2 * 16 * kChunkPad + (NW ? M16::kTiles * kTileFloats : 0);
+    constexpr int kWave = m16_bwd_wave_floats(NW, DX);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -462,7 +453,7 @@ __global__ __launch_bounds__(256, 1) void mcl16_bwd_kernel(SeqArgs a) {
     ubase += (4 - ((ubase - smem) & 3)) & 3;
     stage_params(ubase, a.params, L.P);
     mcl_compose(K, ubase, L);
-    m16_build_table(tab, K, ubase, L, lane, wave, nwb);
+    s16_build_table<M16::NG, m16_entry>(tab, ubase, L, lane, wave, nwb, K);
     const TabPtr tl = to_tab(reinterpret_cast<const float4*>(tab) + lane);
     float* fl = ubase + (size_t)wave * kWave;
     float2* dys = reinterpret_cast<float2*>(fl + 16 * kMclRowF);
@@ -572,27 +563,17 @@ __global__ __launch_bounds__(256, 1) void mcl16_bwd_kernel(SeqArgs a) {
     }
 }
 
-LaunchShape m16_shape(int ngroups, int waves) {
-    LaunchShape ls;
-    ls.waves = waves;
-    const int need = (ngroups + waves - 1) / waves, cus = device_cus();
-    ls.grid = need < cus ? need : cus;
-    return ls;
-}
 size_t m16_front_floats(int C) { return (size_t)s16_tab_floats(M16::NG) + mcl_comp_floats(C) + 4; }
 template <bool NW, bool DX>
 int m16_launch_bwd(hipStream_t st, const SeqArgs& a, int P, int C) {
-    const LaunchShape ls = m16_shape(a.ngroups, 4);
-    size_t body = (size_t)ls.waves * ((DX ? 2 : 1) * 16 * kMclRowF + 2 * 16 * kChunkPad + (NW ? M16::kTiles * kTileFloats : 0));
+    const LaunchShape ls = s16_group_shape(a.ngroups, 4);
+    size_t body = (size_t)ls.waves * m16_bwd_wave_floats(NW, DX);
     const size_t tail = (size_t)ls.waves * kMclRaw + pad4(P) + 5 * C * kMclPP;
     if (body < (size_t)pad4(P)) body = pad4(P);
     if (NW && body < tail) body = tail;
     const size_t lds = (m16_front_floats(C) + body) * sizeof(float);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = mcl16_bwd_kernel<NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, mcl16_bwd_kernel<NW, DX>, ls.grid, 64 * ls.waves, lds, a);
 }
 
 
@@ -917,11 +898,7 @@ __global__ __launch_bounds__(256) void mcl_gp_eval_kernel(SeqArgs a) {
 static size_t mcl_gp_lds_bytes(int C, int T) {
     return ((size_t)pad4(mcl_layout(C).P) + pad4(mcl_comp_floats(C) + kMgpWaves) + mgp_buf(T, C).total) * sizeof(float);
 }
-static int mcl_gp_blocks_per_cu(int C, int T) {
-    const size_t lds = mcl_gp_lds_bytes(C, T);
-    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
-    return n < 2 ? n : 2;
-}
+static int mcl_gp_blocks_per_cu(int C, int T) { return gp_blocks_per_cu(mcl_gp_lds_bytes(C, T), 2); }
 
 }  // namespace
 
@@ -931,7 +908,7 @@ int64_t mcldnn_param_count(const odpd_model_t* m) {
 }
 int mcldnn_rows(const odpd_model_t* m, int B) {
     if (!mcldnn_ok(m)) return ODPD_EUNSUPPORTED;
-    return m16_shape((B + 15) / 16, 4).grid;
+    return s16_group_shape((B + 15) / 16, 4).grid;
 }
 int64_t mcldnn_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!mcldnn_ok(m)) return ODPD_EUNSUPPORTED;
@@ -940,21 +917,12 @@ int64_t mcldnn_ckpt_floats(const odpd_model_t* m, int B, int T) {
 // the fused train kernel of the reference's batch sizes: one sequence per four-wave workgroup, the frame's state in LDS
 bool mcldnn_train_uses_gp(const odpd_model_t* m, int B, int T) {
     if (!mcldnn_ok(m) || T < kMclHalo) return false;
-    const int per_cu = mcl_gp_blocks_per_cu(m->hidden, T);
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0) return B <= max_batch && per_cu > 0;
     // up to four rounds of workgroups (measured: profiles/r03/gp_train_bench_f4.txt): the alternative is the forward / loss / backward chain of the S16 kernels
-    return (long)B <= 4L * device_cus() * per_cu;
+    return gp_batch_fits(B, mcl_gp_blocks_per_cu(m->hidden, T), 4);
 }
-int mcldnn_gp_rows(const odpd_model_t* m, int B, int T) {
-    const long cap = (long)device_cus() * mcl_gp_blocks_per_cu(m->hidden, T);
-    return B < cap ? B : (int)cap;
-}
+int mcldnn_gp_rows(const odpd_model_t* m, int B, int T) { return gp_rows(B, mcl_gp_blocks_per_cu(m->hidden, T)); }
 int mcldnn_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    const size_t lds = mcl_gp_lds_bytes(m->hidden, a.T);
-    if (int e = allow_big_lds(mcl_gp_train_kernel, lds)) return e;
-    hipLaunchKernelGGL(mcl_gp_train_kernel, dim3(mcldnn_gp_rows(m, a.B, a.T)), dim3(kMgpThreads), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, mcl_gp_train_kernel, mcldnn_gp_rows(m, a.B, a.T), kMgpThreads, mcl_gp_lds_bytes(m->hidden, a.T), a);
 }
 // mode 1 forward, 2 backward
 int mcldnn_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int mode) {
@@ -963,29 +931,16 @@ int mcldnn_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int 
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
     const int C = m->hidden, P = mcl_layout(C).P;
-    if (mode == 1 && !a.ckpt && a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0) {
-        // sequences that each get a CU of their own (inference: no checkpoints)
-        const size_t lds = ((size_t)pad4(P) + pad4(mcl_comp_floats(C) + 4) + kMevFloats) * sizeof(float);
-        if (int e = allow_big_lds(mcl_gp_eval_kernel, lds)) return e;
-        hipLaunchKernelGGL(mcl_gp_eval_kernel, dim3(a.B), dim3(256), lds, st, a);
-        return (int)hipGetLastError();
-    }
+    if (gp_eval_fits(a, mode))      // (here a four-wave workgroup per sequence)
+        return launch_lds(st, mcl_gp_eval_kernel, a.B, 256, ((size_t)pad4(P) + pad4(mcl_comp_floats(C) + 4) + kMevFloats) * sizeof(float), a);
     if (mode == 1) {
-        const LaunchShape ls = m16_shape(a.ngroups, a.ngroups <= 4 * device_cus() ? 4 : 8);
-        size_t body = (size_t)ls.waves * (16 * kMclRowF + 2 * 16 * kChunkPad);
+        const LaunchShape ls = s16_fwd_shape(a.ngroups);
+        size_t body = (size_t)ls.waves * m16_fwd_wave_floats();
         if (body < (size_t)pad4(P)) body = pad4(P);
-        const size_t lds = (m16_front_floats(C) + body) * sizeof(float);
-        auto k = mcl16_fwd_kernel;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
+        return launch_lds(st, mcl16_fwd_kernel, ls.grid, 64 * ls.waves, (m16_front_floats(C) + body) * sizeof(float), a);
     }
     if (!a.ckpt && a.nck > 1) return ODPD_EINVAL;
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    if (nw && dx) return m16_launch_bwd<true, true>(st, a, P, C);
-    if (nw) return m16_launch_bwd<true, false>(st, a, P, C);
-    return m16_launch_bwd<false, true>(st, a, P, C);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return m16_launch_bwd<decltype(nw)::value, decltype(dx)::value>(st, a, P, C); });
 }
 
 }  // namespace odpd

@@ -95,6 +95,10 @@ __device__ __forceinline__ float wave_sum64(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// a wave-uniform value into a scalar register
+__device__ __forceinline__ float uni_(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
 // Row select without control flow: a ?: on the row index can come out as exec-mask branches inside a step loop, and an inline-asm
 // v_cndmask hides its VGPR write from the compiler's MFMA hazard handling (a following v_mfma read the stale operand).  So: per-lane
 // all-ones / zero masks, made opaque once at kernel start, and a bitwise blend (one v_bfi_b32).

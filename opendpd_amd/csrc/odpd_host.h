@@ -52,11 +52,37 @@ inline LaunchShape persistent_shape(int ngroups, int waves_per_cu, int max_waves
     if (ls.grid < 1) ls.grid = 1;
     return ls;
 }
+// ... of a 16-sequences-per-wave kernel whose caller fixes `waves`: one workgroup per CU at the most
+inline LaunchShape s16_group_shape(int ngroups, int waves) {
+    LaunchShape ls;
+    ls.waves = waves;
+    const int need = (ngroups + waves - 1) / waves, cus = device_cus();
+    ls.grid = need < cus ? need : cus;
+    return ls;
+}
 
 // run-time tuning knobs (odpd_set_tuning; initialised from $ODPD_S16_MIN_BATCH / $ODPD_S16_OCCUPANCY)
 void audit_lds(const void* kernel, size_t lds);      // $ODPD_AUDIT_LDS: see odpd_seq.h (defined in capi.hip)
 struct Tuning { long s16_min_batch; int s16_occupancy; long gp_max_batch; int cascade_one_launch; int xchg_fused; int s16x; int lstm_pack; int s16x_train; int qat_u3; };
 Tuning& tuning();
+
+// ---- the gate-parallel kernels (one sequence per workgroup, the frame's state in `lds` bytes of LDS) ----
+constexpr size_t kMaxLds = 160 * 1024;
+// workgroups of a CU that the LDS allows, `cap` at the most (0: the frame does not fit)
+inline int gp_blocks_per_cu(size_t lds, int cap) {
+    const int n = lds > kMaxLds ? 0 : (int)(kMaxLds / lds);
+    return n < cap ? n : cap;
+}
+// the fused train kernel is taken for B frames: the "gp_max_batch" knob where it is set, else up to `rounds` rounds of resident workgroups
+inline bool gp_batch_fits(int B, int per_cu, int rounds) {
+    const long max_batch = tuning().gp_max_batch;
+    if (max_batch >= 0) return B <= max_batch && per_cu > 0;
+    return (long)B <= (long)rounds * device_cus() * per_cu;
+}
+inline int gp_rows(int B, int per_cu) {
+    const long cap = (long)device_cus() * per_cu;
+    return B < cap ? B : (int)cap;
+}
 
 // ---- parameter layouts (flattened named_parameters() order of the reference modules) -------------
 struct GruLayout {

@@ -31,11 +31,7 @@ __host__ __device__ inline void qc_fill_layout(QcLayout<NL>& L, int first, Shape
 inline bool qc_bits_ok(const odpd_model_t* m) { return m->bits_w > 0 && m->bits_w <= 16 && m->bits_a > 0 && m->bits_a <= 16; }
 
 // ---- setup --------------------------------------------------------------------------------------
-// a wave-uniform value into a scalar register
-__device__ __forceinline__ float qc_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ void qc_uniform(q16::Quant& q) { q.s = qc_uni(q.s); q.inv = qc_uni(q.inv); }
+__device__ __forceinline__ void qc_uniform(q16::Quant& q) { q.s = uni_(q.s); q.inv = uni_(q.inv); }
 // stage the parameters in pl, form every layer's activation quantiser (qa), quantise the NL weight matrices in the staged copy.
 // UNI: the activation quantisers' scales go through qc_uniform as they are formed.  That is a choice of the kernel, not of the layout: bojanet_q
 // and dvrjanet_q apply them on lanes of every role and want them in scalar registers; pgjanet_q has never done so.  The step sits here, not

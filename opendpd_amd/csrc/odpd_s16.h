@@ -252,6 +252,13 @@ __device__ __forceinline__ void s16n_matvec(TabPtr tl, int base, const f32x4 (&v
             if (kt < kLast || NCK > 3) acc[mt] = mfma4(w.w, v[kt][3], acc[mt]);
         }
 }
+// the one-tile form: acc + T[grp] v
+__device__ __forceinline__ f32x4 s16_mv(TabPtr tl, int grp, const f32x4& v, f32x4 acc) {
+    f32x4 a1[1] = {acc};
+    const f32x4 v1[1] = {v};
+    s16n_matvec<1>(tl, grp, v1, a1);
+    return a1[0];
+}
 
 
 }  // namespace odpd

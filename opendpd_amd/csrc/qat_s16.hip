@@ -392,21 +392,18 @@ __device__ __forceinline__ void delta_cell(TabPtr tl, const QSc& qs, const QK& k
 }
 
 // ---- heads -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float q16_uni(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 __device__ __forceinline__ float q16_hsg(float v) { return v < -3.0f ? 0.0f : (v <= 3.0f ? v * (1.0f / 3.0f) + 0.5f : 1.0f); }
 template <int MK>
 struct Scalars {                 // wave-uniform parameters
     float bout[2], w1[18], w2[6];
     __device__ __forceinline__ void load(const float* pl, const QatLayout& L) {
         constexpr bool TRES = Kind<MK>::TRES;
-        bout[0] = TRES ? 0.0f : q16_uni(pl[L.o_bo]);
-        bout[1] = TRES ? 0.0f : q16_uni(pl[L.o_bo + 1]);
+        bout[0] = TRES ? 0.0f : uni_(pl[L.o_bo]);
+        bout[1] = TRES ? 0.0f : uni_(pl[L.o_bo + 1]);
 #pragma unroll
-        for (int i = 0; i < 18; ++i) w1[i] = TRES ? q16_uni(pl[L.o_tcn0 + i]) : 0.0f;
+        for (int i = 0; i < 18; ++i) w1[i] = TRES ? uni_(pl[L.o_tcn0 + i]) : 0.0f;
 #pragma unroll
-        for (int i = 0; i < 6; ++i) w2[i] = TRES ? q16_uni(pl[L.o_tcn2 + i]) : 0.0f;
+        for (int i = 0; i < 6; ++i) w2[i] = TRES ? uni_(pl[L.o_tcn2 + i]) : 0.0f;
     }
 };
 // TCN skip of one sample: s1[3] pre-activations of the first conv, s2[2] of the second (float path, Conv1d / Hardswish are not swapped)

@@ -140,12 +140,11 @@ __device__ __forceinline__ NtxFir ntx_fir(const float* __restrict__ p, const Tcn
     f.q = bits_w > 0;
     f.qa = q16::Quant{1.0f, 1.0f, 0.0f, 0.0f};
     if (f.q) {      // (wave-uniform values formed on the VALU: moved to scalar registers, the hot loops are register-bound)
-        auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
         const q16::Quant qw = q16::make_quant(p[L.o_m + 4], bits_w);
         const q16::Quant qa = q16::make_quant(p[L.o_m + 5], bits_a);
-        f.qa = q16::Quant{uni(qa.s), uni(qa.inv), uni(qa.qn), uni(qa.qp)};
+        f.qa = q16::Quant{uni_(qa.s), uni_(qa.inv), uni_(qa.qn), uni_(qa.qp)};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { f.mm[k] = uni(q16::qpass(f.m[k], qw)); f.m[k] = uni(q16::qapply(f.m[k], qw)); }
+        for (int k = 0; k < 4; ++k) { f.mm[k] = uni_(q16::qpass(f.m[k], qw)); f.m[k] = uni_(q16::qapply(f.m[k], qw)); }
     }
     return f;
 }
