@@ -319,7 +319,9 @@ int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int K, const od
  * grad is scaled in place like clip_grad_norm_ does.  `step` is the 1-based step index.
  * Hyper-parameters are doubles (Python floats in the reference): 1-beta2 etc. are formed in double
  * and rounded to fp32 once, exactly like torch/optim/adam.py does.
- * norm_out (nullable) receives the pre-clip total norm. */
+ * norm_out (nullable) receives the pre-clip total norm.
+ * Non-finite gradients end as they do in torch: a NaN entry makes the norm, the coefficient, all of grad[0..P) and every stepped
+ * parameter NaN; an inf entry makes the norm inf and the coefficient 0 (that entry NaN, every other gradient 0). */
 int odpd_clip_adamw_step(void* stream, int64_t P, float* params, float* grad, float* exp_avg,
                          float* exp_avg_sq, int64_t step, double lr, double beta1, double beta2,
                          double eps, double weight_decay, double max_norm, float* norm_out);

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void loss_kernel(int kind, int64_t n, float in
         }
         if (dy) d4[i] = g;
     }
-    // tail (n not a multiple of 4; n = B*T*2 is even, so at most 2 elements)
+    // tail (n not a multiple of 4: 1 to 3 elements; n = B*T*2 from the framed paths is even, but the ABI accepts any n > 0)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = (n4 << 2) + threadIdx.x;
         float d = y[i] - t[i];
@@ -149,7 +149,13 @@ __device__ __forceinline__ void clip_optim_block(int kind, int64_t P, float* __r
         float nrm = sqrtf(tot);
         if (norm_out) norm_out[0] = nrm;
         float coef = 1.0f;
-        if (max_norm > 0.f) coef = fminf(max_norm / (nrm + 1e-6f), 1.0f);
+        if (max_norm > 0.f) {
+            // clip_grad_norm_ (torch/nn/utils/clip_grad.py): `max_norm / (total_norm + 1e-6)` with a Python float on the left is
+            // Tensor.__rtruediv__ = reciprocal() * max_norm — two roundings —, then clamp(max=1.0).  The comparison (not fminf) keeps a
+            // NaN norm a NaN coefficient: a non-finite gradient poisons the whole step, as it does there.
+            coef = __fmul_rn(__fdiv_rn(1.0f, nrm + 1e-6f), max_norm);
+            if (coef > 1.0f) coef = 1.0f;
+        }
         coef_s = coef;
     }
     __syncthreads();

@@ -2628,8 +2628,9 @@ double oracle_clip_adamw_step(int64_t P, real* params, real* grad, real* exp_avg
     }
     real total_norm = (real)sqrt(total);
     if (max_norm > 0) {
-        real coef = (real)max_norm / (total_norm + (real)1e-6);
-        if (coef > (real)1) coef = (real)1;
+        /* `max_norm / (total_norm + 1e-6)` with a Python float on the left is reciprocal() * max_norm in torch: two roundings */
+        real coef = ((real)1 / (total_norm + (real)1e-6)) * (real)max_norm;
+        if (coef > (real)1) coef = (real)1;   /* (a comparison, not fmin: a NaN norm stays a NaN coefficient, like clamp(max=1.0)) */
         for (int64_t i = 0; i < P; ++i) grad[i] *= coef;
     }
     double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);

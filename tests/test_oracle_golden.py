@@ -97,6 +97,48 @@ def test_l1_loss(orc):
     assert np.allclose(dy, np.sign(y - t) / y.size)
 
 
+def _torch_clip_adamw(p, g, max_norm, lr):
+    import torch
+    ref = torch.nn.Parameter(torch.from_numpy(p.copy()))
+    ref.grad = torch.from_numpy(g.copy())
+    opt = torch.optim.AdamW([ref], lr=lr)
+    norm = float(torch.nn.utils.clip_grad_norm_([ref], max_norm))
+    opt.step()
+    st = opt.state[ref]
+    return norm, ref.detach().numpy(), ref.grad.numpy(), st["exp_avg"].numpy(), st["exp_avg_sq"].numpy()
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf])
+def test_clip_adamw_nonfinite_gradient_like_torch(orc, bad):
+    """clip_grad_norm_(200) + AdamW on a gradient with one NaN (NaN norm and coefficient: everything NaN) or one inf entry (norm inf,
+    coefficient 0: NaN there, a zero gradient elsewhere) — the oracle ends where torch ends"""
+    p0 = np.array([0.5, -0.25, 1.5, -1.0, 0.125], np.float32)
+    g0 = np.array([1, bad, 2, 3, 4], np.float32)
+    norm_t, p_t, g_t, m_t, v_t = _torch_clip_adamw(p0, g0, 200.0, 1e-3)
+    p, g, m, v = p0.copy(), g0.copy(), np.zeros(5, np.float32), np.zeros(5, np.float32)
+    norm = orc.clip_adamw(p, g, m, v, 1, 1e-3, 200.0)
+    assert np.isnan(g_t).sum() == (5 if np.isnan(bad) else 1)
+    assert (np.isnan(norm) and np.isnan(norm_t)) if np.isnan(bad) else norm == norm_t == np.inf
+    for got, want, tol in ((g, g_t, GRAD_TOL), (p, p_t, STEP_TOL), (m, m_t, 1e-3), (v, v_t, 1e-3)):
+        assert np.array_equal(np.isnan(got), np.isnan(want))
+        ok = ~np.isnan(want)
+        if ok.any():
+            assert rel_err(got[ok], want[ok]) < tol
+
+
+@pytest.mark.parametrize("max_norm", [5.0, 5.00001, 2.5])
+def test_clip_coefficient_bits_like_torch(orc, max_norm):
+    """a gradient whose norm is exactly 5: the clipped gradient is the bits clip_grad_norm_ leaves (total_norm + 1e-6 in fp32, its
+    reciprocal times max_norm, clamp at 1)"""
+    g0 = np.zeros(40, np.float32)
+    g0[[3, 29]] = (3.0, 4.0)
+    norm_t, _, g_t, _, _ = _torch_clip_adamw(np.zeros(40, np.float32), g0, max_norm, 1e-3)
+    g = g0.copy()
+    norm = orc.clip_adamw(np.zeros(40, np.float32), g, np.zeros(40, np.float32), np.zeros(40, np.float32), 1, 1e-3, max_norm)
+    assert norm == norm_t == 5.0
+    assert np.array_equal(g.view(np.uint32), g_t.view(np.uint32)), (g[[3, 29]], g_t[[3, 29]])
+
+
 def test_bad_args(orc):
     m = make_model("gru", 200)  # hidden too large for the oracle
     with pytest.raises(RuntimeError):
