@@ -281,7 +281,10 @@ int odpd_train_epoch(void* stream, const odpd_model_t* m, int loss_kind, const o
  * odpd_train_epoch.  All pointers of a run are device pointers; `runs` itself is a HOST array (copied into `scratch`, device memory of
  * odpd_sweep_scratch_bytes(K, steps of the epoch) bytes, which must stay untouched until the stream has drained).
  * Served: the float GRU family where odpd_sweep_train_supported / odpd_sweep_fwd_supported say so (the one-sequence-per-wave kernels of the
- * reference's own batch sizes); otherwise ODPD_EUNSUPPORTED and the caller loops over odpd_train_epoch. */
+ * reference's own batch sizes); otherwise ODPD_EUNSUPPORTED and the caller loops over odpd_train_epoch.
+ * The same table serves the train_dpd sweep (odpd_train_epoch_cascade_sweep, below): there `params` .. `exp_avg_sq` are the DPD's,
+ * `workspace` (nullable) holds the four sparsity counters of a delta DPD (double[4], 8-byte aligned — the convention odpd_train_fwd_bwd
+ * documents), and the frozen PAs' parameter pointers travel beside the table, as a second array of K pointers (`pa_params`). */
 typedef struct {
     float* params;            /* P floats */
     float* grad;              /* P + 4 */
@@ -290,7 +293,8 @@ typedef struct {
     float* partials;          /* (odpd_partial_rows(m, batch, T, 1), P + 4) */
     float* losses_out;        /* ceil(n_frames / batch): mean loss of every step */
     float* y;                 /* odpd_backbone_fwd_sweep: (B, T, 2) output of this run (else unused) */
-    float* workspace;         /* ODPD_SWEEP_S16: odpd_sweep_workspace_floats floats of BPTT checkpoint scratch of this run (else unused) */
+    float* workspace;         /* ODPD_SWEEP_S16: odpd_sweep_workspace_floats floats of BPTT checkpoint scratch of this run;
+                               * odpd_train_epoch_cascade_sweep: double[4] sparsity counters of a delta DPD, nullable (else unused) */
     const int64_t* order;     /* the run's epoch order: n_frames frame indices (fr->order is ignored) */
     double lr;                /* the run's learning rate of this epoch (the plateau schedulers of the runs are independent) */
 } odpd_sweep_run_t;
@@ -313,6 +317,25 @@ int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K, const odp
 /* the evaluation pass of K models of one shape on the same (B, T, 2) sequences x (net_eval, train_funcs.py:57-90): runs[k].y = model_k(x) */
 int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int B, int T, const float* x,
                             void* scratch);
+/* ---- lockstep train_dpd sweeps: K runs of ONE (DPD, PA) shape pair (the seeds of bash_scripts/train_all_dpd.sh, each DPD in front of the frozen
+ * PA of its own seed) on the one-launch cascade step.  That step gives every frame a workgroup of its own, which fills a CU's LDS: at
+ * batch 64 a solo run occupies 64 CUs.  Here one launch of K x odpd_cascade_rows workgroups carries the step of all runs (run k owns
+ * workgroups [k G, (k + 1) G) and sees exactly its solo launch; workgroups never wait for each other, so K x batch may exceed what the chip
+ * hosts at once), then one row reduction and one clip + AdamW launch: run k is bit-identical to odpd_train_epoch_cascade (comm = NULL, AdamW)
+ * called alone with its buffers, order and learning rate — parameters, optimiser states, per-step losses and counters.
+ * odpd_sweep_cascade_supported: 1 where odpd_cascade_rows(dpd, pa, B, T) > 0 and the DPD is float (bits_w == 0: the GRU family, deltagru,
+ * deltagru_tcnskip, lstm), else 0 (the quantised DPDs' optimiser step needs the skip mask: they keep the per-run epoch).
+ * odpd_sweep_cascade_scratch_bytes: device bytes behind `scratch` (run table, PA pointer table, per-step step sizes); ODPD_EINVAL for
+ * K <= 0 or n_steps < 0.
+ * odpd_train_epoch_cascade_sweep: one epoch.  `runs` and `pa_params` are HOST arrays of K entries (pa_params[k]: device pointer to run k's PA
+ * parameters; the entries may all be equal — the PA is only read); runs[k].order is the run's epoch order, fr->order is ignored;
+ * runs[k].partials: (odpd_cascade_rows of the full batch, P_dpd + 4).  ODPD_EINVAL: missing pointers, K / batch / first_step out of range;
+ * ODPD_EUNSUPPORTED: a pair or batch (the tail batch included) odpd_sweep_cascade_supported refuses, or samples other than ODPD_SAMPLES_F32. */
+int odpd_sweep_cascade_supported(const odpd_model_t* dpd, const odpd_model_t* pa, int B, int T);
+int64_t odpd_sweep_cascade_scratch_bytes(int K, int64_t n_steps);
+int odpd_train_epoch_cascade_sweep(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
+                                   const float* const* pa_params, int loss_kind, const odpd_frames_t* fr, int batch, int64_t first_step,
+                                   double beta1, double beta2, double eps, double weight_decay, double max_norm, void* scratch);
 
 /* clip_grad_norm_(max_norm) (0 = no clipping) + AdamW step over P parameters
  * (torch.optim.AdamW defaults project.py:283: betas .9/.999, eps 1e-8, weight_decay 0.01).

@@ -115,6 +115,11 @@ _EXPORTS = {
     "odpd_sweep_partial_rows": (C.c_int64, [C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int]),
     "odpd_sweep_workspace_floats": (C.c_int64, [C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int]),
     "odpd_backbone_fwd_sweep": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.c_int, C.POINTER(SweepRun), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "odpd_sweep_cascade_supported": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "odpd_sweep_cascade_scratch_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "odpd_train_epoch_cascade_sweep": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(SweepRun), C.POINTER(C.c_void_p),
+                                                 C.c_int, C.POINTER(Frames), C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                 C.c_double, C.c_void_p]),
     "odpd_clip_optim_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }

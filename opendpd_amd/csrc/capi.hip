@@ -879,6 +879,63 @@ extern "C" int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K
     }
     return 0;
 }
+// ---- lockstep train_dpd sweeps (the seeds of bash_scripts/train_all_dpd.sh): K runs of one float (DPD, PA) pair on the one-launch cascade step.
+// The step gives every frame a workgroup with a CU('s LDS) to itself, so at batch 64 one run leaves three quarters of the chip idle: here
+// the launch that fills the chip IS the bit-exact one (workgroups of different runs never interact).  scratch: run table | PA table | step sizes
+static size_t casc_sweep_pa_off(int K) { return ((size_t)K * sizeof(SweepRun) + 255) & ~(size_t)255; }
+static size_t casc_sweep_ss_off(int K) { return casc_sweep_pa_off(K) + (((size_t)K * sizeof(float*) + 255) & ~(size_t)255); }
+extern "C" int odpd_sweep_cascade_supported(const odpd_model_t* dpd, const odpd_model_t* pa, int B, int T) {
+    if (!dpd || !pa || !model_ok(dpd) || !model_ok(pa) || dpd->bits_w != 0) return 0;
+    if (family_of(dpd) == FAM_QAT) return 0;
+    return odpd_cascade_rows(dpd, pa, B, T) > 0 ? 1 : 0;
+}
+extern "C" int64_t odpd_sweep_cascade_scratch_bytes(int K, int64_t n_steps) {
+    if (K <= 0 || n_steps < 0) return ODPD_EINVAL;
+    return (int64_t)casc_sweep_ss_off(K) + (int64_t)K * n_steps * (int64_t)sizeof(float) + 256;
+}
+extern "C" int odpd_train_epoch_cascade_sweep(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
+                                              const float* const* pa_params, int loss_kind, const odpd_frames_t* fr, int batch, int64_t first_step,
+                                              double beta1, double beta2, double eps, double weight_decay, double max_norm, void* scratch) {
+    if (!dpd || !pa || !model_ok(dpd) || !model_ok(pa) || K <= 0 || !runs || !pa_params || !fr || !fr->x_stream || !fr->y_stream || fr->n_frames <= 0 ||
+        fr->frame_length <= 0 || fr->stride <= 0 || batch <= 0 || first_step <= 0 || !scratch)
+        return ODPD_EINVAL;
+    for (int k = 0; k < K; ++k)
+        if (!runs[k].params || !runs[k].grad || !runs[k].exp_avg || !runs[k].exp_avg_sq || !runs[k].partials || !runs[k].losses_out || !runs[k].order ||
+            !pa_params[k] || (reinterpret_cast<uintptr_t>(runs[k].workspace) & 7))      // (workspace: double counters)
+            return ODPD_EINVAL;
+    if (fr->sample_format != ODPD_SAMPLES_F32) return ODPD_EUNSUPPORTED;
+    const int T = fr->frame_length;
+    const int64_t n = fr->n_frames, n_steps = (n + batch - 1) / batch, tail = n - (n_steps - 1) * batch;
+    if (!odpd_sweep_cascade_supported(dpd, pa, (int)(n < batch ? n : batch), T) || !odpd_sweep_cascade_supported(dpd, pa, (int)tail, T))
+        return ODPD_EUNSUPPORTED;
+    const int64_t P = odpd_param_count(dpd);
+    hipStream_t st = (hipStream_t)stream;
+    SweepRun* dev = nullptr;
+    if (int rc = upload_sweep(st, K, runs, weight_decay, scratch, &dev)) return rc;
+    const float** pa_dev = reinterpret_cast<const float**>(reinterpret_cast<char*>(scratch) + casc_sweep_pa_off(K));
+    ODPD_CHECK_HIP(hipMemcpyAsync(pa_dev, pa_params, (size_t)K * sizeof(float*), hipMemcpyHostToDevice, st));      // (pageable source: staged before the call returns)
+    // per-step, per-run step sizes lr_k / (1 - beta1^step): double arithmetic rounded once, exactly launch_clip_adamw's
+    float* ss_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + casc_sweep_ss_off(K));
+    std::vector<float> ss((size_t)(K * n_steps));
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const double bc1 = 1.0 - pow(beta1, (double)(first_step + i));
+        for (int k = 0; k < K; ++k) ss[(size_t)(i * K + k)] = (float)(runs[k].lr / bc1);
+    }
+    ODPD_CHECK_HIP(hipMemcpyAsync(ss_dev, ss.data(), ss.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    CascArgs a{};
+    a.thx = dpd->thx; a.thh = dpd->thh; a.bits_w = dpd->bits_w; a.bits_a = dpd->bits_a;
+    a.x = fr->x_stream; a.target = fr->y_stream; a.frame_stride = fr->stride;
+    a.loss_kind = loss_kind; a.T = T; a.Hd = dpd->hidden; a.Hp = pa->hidden;
+    for (int64_t f0 = 0, i = 0; f0 < n; f0 += batch, ++i) {
+        const int B = (int)((n - f0) < batch ? (n - f0) : batch);
+        const float inv_count = (float)(1.0 / (double)((int64_t)B * T * 2));
+        a.B = B; a.inv_count = inv_count;
+        if (int rc = gru_cascade_sweep_train(st, dpd, pa, a, dev, pa_dev, K, (long long)f0)) return rc;
+        if (int rc = launch_reduce_sweep(st, dev, K, odpd_cascade_rows(dpd, pa, B, T), P)) return rc;
+        if (int rc = launch_clip_adamw_sweep(st, dev, K, P, ss_dev + i * K, first_step + i, i, beta1, beta2, eps, max_norm, inv_count)) return rc;
+    }
+    return 0;
+}
 extern "C" int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int B, int T, const float* x,
                                        void* scratch) {
     if (!model_ok(m) || K <= 0 || !runs || !x || B <= 0 || T <= 0 || !scratch) return ODPD_EINVAL;

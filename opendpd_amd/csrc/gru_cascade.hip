@@ -15,6 +15,8 @@
 // One partial-gradient row per workgroup: (P_dpd + kLossCols), column P_dpd = the loss partial sum.
 // delta_cascade_kernel / lstm_cascade_kernel: the same workgroup with a deltagru / TRes-DeltaGRU (odpd_deltaseq.h) or a plain LSTM
 // (odpd_lstm.h) of <= 16 units as the DPD.
+// *_cascade_sweep_kernel: the same three bodies for K lockstep runs in one launch (odpd_train_epoch_cascade_sweep) — a workgroup fills a CU's
+// LDS, so one run's batch of 64 leaves most of the chip idle, and K runs side by side are what fills it.
 #include "odpd_gpseq.h"
 #include "odpd_deltaseq.h"
 #include "odpd_lstm.h"
@@ -23,8 +25,9 @@ namespace odpd {
 
 // PA variants: PV = 0 hidden <= 16 | 1 hidden 17..24 (two blocks, the second held twice) | 2 hidden 25..32
 // NBD: unit blocks of the DPD (1: hidden <= 16, 2: hidden 17..32 — e.g. the qgru H20 / H30 of quant_qgru_dpd_regr.sh's float stage)
+// (wg / nwg: the workgroup's index and the workgroup count of ITS launch — blockIdx.x / gridDim.x alone, the run-local values in a sweep)
 template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
-__global__ __launch_bounds__(128) void gru_cascade_kernel(CascArgs a) {
+__device__ __forceinline__ void gru_cascade_body(const CascArgs& a, const int wg, const int nwg) {
     using D = GpSeq<NBD, FMD, DGD, true>;
     using P = GpSeq<PV == 0 ? 1 : 2, FMP, DGP, false, PV == 1>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -42,7 +45,7 @@ __global__ __launch_bounds__(128) void gru_cascade_kernel(CascArgs a) {
         D e;
         e.setup(smem, rd, a.dpd_params, a.Hd, T);
         __syncthreads();
-        for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        for (int b = wg; b < a.B; b += nwg) {
             const size_t base = a.frame_idx ? (size_t)a.frame_idx[b] * a.frame_stride : (size_t)b * T;
             const float2* xg = reinterpret_cast<const float2*>(a.x) + base;
             e.fwd_begin();
@@ -71,10 +74,10 @@ __global__ __launch_bounds__(128) void gru_cascade_kernel(CascArgs a) {
             }
         }
         __syncthreads();
-        e.write_partials(a.partials + (size_t)blockIdx.x * (Pd + kLossCols), xch[0]);
+        e.write_partials(a.partials + (size_t)wg * (Pd + kLossCols), xch[0]);
     } else {
         // ---------------- the PA (frozen) ----------------
-        casc_pa_wave<P>(a, smem, rp, pa_ubuf, dpd_dyb, xch);
+        casc_pa_wave<P>(a, wg, nwg, smem, rp, pa_ubuf, dpd_dyb, xch);
     }
 }
 
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(128) void gru_cascade_kernel(CascArgs a) {
 // DeltaSeq's forward chunk produces u (fc_out + TCN skip) and the PA's features; its backward chunk first runs the chunk's forward steps
 // again from the cell state kept at the chunk start (odpd_deltaseq.h), then back-propagates with the dL/du the PA wave left in LDS.
 template <bool TRES, int PV, int FMP, bool DGP>
-__global__ __launch_bounds__(128) void delta_cascade_kernel(CascArgs a) {
+__device__ __forceinline__ void delta_cascade_body(const CascArgs& a, const int wg, const int nwg) {
     using D = DeltaSeq<TRES>;
     using P = GpSeq<PV == 0 ? 1 : 2, FMP, DGP, false, PV == 1>;
     static_assert(D::C == kCascChunk, "one hand-off granularity");
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(128) void delta_cascade_kernel(CascArgs a) {
         D e;
         e.setup(smem, rd, a.dpd_params, a.Hd, T, a.thx, a.thh);
         __syncthreads();
-        for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        for (int b = wg; b < a.B; b += nwg) {
             const size_t base = a.frame_idx ? (size_t)a.frame_idx[b] * a.frame_stride : (size_t)b * T;
             const float2* xg = reinterpret_cast<const float2*>(a.x) + base;
             e.fwd_begin();
@@ -125,16 +128,16 @@ __global__ __launch_bounds__(128) void delta_cascade_kernel(CascArgs a) {
             e.bwd_end();
         }
         __syncthreads();
-        e.write_partials(a.partials + (size_t)blockIdx.x * (Pd + kLossCols), xch[0]);
-        e.add_stats(a.stats, a.B);
+        e.write_partials(a.partials + (size_t)wg * (Pd + kLossCols), xch[0]);
+        e.add_stats(a.stats, a.B, wg == 0);
     } else {
-        casc_pa_wave<P>(a, smem, rp, pa_ubuf, dpd_dyb, xch);
+        casc_pa_wave<P>(a, wg, nwg, smem, rp, pa_ubuf, dpd_dyb, xch);
     }
 }
 
 // ... and with a plain LSTM (backbones/lstm.py) as the DPD (LstmSeq, odpd_lstm.h; hidden <= 16)
 template <int PV, int FMP, bool DGP>
-__global__ __launch_bounds__(128) void lstm_cascade_kernel(CascArgs a) {
+__device__ __forceinline__ void lstm_cascade_body(const CascArgs& a, const int wg, const int nwg) {
     using D = LstmSeq;
     using P = GpSeq<PV == 0 ? 1 : 2, FMP, DGP, false, PV == 1>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(128) void lstm_cascade_kernel(CascArgs a) {
         D e;
         e.setup(smem, rd, a.dpd_params, a.Hd, T);
         __syncthreads();
-        for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        for (int b = wg; b < a.B; b += nwg) {
             const size_t base = a.frame_idx ? (size_t)a.frame_idx[b] * a.frame_stride : (size_t)b * T;
             const float2* xg = reinterpret_cast<const float2*>(a.x) + base;
             e.fwd_begin();
@@ -175,10 +178,52 @@ __global__ __launch_bounds__(128) void lstm_cascade_kernel(CascArgs a) {
             }
         }
         __syncthreads();
-        e.write_partials(a.partials + (size_t)blockIdx.x * (Pd + kLossCols), xch[0]);
+        e.write_partials(a.partials + (size_t)wg * (Pd + kLossCols), xch[0]);
     } else {
-        casc_pa_wave<P>(a, smem, rp, pa_ubuf, dpd_dyb, xch);
+        casc_pa_wave<P>(a, wg, nwg, smem, rp, pa_ubuf, dpd_dyb, xch);
     }
+}
+
+template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void gru_cascade_kernel(CascArgs a) {
+    gru_cascade_body<NBD, FMD, DGD, PV, FMP, DGP>(a, blockIdx.x, gridDim.x);
+}
+template <bool TRES, int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void delta_cascade_kernel(CascArgs a) {
+    delta_cascade_body<TRES, PV, FMP, DGP>(a, blockIdx.x, gridDim.x);
+}
+template <int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void lstm_cascade_kernel(CascArgs a) {
+    lstm_cascade_body<PV, FMP, DGP>(a, blockIdx.x, gridDim.x);
+}
+// K independent train_dpd runs of one pair of model shapes in lockstep (odpd_train_epoch_cascade_sweep: the seeds of
+// bash_scripts/train_all_dpd.sh): run k owns workgroups [k G, (k + 1) G) and sees exactly the launch it would have had alone — its DPD
+// parameters, its frozen PA (pa_tab[k]: the PAs of a seed sweep differ), its epoch order from the step's first frame on, its partial rows
+// and (delta DPDs) its sparsity counters.  Workgroups never wait for one another (workgroup barriers and per-workgroup rows only), so the
+// launch may hold more workgroups than the chip hosts at once.
+__device__ __forceinline__ void casc_sweep_args(CascArgs& a, const SweepRun* __restrict__ runs, const float* const* __restrict__ pa_tab, int k,
+                                                long long first) {
+    const SweepRun r = runs[k];
+    a.dpd_params = r.params; a.pa_params = pa_tab[k]; a.partials = r.partials; a.frame_idx = r.order + first;
+    a.stats = reinterpret_cast<double*>(r.workspace);
+}
+template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void gru_cascade_sweep_kernel(CascArgs a, const SweepRun* __restrict__ runs,
+                                                                const float* const* __restrict__ pa_tab, int G, long long first) {
+    casc_sweep_args(a, runs, pa_tab, blockIdx.x / G, first);
+    gru_cascade_body<NBD, FMD, DGD, PV, FMP, DGP>(a, blockIdx.x % G, G);
+}
+template <bool TRES, int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void delta_cascade_sweep_kernel(CascArgs a, const SweepRun* __restrict__ runs,
+                                                                  const float* const* __restrict__ pa_tab, int G, long long first) {
+    casc_sweep_args(a, runs, pa_tab, blockIdx.x / G, first);
+    delta_cascade_body<TRES, PV, FMP, DGP>(a, blockIdx.x % G, G);
+}
+template <int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void lstm_cascade_sweep_kernel(CascArgs a, const SweepRun* __restrict__ runs,
+                                                                 const float* const* __restrict__ pa_tab, int G, long long first) {
+    casc_sweep_args(a, runs, pa_tab, blockIdx.x / G, first);
+    lstm_cascade_body<PV, FMP, DGP>(a, blockIdx.x % G, G);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -278,6 +323,20 @@ int casc_launch(hipStream_t st, const CascArgs& a, const CascCfg& c) {
     else if constexpr (FMD == kDpdLstm) return launch(lstm_cascade_kernel<PV, FMP, DGP>);
     else return launch(gru_cascade_kernel<NBD, FMD, DGD, PV, FMP, DGP>);
 }
+// the sweep form of casc_launch: K x G workgroups, G = the solo grid of this (B, T)
+template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
+int casc_sweep_launch(hipStream_t st, const CascArgs& a, const CascCfg& c, const SweepRun* runs, const float* const* pa_tab, int K, long long first) {
+    const size_t lds = casc_lds<NBD, FMD, DGD, PV, FMP, DGP>(a.T, c.Pd, c.Pp);
+    const int G = casc_grid(c, a.B, a.T);
+    auto launch = [&](auto k) {
+        if (int e = allow_big_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3((unsigned)G * (unsigned)K), dim3(128), lds, st, a, runs, pa_tab, G, first);
+        return (int)hipGetLastError();
+    };
+    if constexpr (FMD == kDpdDelta || FMD == kDpdTres) return launch(delta_cascade_sweep_kernel<FMD == kDpdTres, PV, FMP, DGP>);
+    else if constexpr (FMD == kDpdLstm) return launch(lstm_cascade_sweep_kernel<PV, FMP, DGP>);
+    else return launch(gru_cascade_sweep_kernel<NBD, FMD, DGD, PV, FMP, DGP>);
+}
 }  // namespace
 
 // rows of partials (> 0) if the pair of models and the batch shape are served by the one-launch cascade step, else ODPD_EUNSUPPORTED
@@ -297,5 +356,17 @@ int gru_cascade_train(hipStream_t st, const odpd_model_t* dpd, const odpd_model_
     return ODPD_EUNSUPPORTED;
 }
 
+// K runs of one (DPD, PA) shape pair in one launch (float DPDs only: the quantised ones keep the per-run epoch); a.dpd_params / pa_params /
+// partials / frame_idx / stats come from the two device tables
+int gru_cascade_sweep_train(hipStream_t st, const odpd_model_t* dpd, const odpd_model_t* pa, const CascArgs& a, const SweepRun* runs,
+                            const float* const* pa_tab, int K, long long first) {
+    CascCfg c;
+    if (!casc_cfg(dpd, pa, c) || c.fmd == kDpdQat || casc_grid(c, a.B, a.T) <= 0 || K <= 0 || !runs || !pa_tab) return ODPD_EUNSUPPORTED;
+    if ((long long)casc_grid(c, a.B, a.T) * K > 0x7fffffffLL) return ODPD_EUNSUPPORTED;
+#define ODPD_CASC_SWEEP(NBD_, FMD_, DGD_, PV_, FMP_, DGP_) casc_sweep_launch<NBD_, FMD_, DGD_, PV_, FMP_, DGP_>(st, a, c, runs, pa_tab, K, first)
+    ODPD_CASC_ALL(ODPD_CASC_SWEEP)
+#undef ODPD_CASC_SWEEP
+    return ODPD_EUNSUPPORTED;
+}
 
 }  // namespace odpd

@@ -297,7 +297,8 @@ struct DeltaSeq {
             }
     }
     // sparsity counters of the forward passes (deltagru.py:214-226): dx zeros = the six feature lanes of row 0, dh zeros = the hidden units of row 0
-    __device__ __forceinline__ void add_stats(double* stats, int B) {
+    // (first: the workgroup that adds the element counts of its launch — one per run of a sweep launch)
+    __device__ __forceinline__ void add_stats(double* stats, int B, bool first) {
         if (stats == nullptr) return;
         float tx = (role == 0 && col < 6) ? zx : 0.0f, th = role == 0 ? zh : 0.0f;
         for (int o = 32; o > 0; o >>= 1) { tx += __shfl_down(tx, o); th += __shfl_down(th, o); }
@@ -305,7 +306,7 @@ struct DeltaSeq {
             atomicAdd(&stats[0], (double)tx);
             atomicAdd(&stats[2], (double)th);
         }
-        if (blockIdx.x == 0 && lane == 0) {
+        if (first && lane == 0) {
             atomicAdd(&stats[1], 6.0 * (double)B * (double)T);
             atomicAdd(&stats[3], (double)H * (double)B * (double)T);
         }

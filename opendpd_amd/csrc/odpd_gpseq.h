@@ -404,8 +404,10 @@ struct GpSeq {
 
 // The frozen PA's wave of a cascade workgroup.  One workgroup barrier per hand-off (the DPD wave executes the same number): forward
 // chunk k - 1 while the DPD wave produces chunk k; loss; backward chunk c + dL/du of the chunk into the DPD wave's dL/dy buffer.
+// wg / nwg: the workgroup's index and the workgroup count of its launch (run-local in a sweep launch: gru_cascade.hip)
 template <typename P>
-__device__ __forceinline__ void casc_pa_wave(const CascArgs& a, float* smem, float* rp, float2* pa_ubuf, float2* dpd_dyb, float* xch) {
+__device__ __forceinline__ void casc_pa_wave(const CascArgs& a, const int wg, const int nwg, float* smem, float* rp, float2* pa_ubuf, float2* dpd_dyb,
+                                             float* xch) {
     const int lane = threadIdx.x & 63, T = a.T, NC = (T + kCascChunk - 1) / kCascChunk;
     P e;
     e.setup(smem, rp, a.pa_params, a.Hp, T);
@@ -413,7 +415,7 @@ __device__ __forceinline__ void casc_pa_wave(const CascArgs& a, float* smem, flo
     const S16Loss lossc = s16_loss_setup(a.loss_kind == ODPD_LOSS_L2, a.inv_count, true);
     float2* pa_dyb = reinterpret_cast<float2*>(e.dyb);
     float loss_acc = 0.0f;
-    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    for (int b = wg; b < a.B; b += nwg) {
         const size_t base = a.frame_idx ? (size_t)a.frame_idx[b] * a.frame_stride : (size_t)b * T;
         const float2* tg = reinterpret_cast<const float2*>(a.target) + base;
         e.fwd_begin();
@@ -450,6 +452,10 @@ __device__ __forceinline__ void casc_pa_wave(const CascArgs& a, float* smem, flo
     for (int o = 32; o > 0; o >>= 1) lp += __shfl_down(lp, o);
     if (lane == 0) xch[0] = lp;
     __syncthreads();
+}
+template <typename P>
+__device__ __forceinline__ void casc_pa_wave(const CascArgs& a, float* smem, float* rp, float2* pa_ubuf, float2* dpd_dyb, float* xch) {
+    casc_pa_wave<P>(a, blockIdx.x, gridDim.x, smem, rp, pa_ubuf, dpd_dyb, xch);
 }
 
 }  // namespace odpd

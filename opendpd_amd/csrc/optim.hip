@@ -143,7 +143,13 @@ __device__ __forceinline__ void clip_optim_block(int kind, int64_t P, float* __r
     if (loss_out && threadIdx.x == 0) loss_out[0] = g[P] * inv_count;   // column P of the reduced row = loss partial sum
     float acc = 0.f;
     // skip[i] != 0: a parameter whose .grad is None in the reference — outside the norm, untouched by the update
-    for (int64_t i = threadIdx.x; i < P; i += blockDim.x) acc += (skip && skip[i]) ? 0.f : g[i] * g[i];
+    // (the square as a product of its own, never contracted into the sum — contract(off): with a run-time `skip` the product passes through a select and
+    // cannot fuse, while clip_adamw_sweep_kernel's constant NULL would let it — above 1024 parameters a thread adds more than one square, and
+    // the two kernels' norms, hence an active clip coefficient, would differ in the last bit)
+    for (int64_t i = threadIdx.x; i < P; i += blockDim.x) {
+#pragma clang fp contract(off)
+        acc += (skip && skip[i]) ? 0.f : g[i] * g[i];
+    }
     float tot = block_sum(acc, sh);
     if (threadIdx.x == 0) {
         float nrm = sqrtf(tot);

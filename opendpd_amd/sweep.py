@@ -6,7 +6,12 @@ and one clip + AdamW launch (csrc: odpd_train_epoch_sweep), and the evaluation p
 (odpd_backbone_fwd_sweep).  Each run is BIT-IDENTICAL to its solo run — same seeded initialisation, same epoch orders (each run keeps its
 own copy of the global RNG state, swapped in around everything that draws from it), same kernels, same reduction order — and writes the same
 `save/` and `log/` files (tests/test_sweep_gpu.py compares them with solo runs).  Runs whose shape the sweep kernels do not serve (other
-families, batches beyond the one-sequence-per-wave regime) advance through the ordinary per-run epoch, in the same lockstep loop."""
+families, batches beyond the one-sequence-per-wave regime) advance through the ordinary per-run epoch, in the same lockstep loop.
+
+`train_dpd_sweep` does the same for `train_dpd` (bash_scripts/train_all_dpd.sh: seeds x DPD backbones, each DPD in front of the frozen PA of
+its own seed).  Its step is the one-launch cascade step, which gives every frame a workgroup with a CU's LDS to itself: at batch 64 a solo
+run occupies 64 CUs, and the launch that carries K runs (csrc: odpd_train_epoch_cascade_sweep) fills the rest of the chip while every run
+stays its solo run bit for bit — for train_dpd the chip-filling mode and the exact mode are the same mode."""
 import ctypes as C
 import random
 import time
@@ -15,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .models import CoreModel
+from .models import CascadedModel, CoreModel
 from .project import Project, count_net_params
 from .train_funcs import FusedAdamW, _loss_kind, _sample_format
 
@@ -165,25 +170,17 @@ class _Group:
         p0 = self.runs[0].proj
         batches, lists = None, None
         if p0.eval_val and p0.eval_test and self.desc is not None and len(self.runs) > 1:
-            # (one pass over a torch DataLoader draws its base seed from the global RNG even without shuffling: every run makes the two passes
-            # its solo epoch makes, under its own RNG copy — the NEXT epoch's shuffle depends on it)
-            lists = []
-            for r in self.runs:
-                with r.rng:
-                    lists.append((list(r.loaders[1]), list(r.loaders[2])))
+            lists = _loader_passes(self.runs)
             ba, bb_ = lists[0]
-            if len(ba) == len(bb_) and all(fa.shape[1:] == fb.shape[1:] for (fa, _), (fb, _) in zip(ba, bb_)):
+            if _pairable(ba, bb_):
                 xs = [torch.cat((fa, fb), dim=0).to(self.dev).float().contiguous() for (fa, _), (fb, _) in zip(ba, bb_)]
                 if all(lib.odpd_sweep_fwd_supported(C.byref(self.desc), x.shape[0], x.shape[1]) for x in xs):
                     batches = (ba, bb_, xs)
         if batches is None:
-            for r, pre in zip(self.runs, lists if lists is not None else [None] * len(self.runs)):
-                p = r.proj
-                if pre is not None:      # the passes over the loaders were made above (their RNG draws with them)
-                    _, (pv, tv), (pt, tt) = net_eval_pair(p.log_val, p.log_test, r.net, pre[0], pre[1], r.criterion, p.device)
-                    p.log_val = calculate_metrics(p.args, p.log_val, pv, tv)
-                    p.log_test = calculate_metrics(p.args, p.log_test, pt, tt)
-                    continue
+            if lists is not None:      # the passes over the loaders were made above
+                _eval_pairs_per_run(self.runs, lists)
+                return
+            for r in self.runs:
                 with r.rng:
                     self._eval_solo(r, calculate_metrics, net_eval, net_eval_pair)
             return
@@ -222,26 +219,99 @@ class _Group:
                 for k, r in enumerate(self.runs):
                     for (losses, pred, truth), o, t in ((outs[0][k], ys[k][:fa.shape[0]], ta), (outs[1][k], ys[k][fa.shape[0]:], tb)):
                         losses.append(r.criterion(o, t)); pred.append(o); truth.append(t)
-        # host side of the K x 2 evaluations at sweep level: one device-to-host copy per split for all runs' predictions, one for every loss,
-        # the split's ground truth once (the runs of a group share their dataset), metrics over the (K, segments, nperseg) stack with one
-        # FFT / Welch call per split (metrics.calculate_metrics_many: each run's numbers are those of its own calculate_metrics call)
-        from .metrics import calculate_metrics_many
-        for split, name in ((0, "log_val"), (1, "log_test")):
-            per_run = outs[split]
-            if not per_run[0][0]:
-                for r in self.runs:
-                    getattr(r.proj, name)["loss"] = float("nan")
-                continue
-            loss_m = torch.stack([torch.stack([l.float() for l in per_run[k][0]]) for k in range(K)]).cpu().numpy()      # (K, batches)
-            preds = torch.stack([torch.cat(per_run[k][1], dim=0) for k in range(K)]).cpu().numpy()                       # (K, segments, nperseg, 2)
-            truth = torch.cat(per_run[0][2], dim=0).cpu().numpy()
-            stats = []
-            for k, r in enumerate(self.runs):
-                getattr(r.proj, name)["loss"] = float(np.mean(loss_m[k]))
-                stats.append(getattr(r.proj, name))
-            done = calculate_metrics_many(self.runs[0].proj.args, stats, [preds[k] for k in range(K)], [truth] * K)
-            for r, st in zip(self.runs, done):
-                setattr(r.proj, name, st)
+        _metrics_many(self.runs, outs)
+
+
+def _metrics_many(runs, outs):
+    """host side of the K x 2 evaluations at sweep level: one device-to-host copy per split for all runs' predictions, one for every loss,
+    the split's ground truth once (the runs of a group share their dataset), metrics over the (K, segments, nperseg) stack with one
+    FFT / Welch call per split (metrics.calculate_metrics_many: each run's numbers are those of its own calculate_metrics call).
+    outs[split][k] = (losses, predictions, ground truth) of run k, one entry per batch"""
+    from .metrics import calculate_metrics_many
+    K = len(runs)
+    for split, name in ((0, "log_val"), (1, "log_test")):
+        per_run = outs[split]
+        if not per_run[0][0]:
+            for r in runs:
+                getattr(r.proj, name)["loss"] = float("nan")
+            continue
+        loss_m = torch.stack([torch.stack([l.float() for l in per_run[k][0]]) for k in range(K)]).cpu().numpy()      # (K, batches)
+        preds = torch.stack([torch.cat(per_run[k][1], dim=0) for k in range(K)]).cpu().numpy()                       # (K, segments, nperseg, 2)
+        truth = torch.cat(per_run[0][2], dim=0).cpu().numpy()
+        stats = []
+        for k, r in enumerate(runs):
+            getattr(r.proj, name)["loss"] = float(np.mean(loss_m[k]))
+            stats.append(getattr(r.proj, name))
+        done = calculate_metrics_many(runs[0].proj.args, stats, [preds[k] for k in range(K)], [truth] * K)
+        for r, st in zip(runs, done):
+            setattr(r.proj, name, st)
+
+
+def _flush_loggers(runs, failed):
+    """the deferred checkpoints of every run, at the end of the sweep loop.  `failed`: the exception that ended the loop (None: it finished) —
+    a flush that fails then must not mask it and is reported as a warning; after a finished loop a failing flush is the sweep's error (every
+    other run is still flushed first)"""
+    import warnings
+    first = None
+    for r in runs:
+        try:
+            r.proj.logger.flush()
+        except Exception as e:
+            if failed is not None:
+                warnings.warn(f"checkpoint of {r.proj.path_save_file_best} not written ({type(e).__name__}: {e}) while the sweep ended with "
+                              f"{type(failed).__name__}", RuntimeWarning, stacklevel=2)
+            elif first is None:
+                first = e
+    if first is not None:
+        raise first
+
+
+def _loader_passes(runs):
+    """[(validation batches, test batches)] per run.  One pass over a torch DataLoader draws its base seed from the global RNG even without
+    shuffling: every run makes the two passes its solo epoch makes, under its own RNG copy — the NEXT epoch's shuffle depends on it"""
+    lists = []
+    for r in runs:
+        with r.rng:
+            lists.append((list(r.loaders[1]), list(r.loaders[2])))
+    return lists
+
+
+def _pairable(ba, bb_):
+    return len(ba) == len(bb_) and all(fa.shape[1:] == fb.shape[1:] for (fa, _), (fb, _) in zip(ba, bb_))
+
+
+def _eval_pairs_per_run(runs, lists):
+    """train_funcs.net_eval_pair per run on batches already drawn (their RNG draws were made with the passes)"""
+    from .metrics import calculate_metrics
+    from .train_funcs import net_eval_pair
+    for r, pre in zip(runs, lists):
+        p = r.proj
+        _, (pv, tv), (pt, tt) = net_eval_pair(p.log_val, p.log_test, r.net, pre[0], pre[1], r.criterion, p.device)
+        p.log_val = calculate_metrics(p.args, p.log_val, pv, tv)
+        p.log_test = calculate_metrics(p.args, p.log_test, pt, tt)
+
+
+def _sweep_loop(runs, groups, n_epochs, metric):
+    """the lockstep loop of both sweeps; sweep-level bookkeeping: history rows are appended (project.CsvLogger), an
+    improved model is remembered on the device and its checkpoint written once, when the sweep ends or is interrupted (`flush`), instead of
+    one torch.save per run and improving epoch"""
+    for r in runs:
+        r.proj.logger.defer_checkpoints = True
+    start = time.time()
+    failed = None
+    try:
+        for epoch in range(n_epochs):
+            for g in groups:
+                g.train_epoch()
+            for g in groups:
+                g.eval_epoch()
+            for r in runs:      # (log row, best-model bookkeeping, plateau scheduler: nothing here draws from an RNG — no state swap)
+                r.proj.finish_epoch(r.net, r.opt, r.sched, epoch, start, metric)
+    except BaseException as e:
+        failed = e
+        raise
+    finally:
+        _flush_loggers(runs, failed)
 
 
 def train_pa_sweep(dataset_name=None, seeds=(0,), hidden_sizes=None, PA_backbone="gru", PA_hidden_size=23, n_epochs=100, batch_size=256,
@@ -277,23 +347,209 @@ def train_pa_sweep(dataset_name=None, seeds=(0,), hidden_sizes=None, PA_backbone
     for r in runs:
         groups.setdefault(_group_key(r), []).append(r)
     groups = [_Group(v, exact=exact) for v in groups.values()]
-    # sweep-level bookkeeping: history rows are appended (project.CsvLogger), an improved model is remembered on the device
-    # and its checkpoint written once, when the sweep ends or is interrupted (`flush`), instead of one torch.save per run and improving epoch
-    for r in runs:
-        r.proj.logger.defer_checkpoints = True
-    start = time.time()
-    try:
-        for epoch in range(n_epochs):
-            for g in groups:
-                g.train_epoch()
-            for g in groups:
-                g.eval_epoch()
-            for r in runs:      # (log row, best-model bookkeeping, plateau scheduler: nothing here draws from an RNG — no state swap)
-                r.proj.finish_epoch(r.net, r.opt, r.sched, epoch, start, "NMSE")
-    finally:
-        for r in runs:
-            r.proj.logger.flush()
+    _sweep_loop(runs, groups, n_epochs, "NMSE")
     return [{"status": "completed", "model_path": r.proj.path_save_file_best, "log_path": r.proj.path_log_file_best, "seed": r.proj.seed,
              "PA_hidden_size": r.proj.PA_hidden_size, "lockstep": bool(g_.train_sweep),
              "mode": ("s16" if g_.flags else "exact") if g_.train_sweep else "per-run"}
             for g_ in groups for r in g_.runs]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# train_dpd
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _setup_dpd(run):
+    """steps/train_dpd.py:14-90 up to the training loop (project.run_train_dpd), under the run's own RNG: the frozen PA is the one `train_pa`
+    saved for this run's seed"""
+    import os
+
+    from .quant import get_quant_model
+    p = run.proj
+    p.set_device()
+    run.loaders, input_size = p.build_dataloaders()
+    pa = CoreModel(input_size, p.PA_hidden_size, p.PA_num_layers, p.PA_backbone, window_size=p.window_size, num_dvr_units=p.num_dvr_units)
+    pa_id = p.gen_pa_model_id(count_net_params(pa))
+    pa.load_state_dict(torch.load(os.path.join("save", p.dataset_label, "train_pa", pa_id + ".pt"), map_location="cpu"))
+    dpd = CoreModel(input_size, p.DPD_hidden_size, p.DPD_num_layers, p.DPD_backbone, window_size=p.window_size, num_dvr_units=p.num_dvr_units,
+                    thx=p.thx, thh=p.thh)
+    dpd = get_quant_model(p, dpd)
+    p.build_logger(p.gen_dpd_model_id(count_net_params(dpd)))
+    net = CascadedModel(dpd_model=dpd, pa_model=pa)
+    net.freeze_pa_model()
+    run.net = net.to(p.device)
+    run.opt, run.sched = p.build_optimizer(run.net)
+    run.criterion = p.build_criterion()
+
+
+def _dpd_group_key(run):
+    p = run.proj
+    return (p.DPD_backbone, p.DPD_hidden_size, p.DPD_num_layers, p.PA_backbone, p.PA_hidden_size, p.PA_num_layers, p.batch_size, p.frame_length,
+            p.frame_stride, p.loss_type, p.opt_type, p.dataset_label, p.frame_storage, p.grad_clip_val, p.thx, p.thh, p.quant, p.n_bits_w,
+            p.n_bits_a, p.pretrained_model, p.quant_dir_label, p.q_pretrain)
+
+
+class _DpdGroup:
+    """train_dpd runs of one (DPD, PA) shape pair on one dataset: what one cascade sweep launch can carry"""
+
+    def __init__(self, runs):
+        self.runs = runs
+        r0 = runs[0]
+        train = r0.loaders[0]
+        self.T, self.n, self.B = train.frame_length, train.n, min(train.batch_size, train.n)
+        self.n_steps = (self.n + self.B - 1) // self.B
+        self.last = self.n - (self.n_steps - 1) * self.B
+        self.dev = train.x.device if hasattr(train, "x") else None
+        self.kind = _loss_kind(r0.criterion)
+        fused = all(isinstance(r.opt, FusedAdamW) and r.opt.kind == "adamw" and r.opt.pa is not None and r.opt.world_size() == 1
+                    and r.opt.native_comm() is None and r.opt.pa.native and r.opt.backbone.native
+                    and getattr(r.opt.backbone, "frozen_mask", None) is None for r in runs)
+        self.eligible = bool(fused and self.kind is not None and len(runs) > 1 and hasattr(train, "epoch_order") and train.x.is_cuda
+                             and train.x.dtype == torch.float32)
+        self.dpd_desc = getattr(getattr(r0.net.dpd_model, "backbone", None), "desc", None)
+        self.pa_desc = getattr(r0.net.pa_model.backbone, "desc", None)
+        self.train_sweep = False
+        self.scratch = None
+        self._tuning_gen = None
+        self._size_buffers()
+
+    def _size_buffers(self):
+        """whether the cascade sweep launch serves the group, and the partial rows / scratch of every run, under the CURRENT kernel-selection
+        knobs (odpd_set_tuning: cascade_one_launch, gp_max_batch ..); re-done by train_epoch when odpd_tuning_generation has moved"""
+        lib = _lib.load()
+        self._tuning_gen = int(lib.odpd_tuning_generation())
+        self.train_sweep = bool(self.eligible and self.dpd_desc is not None and self.pa_desc is not None and all(
+            lib.odpd_sweep_cascade_supported(C.byref(self.dpd_desc), C.byref(self.pa_desc), b, self.T) == 1 for b in {self.B, self.last}))
+        if self.train_sweep:
+            rows = max(int(lib.odpd_cascade_rows(C.byref(self.dpd_desc), C.byref(self.pa_desc), b, self.T)) for b in {self.B, self.last})
+            for r in self.runs:
+                r.opt._ensure(self.dev)
+                r.partials = torch.empty(rows, r.opt.backbone.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=self.dev)
+            self.scratch = torch.empty(int(lib.odpd_sweep_cascade_scratch_bytes(len(self.runs), self.n_steps)), dtype=torch.uint8, device=self.dev)
+
+    # ---- one training epoch of every run of the group ----
+    def train_epoch(self):
+        from .train_funcs import net_train
+        lib = _lib.load()
+        if int(lib.odpd_tuning_generation()) != self._tuning_gen:
+            self._size_buffers()
+        if not self.train_sweep:
+            for r in self.runs:
+                with r.rng:
+                    r.net = net_train(r.proj.log_train, r.net, r.loaders[0], r.opt, r.criterion, r.proj.grad_clip_val, r.proj.device)
+            return
+        K = len(self.runs)
+        table = (_lib.SweepRun * K)()
+        pa_tab = (C.c_void_p * K)()
+        train0 = self.runs[0].loaders[0]
+        keep = []
+        for k, r in enumerate(self.runs):
+            r.net.train()
+            with r.rng:
+                r.order = r.loaders[0].epoch_order()           # the run's own shuffle, drawn from the run's own RNG stream
+            r.losses = torch.empty(self.n_steps, dtype=torch.float32, device=self.dev)
+            g = r.opt.param_groups[0]
+            dpd, pa = r.opt.backbone, r.opt.pa
+            flat, pa_flat = dpd.flat_params(full_check=True), pa.flat_params(full_check=True)
+            stats = dpd._stats_buffer(self.dev)               # delta DPDs: the four sparsity counters (None while switched off)
+            keep.append((pa_flat, stats))
+            table[k] = _lib.SweepRun(flat.data_ptr(), r.opt.grad.data_ptr(), r.opt.exp_avg.data_ptr(), r.opt.exp_avg_sq.data_ptr(),
+                                     r.partials.data_ptr(), r.losses.data_ptr(), None, stats.data_ptr() if stats is not None else None,
+                                     r.order.data_ptr(), float(g["lr"]))
+            pa_tab[k] = pa_flat.data_ptr()
+        g0 = self.runs[0].opt.param_groups[0]
+        assert all(r.opt.step_count == self.runs[0].opt.step_count for r in self.runs)
+        fr = _lib.Frames(train0.x.data_ptr(), train0.y.data_ptr(), None, self.n, self.T, train0.stride, _sample_format(train0.x, train0.y), 0)
+        rc = lib.odpd_train_epoch_cascade_sweep(_lib.stream_ptr(), C.byref(self.dpd_desc), C.byref(self.pa_desc), K, table, pa_tab,
+                                                _lib.LOSS_IDS[self.kind], C.byref(fr), self.B, self.runs[0].opt.step_count + 1,
+                                                float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), float(g0["weight_decay"]),
+                                                float(self.runs[0].proj.grad_clip_val or 0.0), C.c_void_p(self.scratch.data_ptr()))
+        _lib.check(rc, "odpd_train_epoch_cascade_sweep")
+        # the K epoch means: each the reduction its solo run makes (train_funcs.net_train), queued back to back and read with ONE synchronisation
+        means = torch.stack([r.losses.double().mean() for r in self.runs]).cpu() if self.n_steps else None
+        for k, r in enumerate(self.runs):
+            r.opt.step_count += self.n_steps
+            r.opt.last_epoch_losses = r.losses
+            r.opt._keepalive = r.order
+            r.proj.log_train["loss"] = float(means[k].item()) if means is not None else float("nan")
+
+    # ---- validation + test of every run of the group: what train_funcs.net_eval_pair computes for each run ----
+    def eval_epoch(self):
+        from .metrics import calculate_metrics
+        from .train_funcs import net_eval, net_eval_pair
+        lib = _lib.load()
+        p0, K = self.runs[0].proj, len(self.runs)
+        if not (p0.eval_val and p0.eval_test) or K == 1:
+            for r in self.runs:
+                with r.rng:
+                    _Group._eval_solo(r, calculate_metrics, net_eval, net_eval_pair)
+            return
+        lists = _loader_passes(self.runs)
+        ba, bb_ = lists[0]
+        if not _pairable(ba, bb_):      # the splits do not pair up: net_eval_pair's own fallback, per run
+            _eval_pairs_per_run(self.runs, lists)
+            return
+        dpd_float = self.dpd_desc is not None and int(self.dpd_desc.bits_w) == 0 and all(
+            getattr(r.net.dpd_model.backbone, "native", False) for r in self.runs)
+        scratch = torch.empty(int(lib.odpd_sweep_scratch_bytes(K, 0)), dtype=torch.uint8, device=self.dev)
+        outs = [([], [], []) for _ in range(K)], [([], [], []) for _ in range(K)]
+        with torch.no_grad():
+            for r in self.runs:
+                r.net.eval()
+            for (fa, ta), (fb, tb) in zip(ba, bb_):
+                fa, ta, fb, tb = fa.to(self.dev), ta.to(self.dev), fb.to(self.dev), tb.to(self.dev)
+                x = torch.cat((fa, fb), dim=0)
+                # the DPD stage of the K runs: one launch where the evaluation sweep serves the shape (the kernel a solo forward takes) ...
+                if (dpd_float and x.dtype == torch.float32
+                        and lib.odpd_sweep_fwd_supported(C.byref(self.dpd_desc), x.shape[0], x.shape[1]) == 1):
+                    x = x.contiguous()
+                    us = [torch.empty(x.shape[0], x.shape[1], 2, dtype=torch.float32, device=self.dev) for _ in range(K)]
+                    table = (_lib.SweepRun * K)()
+                    for k, r in enumerate(self.runs):
+                        table[k] = _lib.SweepRun(r.net.dpd_model.backbone.flat_params().data_ptr(), None, None, None, None, None, us[k].data_ptr(),
+                                                 None, None, 0.0)
+                    _lib.check(lib.odpd_backbone_fwd_sweep(_lib.stream_ptr(), C.byref(self.dpd_desc), K, table, x.shape[0], x.shape[1], _lib.ptr(x),
+                                                           C.c_void_p(scratch.data_ptr())), "odpd_backbone_fwd_sweep")
+                else:      # ... else per run (delta DPDs count their sparsity statistics in this forward; quantised DPDs)
+                    us = [r.net.dpd_model(x) for r in self.runs]
+                # the PA stage per run, with the call the solo run makes: the PAs differ, and stacking would change the batch size (and so the kernel)
+                for k, r in enumerate(self.runs):
+                    y = r.net.pa_model(us[k])
+                    for (losses, pred, truth), o, t in ((outs[0][k], y[:fa.shape[0]], ta), (outs[1][k], y[fa.shape[0]:], tb)):
+                        losses.append(r.criterion(o, t)); pred.append(o); truth.append(t)
+        _metrics_many(self.runs, outs)
+
+
+def train_dpd_sweep(dataset_name=None, seeds=(0,), hidden_sizes=None, DPD_backbone="deltagru_tcnskip", DPD_hidden_size=15, PA_backbone="gru",
+                    PA_hidden_size=23, n_epochs=100, batch_size=256, lr=5e-4, accelerator="cuda", frame_length=200, thx=0.0, thh=0.0, **kwargs):
+    """`opendpd.api.train_dpd` for every (DPD hidden size, seed) pair, the runs of one (DPD, PA) shape pair advancing in lockstep on one GPU:
+    every training step of a group is ONE cascade launch for all its runs (+ one row reduction, one clip + AdamW launch).  Each run trains in
+    front of the frozen PA `train_pa` saved for its own seed and is its solo `train_dpd` bit for bit (same files under `save/` and `log/`).
+    Returns one result dictionary per run ({'status', 'model_path', 'log_path', 'seed', 'DPD_hidden_size', 'lockstep'}), in
+    hidden-size-major order.  Groups the sweep launch does not serve (quantised DPDs, other families or optimisers, a single run) advance
+    through the ordinary per-run epoch inside the same loop ('lockstep': False)."""
+    if not dataset_name:
+        raise ValueError("train_dpd_sweep requires dataset_name. Create a dataset first with create_dataset().")
+    from . import data as D
+    from . import project as PJ
+    runs = []
+    D._share = {}      # one parse of the dataset's CSV files for all runs ...
+    PJ._stream_share = {}      # ... and one upload of its train streams (read-only on the device)
+    try:
+        for H in (list(hidden_sizes) if hidden_sizes else [DPD_hidden_size]):
+            for seed in seeds:
+                run = _Run(None)
+                with run.rng:      # Project.__init__ seeds the global RNGs (project.py:108-112): from here on this run owns its own copy of them
+                    run.proj = Project(step="train_dpd", dataset_name=dataset_name, DPD_backbone=DPD_backbone, DPD_hidden_size=int(H),
+                                       PA_backbone=PA_backbone, PA_hidden_size=PA_hidden_size, n_epochs=n_epochs, batch_size=batch_size, lr=lr,
+                                       accelerator=accelerator, frame_length=frame_length, seed=int(seed), thx=thx, thh=thh, **kwargs)
+                    _setup_dpd(run)
+                runs.append(run)
+    finally:
+        D._share = None
+        PJ._stream_share = None
+    groups = {}
+    for r in runs:
+        groups.setdefault(_dpd_group_key(r), []).append(r)
+    groups = [_DpdGroup(v) for v in groups.values()]
+    _sweep_loop(runs, groups, n_epochs, "ACLR_AVG")
+    return [{"status": "completed", "model_path": r.proj.path_save_file_best, "log_path": r.proj.path_log_file_best, "seed": r.proj.seed,
+             "DPD_hidden_size": r.proj.DPD_hidden_size, "lockstep": bool(g_.train_sweep)} for g_ in groups for r in g_.runs]
