@@ -11,17 +11,16 @@
 //             lane, G_xp wave-uniform): one transposed mat-vec per step for W_hh^T (G_r, G_z, G_nh), dW_hh as rotated 4-block MFMA outer
 //             products against the masked state delta, dW_ih on the VALU.  dL/dx: dL/d(features) per step and the TCN's tap gradients are
 //             collected per SAMPLE in LDS over the frame (8 T floats) and turned into dL/d(I, Q) at the end of the sequence.
-#include "odpd_seq.h"
+#include "odpd_wide.h"
 #include "odpd_delta.h"
 
 namespace odpd {
 namespace {
-constexpr int kDC = 64, kDS = 65, kDNS = 8;
-constexpr int kDHs = ((kDC + 1) * kDS + 3) & ~3;
+constexpr int kDNS = 8;
 
-__host__ __device__ inline int dw_fwd_floats(int P) { return pad4(P) + kDC * 8 + 64 + kDC * kDS; }
+__host__ __device__ inline int dw_fwd_floats(int P) { return pad4(P) + kWC * 8 + 64 + kWC * kWS; }
 __host__ __device__ inline int dw_bwd_floats(int P, int T, bool dx) {
-    return pad4(P) + kDC * 2 + 4 * 64 + 64 + kDHs + (dx ? 8 * ((T + 3) & ~3) : 0);
+    return pad4(P) + kWC * 2 + 4 * 64 + 64 + kWHs + (dx ? 8 * ((T + 3) & ~3) : 0);
 }
 template <bool TRES>
 __device__ __forceinline__ void dw_stage_features(float* ftab, const float2* xg, int t0, int T, int lane) {
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(64) void wide_delta_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* ftab = smem + pad4(L.P);            // [64][8]: features of the chunk's steps
-    float* hb = ftab + kDC * 8;                // [64]: the masked state deltas, for the broadcast reads
+    float* hb = ftab + kWC * 8;                // [64]: the masked state deltas, for the broadcast reads
     float* hist = hb + 64;                     // [64][65]: h of the chunk's steps
     const bool vo = lane < H;
     float whh[3][64], wih[3][6], dm0[4];
@@ -88,8 +87,8 @@ __global__ __launch_bounds__(64) void wide_delta_fwd_kernel(SeqArgs a) {
         float* sv = SAVE ? a.ckpt + (size_t)b * T * kDNS * 64 : nullptr;
         float h = 0.0f, hp = 0.0f, xp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float dmr = dm0[0], dmz = dm0[1], dmn = dm0[2], dmnh = dm0[3], zx = 0.0f, zh = 0.0f;
-        for (int t0 = 0; t0 < T; t0 += kDC) {
-            const int len = min(kDC, T - t0);
+        for (int t0 = 0; t0 < T; t0 += kWC) {
+            const int len = min(kWC, T - t0);
             wave_lds_fence();
             dw_stage_features<TRES>(ftab, xg, t0, T, lane);
             wave_lds_fence();
@@ -141,11 +140,11 @@ __global__ __launch_bounds__(64) void wide_delta_fwd_kernel(SeqArgs a) {
                     s[448] = aux;
                 }
                 h = hn;
-                hist[tt * kDS + lane] = h;
+                hist[tt * kWS + lane] = h;
                 wave_lds_fence();
             }
             if (lane < len) {      // the chunk's outputs, lane = time step
-                const float* hr = hist + lane * kDS;
+                const float* hr = hist + lane * kWS;
                 float y0 = TRES ? 0.0f : pl[L.o_b_out], y1 = TRES ? 0.0f : pl[L.o_b_out + 1];
                 for (int j = 0; j < H; ++j) {
                     const float hv = hr[j];
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(64) void wide_delta_fwd_kernel(SeqArgs a) {
             }
         }
         if (a.stats != nullptr) {      // num_dx_zeros, num_dx_numel, num_dh_zeros, num_dh_numel of this sequence (deltagru.py:179-192)
-            for (int o = 32; o > 0; o >>= 1) zh += __shfl_xor(zh, o);
+            zh = wave_sum64(zh);
             if (lane == 0) {
                 atomicAdd(&a.stats[0], (double)zx); atomicAdd(&a.stats[1], 6.0 * (double)T);
                 atomicAdd(&a.stats[2], (double)zh); atomicAdd(&a.stats[3], (double)H * (double)T);
@@ -176,14 +175,14 @@ __global__ __launch_bounds__(64) void wide_delta_bwd_kernel(SeqArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
     const DeltaLayout L = delta_layout(a.H, TRES);
-    const int H = L.H, T = a.T, NC = (T + kDC - 1) / kDC, Tp = (T + 3) & ~3;
+    const int H = L.H, T = a.T, NC = (T + kWC - 1) / kWC, Tp = (T + 3) & ~3;
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* dyb = smem + pad4(L.P);             // [64][2]  dL/dy of the chunk's steps
-    float* dgb = dyb + kDC * 2;                // [4][64]  the step's G_r, G_z, G_nh, for the broadcast reads
+    float* dgb = dyb + kWC * 2;                // [4][64]  the step's G_r, G_z, G_nh, for the broadcast reads
     float* auxb = dgb + 4 * 64;                // [64]     the step's masked feature deltas (0..5) and their masks (8..13)
     float* hs = auxb + 64;                     // [65][65] row i = h(t0 - 1 + i)
-    float* dff = hs + kDHs;                    // DX: [6][Tp] dL/d(features) per step; [2][Tp] the TCN's dL/dx per sample
+    float* dff = hs + kWHs;                    // DX: [6][Tp] dL/d(features) per step; [2][Tp] the TCN's dL/dx per sample
     const bool vo = lane < H;
     float wih[3][6];
 #pragma unroll
@@ -192,12 +191,7 @@ __global__ __launch_bounds__(64) void wide_delta_bwd_kernel(SeqArgs a) {
         for (int i = 0; i < 6; ++i) wih[g][i] = vo ? pl[L.o_w_ih + (g * H + lane) * 6 + i] : 0.0f;
     const float wo0 = vo ? pl[L.o_w_out + lane] : 0.0f, wo1 = vo ? pl[L.o_w_out + H + lane] : 0.0f;
     f32x16 acc[3][4];
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[g][r][i] = 0.0f;
+    wide_zero_acc(acc);
     float dwih[3][6], dbs[4] = {0.f, 0.f, 0.f, 0.f}, dwo0 = 0.0f, dwo1 = 0.0f, tacc[26];      // tacc: fc_out bias (2) | TCN conv1 (18), conv2 (6), per time lane
 #pragma unroll
     for (int g = 0; g < 3; ++g)
@@ -216,14 +210,14 @@ __global__ __launch_bounds__(64) void wide_delta_bwd_kernel(SeqArgs a) {
             for (int i = lane; i < 8 * Tp; i += 64) dff[i] = 0.0f;
         }
         for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * kDC, len = min(kDC, T - t0);
+            const int t0 = c * kWC, len = min(kWC, T - t0);
             wave_lds_fence();
             float2 dyv = make_float2(0.0f, 0.0f);
             if (lane < len) dyv = dyg[t0 + lane];
             reinterpret_cast<float2*>(dyb)[lane] = dyv;
             if constexpr (NW && !TRES) { tacc[0] += dyv.x; tacc[1] += dyv.y; }
             hs[lane] = t0 > 0 ? sv[(size_t)(t0 - 1) * kDNS * 64 + 256 + lane] : 0.0f;
-            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kDS + lane] = sv[(size_t)(t0 + tt) * kDNS * 64 + 256 + lane];
+            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kWS + lane] = sv[(size_t)(t0 + tt) * kDNS * 64 + 256 + lane];
             if constexpr (TRES) {      // the TCN skip's gradients, lane = time step (state-free)
                 if (lane < len) {
                     const int t = t0 + lane;
@@ -269,7 +263,7 @@ __global__ __launch_bounds__(64) void wide_delta_bwd_kernel(SeqArgs a) {
                     const float* s = sv + (size_t)(t0 + tt - 1) * kDNS * 64 + lane;
                     rn = s[0]; zn = s[64]; nn = s[128]; qn = s[192]; dn_ = s[320]; mn_ = s[384]; an_ = s[448];
                 }
-                const float hprev = hs[tt * kDS + lane], ht = hs[(tt + 1) * kDS + lane];
+                const float hprev = hs[tt * kWS + lane], ht = hs[(tt + 1) * kWS + lane];
                 const float2 d = reinterpret_cast<const float2*>(dyb)[tt];
                 Gh = __builtin_fmaf(d.x, wo0, __builtin_fmaf(d.y, wo1, Gh));
                 if constexpr (NW) { dwo0 = __builtin_fmaf(d.x, ht, dwo0); dwo1 = __builtin_fmaf(d.y, ht, dwo1); }
@@ -357,13 +351,8 @@ __global__ __launch_bounds__(64) void wide_delta_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int i = lane; i < L.P + kLossCols; i += 64) prow[i] = 0.0f;
-        __builtin_amdgcn_s_waitcnt(0);
-        wave_lds_fence();
-#pragma unroll
-        for (int i = 0; i < 26; ++i)
-            for (int o = 32; o > 0; o >>= 1) tacc[i] += __shfl_xor(tacc[i], o);
+        float* prow = wide_partial_row(a.partials, L.P + kLossCols, lane);
+        wide_sum_lanes(tacc);
         if (lane == 0) {
             if constexpr (TRES) {
 #pragma unroll
@@ -397,12 +386,6 @@ __global__ __launch_bounds__(64) void wide_delta_bwd_kernel(SeqArgs a) {
                     }
     }
 }
-
-template <typename K>
-int dw_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    return launch_seq(st, k, grid, lds, a);
-}
 }  // namespace
 
 // float deltagru / deltagru_tcnskip of 33 .. 64 hidden units
@@ -410,30 +393,25 @@ bool delta_wide_ok(const odpd_model_t* m) {
     return (m->backbone == ODPD_DELTAGRU || m->backbone == ODPD_TRES_DELTAGRU) && m->bits_w == 0 && m->hidden > 32 && m->hidden <= 64;
 }
 int64_t delta_wide_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * T * kDNS * 64; }
-int delta_wide_rows(const odpd_model_t*, int B) { const int cap = 4 * device_cus(); return B < cap ? B : cap; }
+int delta_wide_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int delta_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!delta_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const bool tres = m->backbone == ODPD_TRES_DELTAGRU;
     const size_t lds = (size_t)dw_fwd_floats(delta_layout(m->hidden, tres).P) * sizeof(float);
-    const int grid = delta_wide_rows(m, a.B);
-    if (tres) return a.ckpt ? dw_launch(st, wide_delta_fwd_kernel<true, true>, grid, lds, a) : dw_launch(st, wide_delta_fwd_kernel<true, false>, grid, lds, a);
-    return a.ckpt ? dw_launch(st, wide_delta_fwd_kernel<false, true>, grid, lds, a) : dw_launch(st, wide_delta_fwd_kernel<false, false>, grid, lds, a);
+    return wide_fwd_dispatch(a, [&](auto sv) {
+        constexpr bool SAVE = decltype(sv)::value;
+        return tres ? wide_launch(st, wide_delta_fwd_kernel<true, SAVE>, lds, a) : wide_launch(st, wide_delta_fwd_kernel<false, SAVE>, lds, a);
+    });
 }
 int delta_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!delta_wide_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
-    const bool tres = m->backbone == ODPD_TRES_DELTAGRU, nw = a.partials != nullptr, dx = a.dx != nullptr;
-    const size_t lds = (size_t)dw_bwd_floats(delta_layout(m->hidden, tres).P, a.T, dx) * sizeof(float);
-    const int grid = delta_wide_rows(m, a.B);
-#define ODPD_DW_BWD(TR_)                                                                               \
-    if (tres == TR_) {                                                                                 \
-        if (nw && dx) return dw_launch(st, wide_delta_bwd_kernel<TR_, true, true>, grid, lds, a);      \
-        if (nw) return dw_launch(st, wide_delta_bwd_kernel<TR_, true, false>, grid, lds, a);           \
-        return dw_launch(st, wide_delta_bwd_kernel<TR_, false, true>, grid, lds, a);                   \
-    }
-    ODPD_DW_BWD(true) ODPD_DW_BWD(false)
-#undef ODPD_DW_BWD
-    return ODPD_EUNSUPPORTED;
+    const bool tres = m->backbone == ODPD_TRES_DELTAGRU;
+    const size_t lds = (size_t)dw_bwd_floats(delta_layout(m->hidden, tres).P, a.T, a.dx != nullptr) * sizeof(float);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) {
+        constexpr bool NW = decltype(nw)::value, DX = decltype(dx)::value;
+        return tres ? wide_launch(st, wide_delta_bwd_kernel<true, NW, DX>, lds, a) : wide_launch(st, wide_delta_bwd_kernel<false, NW, DX>, lds, a);
+    });
 }
 
 }  // namespace odpd

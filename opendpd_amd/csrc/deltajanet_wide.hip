@@ -9,17 +9,16 @@
 //             surgery finds one nn.Linear in this backbone, fc_out (the gates are nn.Parameter tensors, deltajanet.py:100-113), and makes it an
 //             INT_Linear (quant_layers.py:48-85): y = q_w(W) q_a(h) + b, three scale parameters behind fc_out.bias (gradients exactly 0),
 //             ODPD_FLAG_EVAL: the 16-bit output grid.  The recurrent cell stays float.
-#include "odpd_seq.h"
+#include "odpd_wide.h"
 #include "odpd_delta.h"
 #include "odpd_quant.h"
 
 namespace odpd {
 namespace {
-constexpr int kQC = 64, kQS = 65, kQNS = 5;
-constexpr int kQHs = ((kQC + 1) * kQS + 3) & ~3;
+constexpr int kQNS = 5;
 
-__host__ __device__ inline int dj_fwd_floats(int P) { return pad4(P) + kQC * 8 + 64 + kQC * kQS; }
-__host__ __device__ inline int dj_bwd_floats(int P) { return pad4(P) + kQC * 8 + kQC * 2 + kQC * 2 + 2 * 64 + 64 + kQHs; }
+__host__ __device__ inline int dj_fwd_floats(int P) { return pad4(P) + kWC * 8 + 64 + kWC * kWS; }
+__host__ __device__ inline int dj_bwd_floats(int P) { return pad4(P) + kWC * 8 + kWC * 2 + kWC * 2 + 2 * 64 + 64 + kWHs; }
 __device__ __forceinline__ void dj_stage_features(float* ftab, const float2* xg, int t0, int T, int lane) {
     const int t = t0 + lane;
     float f[6] = {0.5f, 0.5f, 0.7f, 0.35f, 0.7f, 0.7f};
@@ -37,7 +36,7 @@ __global__ __launch_bounds__(64) void wide_deltajanet_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, P);
     float* ftab = smem + pad4(P);              // [64][8]: features of the chunk's steps
-    float* hb = ftab + kQC * 8;                // [64]: the state deltas, for the broadcast reads
+    float* hb = ftab + kWC * 8;                // [64]: the state deltas, for the broadcast reads
     float* hist = hb + 64;                     // [64][65]: h of the chunk's steps
     const bool vo = lane < H;
     float whh[2][64], wih[2][6], dm0[2];
@@ -63,8 +62,8 @@ __global__ __launch_bounds__(64) void wide_deltajanet_fwd_kernel(SeqArgs a) {
         float2* yg = reinterpret_cast<float2*>(a.y) + (size_t)b * T;
         float* sv = SAVE ? a.ckpt + (size_t)b * T * kQNS * 64 : nullptr;
         float h = 0.0f, hp = 0.0f, xp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dmf = dm0[0], dmg = dm0[1], zx = 0.0f, zh = 0.0f;
-        for (int t0 = 0; t0 < T; t0 += kQC) {
-            const int len = min(kQC, T - t0);
+        for (int t0 = 0; t0 < T; t0 += kWC) {
+            const int len = min(kWC, T - t0);
             wave_lds_fence();
             dj_stage_features(ftab, xg, t0, T, lane);
             wave_lds_fence();
@@ -106,11 +105,11 @@ __global__ __launch_bounds__(64) void wide_deltajanet_fwd_kernel(SeqArgs a) {
                     s[256] = aux;
                 }
                 h = hn;
-                hist[tt * kQS + lane] = h;
+                hist[tt * kWS + lane] = h;
                 wave_lds_fence();
             }
             if (lane < len) {      // the chunk's outputs, lane = time step
-                const float* hr = hist + lane * kQS;
+                const float* hr = hist + lane * kWS;
                 float y0 = QH ? 0.0f : pl[L.o_b_out], y1 = QH ? 0.0f : pl[L.o_b_out + 1];
                 for (int j = 0; j < H; ++j) {
                     const float hv = QH ? q16::qapply(hr[j], qa) : hr[j];
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(64) void wide_deltajanet_fwd_kernel(SeqArgs a) {
             }
         }
         if (a.stats != nullptr) {
-            for (int o = 32; o > 0; o >>= 1) zh += __shfl_xor(zh, o);
+            zh = wave_sum64(zh);
             if (lane == 0) {
                 atomicAdd(&a.stats[0], (double)zx); atomicAdd(&a.stats[1], 6.0 * (double)T);
                 atomicAdd(&a.stats[2], (double)zh); atomicAdd(&a.stats[3], (double)H * (double)T);
@@ -139,13 +138,13 @@ __global__ __launch_bounds__(64) void wide_deltajanet_bwd_kernel(SeqArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
     const DeltaLayout L = delta_layout(a.H, 0, 2);
-    const int H = L.H, T = a.T, NC = (T + kQC - 1) / kQC, P = L.P + (QH ? 3 : 0);
+    const int H = L.H, T = a.T, NC = (T + kWC - 1) / kWC, P = L.P + (QH ? 3 : 0);
     float* pl = smem;
     stage_params(pl, a.params, P);
     float* ftab = smem + pad4(P);              // [64][8]  features of the chunk's steps (for dL/dx)
-    float* dxb = ftab + kQC * 8;               // [64][2]  dL/dx of the chunk's steps
-    float* dyb = dxb + kQC * 2;                // [64][2]  dL/dy of the chunk's steps
-    float* dgb = dyb + kQC * 2;                // [2][64]  the step's G_f, G_g, for the broadcast reads
+    float* dxb = ftab + kWC * 8;               // [64][2]  dL/dx of the chunk's steps
+    float* dyb = dxb + kWC * 2;                // [64][2]  dL/dy of the chunk's steps
+    float* dgb = dyb + kWC * 2;                // [2][64]  the step's G_f, G_g, for the broadcast reads
     float* auxb = dgb + 2 * 64;                // [64]     the step's feature deltas (0..5)
     float* hs = auxb + 64;                     // [65][65] row i = h(t0 - 1 + i)
     const bool vo = lane < H;
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(64) void wide_deltajanet_bwd_kernel(SeqArgs a) {
         const float* sv = a.ckpt + (size_t)b * T * kQNS * 64;
         float Gh = 0.0f, Ghp = 0.0f, Gf = 0.0f, Gg = 0.0f, Gxp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * kQC, len = min(kQC, T - t0);
+            const int t0 = c * kWC, len = min(kWC, T - t0);
             wave_lds_fence();
             dj_stage_features(ftab, xg, t0, T, lane);
             float2 dyv = make_float2(0.0f, 0.0f);
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(64) void wide_deltajanet_bwd_kernel(SeqArgs a) {
             reinterpret_cast<float2*>(dyb)[lane] = dyv;
             if constexpr (NW) { tb0 += dyv.x; tb1 += dyv.y; }
             hs[lane] = t0 > 0 ? sv[(size_t)(t0 - 1) * kQNS * 64 + 128 + lane] : 0.0f;
-            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kQS + lane] = sv[(size_t)(t0 + tt) * kQNS * 64 + 128 + lane];
+            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kWS + lane] = sv[(size_t)(t0 + tt) * kQNS * 64 + 128 + lane];
             wave_lds_fence();
             float fn_, gn_, dn_, an_;
             {
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(64) void wide_deltajanet_bwd_kernel(SeqArgs a) {
                     const float* s = sv + (size_t)(t0 + tt - 1) * kQNS * 64 + lane;
                     fn_ = s[0]; gn_ = s[64]; dn_ = s[192]; an_ = s[256];
                 }
-                const float hprev = hs[tt * kQS + lane], ht = hs[(tt + 1) * kQS + lane];
+                const float hprev = hs[tt * kWS + lane], ht = hs[(tt + 1) * kWS + lane];
                 const float2 d = reinterpret_cast<const float2*>(dyb)[tt];
                 if constexpr (QH) {      // q_a(h) feeds the head; dL/dh passes where h lies inside the activation grid
                     const float hq = q16::qapply(ht, qa);
@@ -276,11 +275,8 @@ __global__ __launch_bounds__(64) void wide_deltajanet_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (P + kLossCols);      // (the scale parameters' columns stay 0: round() inside the quantiser)
-        for (int i = lane; i < P + kLossCols; i += 64) prow[i] = 0.0f;
-        __builtin_amdgcn_s_waitcnt(0);
-        wave_lds_fence();
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
+        float* prow = wide_partial_row(a.partials, P + kLossCols, lane);      // (the scale parameters' columns stay 0: round() inside the quantiser)
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
         if (lane == 0) { prow[L.o_b_out] = tb0; prow[L.o_b_out + 1] = tb1; }
         if (vo) {
             prow[L.o_w_out + lane] = dwo0 * wm0; prow[L.o_w_out + H + lane] = dwo1 * wm1;
@@ -315,29 +311,25 @@ bool deltajanet_wide_ok(const odpd_model_t* m) {
 }
 static int dj_params(const odpd_model_t* m) { return delta_layout(m->hidden, 0, 2).P + (m->bits_w > 0 ? 3 : 0); }
 int64_t deltajanet_wide_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * T * kQNS * 64; }
-int deltajanet_wide_rows(const odpd_model_t*, int B) { const int cap = 4 * device_cus(); return B < cap ? B : cap; }
+int deltajanet_wide_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int deltajanet_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!deltajanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)dj_fwd_floats(dj_params(m)) * sizeof(float);
-    const int grid = deltajanet_wide_rows(m, a.B);
-    if (m->bits_w > 0)
-        return a.ckpt ? launch_seq(st, wide_deltajanet_fwd_kernel<true, true>, grid, lds, a) : launch_seq(st, wide_deltajanet_fwd_kernel<false, true>, grid, lds, a);
-    return a.ckpt ? launch_seq(st, wide_deltajanet_fwd_kernel<true, false>, grid, lds, a) : launch_seq(st, wide_deltajanet_fwd_kernel<false, false>, grid, lds, a);
+    const bool qh = m->bits_w > 0;
+    return wide_fwd_dispatch(a, [&](auto sv) {
+        constexpr bool SAVE = decltype(sv)::value;
+        return qh ? wide_launch(st, wide_deltajanet_fwd_kernel<SAVE, true>, lds, a) : wide_launch(st, wide_deltajanet_fwd_kernel<SAVE, false>, lds, a);
+    });
 }
 int deltajanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!deltajanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
     const size_t lds = (size_t)dj_bwd_floats(dj_params(m)) * sizeof(float);
-    const int grid = deltajanet_wide_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (m->bits_w > 0) {
-        if (nw && dx) return launch_seq(st, wide_deltajanet_bwd_kernel<true, true, true>, grid, lds, a);
-        if (nw) return launch_seq(st, wide_deltajanet_bwd_kernel<true, false, true>, grid, lds, a);
-        return launch_seq(st, wide_deltajanet_bwd_kernel<false, true, true>, grid, lds, a);
-    }
-    if (nw && dx) return launch_seq(st, wide_deltajanet_bwd_kernel<true, true, false>, grid, lds, a);
-    if (nw) return launch_seq(st, wide_deltajanet_bwd_kernel<true, false, false>, grid, lds, a);
-    return launch_seq(st, wide_deltajanet_bwd_kernel<false, true, false>, grid, lds, a);
+    const bool qh = m->bits_w > 0;
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) {
+        constexpr bool NW = decltype(nw)::value, DX = decltype(dx)::value;
+        return qh ? wide_launch(st, wide_deltajanet_bwd_kernel<NW, DX, true>, lds, a) : wide_launch(st, wide_deltajanet_bwd_kernel<NW, DX, false>, lds, a);
+    });
 }
 
 }  // namespace odpd

@@ -13,12 +13,11 @@
 //   dgru      its head (relu(fc_hid h2), fc_out over [hid, features]) runs with lane = tick on the chunk, reading the features of time s - 1 at tick
 //             s; in the backward pass the head's share of dL/dx(s - 1) is stored at tick s and layer 1 adds its share at tick s - 1.
 // Per-tick records (r, z, n, W_hn h + b_hn, h of both layers; dgru: + the fc_hid pre-activation) in HBM: B x (T + 1) x 5 (6) x 64 floats.
-#include "odpd_seq.h"
+#include "odpd_wide.h"
 
 namespace odpd {
 namespace {
-constexpr int k2C = 64, k2S = 65, k2NS = 5;
-constexpr int k2Hs = ((k2C + 1) * k2S + 3) & ~3;
+constexpr int k2NS = 5;
 
 struct Gru2Layout { int H, F, OW, o_w_ih0, o_w_hh0, o_b_ih0, o_b_hh0, o_w_ih1, o_w_hh1, o_b_ih1, o_b_hh1, o_w_out, o_b_out, o_w_hid, o_b_hid, P; };
 // named_parameters() of nn.GRU(F -> H, num_layers 2) + fc_out (dgru: over [relu(fc_hid h), features], then fc_hid: dgru.py:22-32)
@@ -41,9 +40,9 @@ __host__ __device__ inline int gru2_super_index(const Gru2Layout& L, int g, int 
     return k < 32 ? L.o_w_ih1 + (g * H + ju) * H + ku : L.o_w_hh1 + (g * H + ju) * H + ku;
 }
 constexpr int k2X = 33;          // row stride of the dgru head's [tick][unit <= 32] arrays
-__host__ __device__ inline int gru2_fwd_floats(int P, bool dg) { return pad4(P) + (k2C + 1) * 8 + 64 + k2C * k2S + (dg ? k2C * k2X + 32 * 32 : 0); }
+__host__ __device__ inline int gru2_fwd_floats(int P, bool dg) { return pad4(P) + (kWC + 1) * 8 + 64 + kWC * kWS + (dg ? kWC * k2X + 32 * 32 : 0); }
 __host__ __device__ inline int gru2_bwd_floats(int P, bool dg) {
-    return pad4(P) + 3 * 64 * 64 + (k2C + 1) * 8 + k2C * 2 + k2C * 2 + 4 * 64 + k2Hs + (dg ? 2 * k2C * k2X + 32 * 32 : 0);
+    return pad4(P) + 3 * 64 * 64 + (kWC + 1) * 8 + kWC * 2 + kWC * 2 + 4 * 64 + kWHs + (dg ? 2 * kWC * k2X + 32 * 32 : 0);
 }
 
 // features of the chunk's ticks: row 1 + i = time s0 + i (layer 1's input at that tick), row 0 = time s0 - 1 (the dgru head of tick s0 reads it)
@@ -75,10 +74,10 @@ __global__ __launch_bounds__(64) void gru2_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* ftab = smem + pad4(L.P);            // [65][8]: features (gru2_stage_features)
-    float* hb = ftab + (k2C + 1) * 8;          // [64]: [h1 | h2], for the broadcast reads
+    float* hb = ftab + (kWC + 1) * 8;          // [64]: [h1 | h2], for the broadcast reads
     float* hist = hb + 64;                     // [64][65]: the state after each tick of the chunk
-    float* hist2 = hist + k2C * k2S;           // DG: [64][33] fc_hid pre-activations of the chunk's ticks
-    float* whp = hist2 + k2C * k2X;            // DG: fc_hid rows, zero padded to 32 columns (64 x 33 floats before it: 16-byte aligned)
+    float* hist2 = hist + kWC * kWS;           // DG: [64][33] fc_hid pre-activations of the chunk's ticks
+    float* whp = hist2 + kWC * k2X;            // DG: fc_hid rows, zero padded to 32 columns (64 x 33 floats before it: 16-byte aligned)
     const bool vo = ju < H;
     if constexpr (DG) {
         for (int i = lane; i < 32 * 32; i += 64) whp[i] = ((i >> 5) < H && (i & 31) < H) ? pl[L.o_w_hid + (i >> 5) * H + (i & 31)] : 0.0f;
@@ -99,8 +98,8 @@ __global__ __launch_bounds__(64) void gru2_fwd_kernel(SeqArgs a) {
         float2* yg = reinterpret_cast<float2*>(a.y) + (size_t)b * T;
         float* sv = SAVE ? a.ckpt + (size_t)b * NT * NS * 64 : nullptr;
         float h = 0.0f;
-        for (int s0 = 0; s0 < NT; s0 += k2C) {
-            const int len = min(k2C, NT - s0);
+        for (int s0 = 0; s0 < NT; s0 += kWC) {
+            const int len = min(kWC, NT - s0);
             wave_lds_fence();
             gru2_stage_features<FM>(ftab, xg, s0, T, lane);
             wave_lds_fence();
@@ -139,12 +138,12 @@ __global__ __launch_bounds__(64) void gru2_fwd_kernel(SeqArgs a) {
                     rec[0] = r; rec[64] = z; rec[128] = n; rec[192] = gh[2]; rec[256] = hn;
                 }
                 h = hn;
-                hist[tt * k2S + lane] = h;
+                hist[tt * kWS + lane] = h;
                 wave_lds_fence();
             }
             // outputs of the chunk's ticks, lane = tick: y(s - 1) = fc_out(h2(s - 1))
             if (lane < len && s0 + lane >= 1) {
-                const float* hr = hist + lane * k2S + 32;
+                const float* hr = hist + lane * kWS + 32;
                 float y0 = pl[L.o_b_out], y1 = pl[L.o_b_out + 1];
                 if constexpr (!DG) {
                     for (int j = 0; j < H; ++j) {
@@ -193,18 +192,18 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
     const int lane = threadIdx.x & 63, ju = lane & 31, col = lane & 15, quad = lane >> 4;
     const bool l2 = lane >= 32;
     const Gru2Layout L = gru2_layout(a.H, F, DG);
-    const int H = L.H, T = a.T, NT = T + 1, NC = (NT + k2C - 1) / k2C, OW = L.OW;
+    const int H = L.H, T = a.T, NT = T + 1, NC = (NT + kWC - 1) / kWC, OW = L.OW;
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* wsup = smem + pad4(L.P);            // [3][64][64]: the gates' block matrices (row j, column k), zero padded
     float* ftab = wsup + 3 * 64 * 64;          // [65][8]  features (gru2_stage_features)
-    float* dxb = ftab + (k2C + 1) * 8;         // [64][2]  dL/dx of the chunk's ticks (layer 1's share)
-    float* dyb = dxb + k2C * 2;                // [64][2]  dL/dy(s - 1) at tick s
-    float* dgb = dyb + k2C * 2;                // [4][64]  d_r, d_z, n-gate gradient for first-half columns, for second-half columns
+    float* dxb = ftab + (kWC + 1) * 8;         // [64][2]  dL/dx of the chunk's ticks (layer 1's share)
+    float* dyb = dxb + kWC * 2;                // [64][2]  dL/dy(s - 1) at tick s
+    float* dgb = dyb + kWC * 2;                // [4][64]  d_r, d_z, n-gate gradient for first-half columns, for second-half columns
     float* hs = dgb + 4 * 64;                  // [65][65] row i = the state after tick s0 - 1 + i
-    float* x1 = hs + k2Hs;                     // DG: [64][33] relu(fc_hid) of the tick, then fc_hid^T dL/dhid
-    float* dhid = x1 + k2C * k2X;              // DG: [64][33] dL/d(fc_hid pre-activation)
-    float* whp = dhid + k2C * k2X;             // DG: fc_hid rows, zero padded to 32 columns
+    float* x1 = hs + kWHs;                     // DG: [64][33] relu(fc_hid) of the tick, then fc_hid^T dL/dhid
+    float* dhid = x1 + kWC * k2X;              // DG: [64][33] dL/d(fc_hid pre-activation)
+    float* whp = dhid + kWC * k2X;             // DG: fc_hid rows, zero padded to 32 columns
     const bool vo = ju < H;
     if constexpr (DG) {
         for (int i = lane; i < 32 * 32; i += 64) whp[i] = ((i >> 5) < H && (i & 31) < H) ? pl[L.o_w_hid + (i >> 5) * H + (i & 31)] : 0.0f;
@@ -229,12 +228,7 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) tf[i] = 0.0f;
     f32x16 acc[3][4];
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[g][r][i] = 0.0f;
+    wide_zero_acc(acc);
     float dwih[3][F], dbs[4] = {0.f, 0.f, 0.f, 0.f}, dwo0 = 0.0f, dwo1 = 0.0f, tb0 = 0.0f, tb1 = 0.0f;
 #pragma unroll
     for (int g = 0; g < 3; ++g)
@@ -248,7 +242,7 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
         const float* sv = a.ckpt + (size_t)b * NT * NS * 64;
         float dh = 0.0f;
         for (int c = NC - 1; c >= 0; --c) {
-            const int s0 = c * k2C, len = min(k2C, NT - s0);
+            const int s0 = c * kWC, len = min(kWC, NT - s0);
             wave_lds_fence();
             gru2_stage_features<FM>(ftab, xg, s0, T, lane);
             float2 dyv = make_float2(0.0f, 0.0f);
@@ -256,8 +250,8 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
             reinterpret_cast<float2*>(dyb)[lane] = dyv;
             if constexpr (NW) { tb0 += dyv.x; tb1 += dyv.y; }
             hs[lane] = s0 > 0 ? sv[(size_t)(s0 - 1) * NS * 64 + 256 + lane] : 0.0f;
-            for (int tt = 0; tt < k2C; ++tt) {
-                hs[(tt + 1) * k2S + lane] = tt < len ? sv[(size_t)(s0 + tt) * NS * 64 + 256 + lane] : 0.0f;
+            for (int tt = 0; tt < kWC; ++tt) {
+                hs[(tt + 1) * kWS + lane] = tt < len ? sv[(size_t)(s0 + tt) * NS * 64 + 256 + lane] : 0.0f;
                 if constexpr (DG) { if (l2) x1[tt * k2X + ju] = tt < len ? sv[(size_t)(s0 + tt) * NS * 64 + 320 + lane] : 0.0f; }
             }
             wave_lds_fence();
@@ -303,9 +297,9 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
 #pragma unroll
                         for (int kb = 0; kb < 2; ++kb) {
                             f32x4 t = ahid[jb][kb];
-                            for (int t4 = 0; t4 < k2C / 4; ++t4) {
+                            for (int t4 = 0; t4 < kWC / 4; ++t4) {
                                 const float av = dhid[(4 * t4 + quad) * k2X + 16 * jb + col];
-                                const float bv = hs[(4 * t4 + quad + 1) * k2S + 32 + 16 * kb + col];
+                                const float bv = hs[(4 * t4 + quad + 1) * kWS + 32 + 16 * kb + col];
                                 t = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, t, 0, 0, 0);
                             }
                             ahid[jb][kb] = t;
@@ -345,7 +339,7 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
                     rn = rec[0]; zn = rec[64]; nn = rec[128]; gn_ = rec[192];
                 }
                 const bool active = vo && (l2 ? s >= 1 : s < T);
-                const float hp = hs[tt * k2S + lane], ht = hs[(tt + 1) * k2S + lane];
+                const float hp = hs[tt * kWS + lane], ht = hs[(tt + 1) * kWS + lane];
                 const float2 d = reinterpret_cast<const float2*>(dyb)[tt];
                 float dht = __builtin_fmaf(d.x, wo0, __builtin_fmaf(d.y, wo1, dh));      // (layer 1 lanes, dgru: wo = 0)
                 if constexpr (DG) { if (l2) dht += x1[tt * k2X + ju]; }
@@ -428,16 +422,9 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int i = lane; i < L.P + kLossCols; i += 64) prow[i] = 0.0f;
-        __builtin_amdgcn_s_waitcnt(0);
-        wave_lds_fence();
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
-        if constexpr (DG) {
-#pragma unroll
-            for (int i = 0; i < 12; ++i)
-                for (int o = 32; o > 0; o >>= 1) tf[i] += __shfl_xor(tf[i], o);
-        }
+        float* prow = wide_partial_row(a.partials, L.P + kLossCols, lane);
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
+        if constexpr (DG) wide_sum_lanes(tf);
         if (lane == 0) {
             prow[L.o_b_out] = tb0; prow[L.o_b_out + 1] = tb1;
             if constexpr (DG) {
@@ -507,14 +494,13 @@ int64_t gru2_param_count(const odpd_model_t* m) {
     return gru2_P(m, FM);
 }
 int64_t gru2_ckpt_floats(const odpd_model_t* m, int B, int T) { return (int64_t)B * (T + 1) * (m->backbone == ODPD_DGRU ? 6 : k2NS) * 64; }
-int gru2_rows(const odpd_model_t*, int B) { const int cap = 4 * device_cus(); return B < cap ? B : cap; }
+int gru2_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int gru2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     int FM;
     if (!gru2_ok(m) || !gru2_cfg(m, FM)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)gru2_fwd_floats(gru2_P(m, FM), FM == FEAT_DGRU6) * sizeof(float);
-    const int grid = gru2_rows(m, a.B);
 #define ODPD_GRU2_FWD(FM_, DG_) \
-    if (FM == FM_) return a.ckpt ? launch_seq(st, gru2_fwd_kernel<FM_, DG_, true>, grid, lds, a) : launch_seq(st, gru2_fwd_kernel<FM_, DG_, false>, grid, lds, a);
+    if (FM == FM_) return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, gru2_fwd_kernel<FM_, DG_, decltype(sv)::value>, lds, a); });
     ODPD_GRU2_FWD(FEAT_RAW2, false) ODPD_GRU2_FWD(FEAT_DGRU6, true) ODPD_GRU2_FWD(FEAT_Q4, false) ODPD_GRU2_FWD(FEAT_A4, false)
 #undef ODPD_GRU2_FWD
     return ODPD_EUNSUPPORTED;
@@ -524,14 +510,11 @@ int gru2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!gru2_ok(m) || !gru2_cfg(m, FM)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
     const size_t lds = (size_t)gru2_bwd_floats(gru2_P(m, FM), FM == FEAT_DGRU6) * sizeof(float);
-    const int grid = gru2_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-#define ODPD_GRU2_BWD(FM_, DG_)                                                                       \
-    if (FM == FM_) {                                                                                  \
-        if (nw && dx) return launch_seq(st, gru2_bwd_kernel<FM_, DG_, true, true>, grid, lds, a);     \
-        if (nw) return launch_seq(st, gru2_bwd_kernel<FM_, DG_, true, false>, grid, lds, a);          \
-        return launch_seq(st, gru2_bwd_kernel<FM_, DG_, false, true>, grid, lds, a);                  \
-    }
+#define ODPD_GRU2_BWD(FM_, DG_)                                                                                              \
+    if (FM == FM_)                                                                                                           \
+        return s16_bwd_dispatch(a, [&](auto nw, auto dx) {                                                                   \
+            return wide_launch(st, gru2_bwd_kernel<FM_, DG_, decltype(nw)::value, decltype(dx)::value>, lds, a);             \
+        });
     ODPD_GRU2_BWD(FEAT_RAW2, false) ODPD_GRU2_BWD(FEAT_DGRU6, true) ODPD_GRU2_BWD(FEAT_Q4, false) ODPD_GRU2_BWD(FEAT_A4, false)
 #undef ODPD_GRU2_BWD
     return ODPD_EUNSUPPORTED;

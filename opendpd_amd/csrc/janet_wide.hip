@@ -10,14 +10,14 @@
 //             their u-columns (dL/du) — the two transposed mat-vecs of that stage run side by side in the two halves —; A turns dL/du into d_a, d_p1,
 //             d_p2 -> LDS; B adds W_a^T d_a + W_p1^T d_p1 + W_p2^T d_p2.  The seven H x H gradient blocks accumulate as 4-block MFMA outer products
 //             (block = (row half-tile, column half-tile) of the 32 x 32 block): 7 x 16 accumulators.
-#include "odpd_seq.h"
+#include "odpd_wide.h"
 
 namespace odpd {
 namespace {
-constexpr int kJC = 64, kJS = 33, kJNS = 4;
+constexpr int kJS = 33, kJNS = 4;      // row stride of the [time][unit <= 32] arrays, record slots
 
-__host__ __device__ inline int jw_fwd_floats(int P) { return pad4(P) + kJC * 4 + 64 + kJC * kJS; }
-__host__ __device__ inline int jw_bwd_floats(int P) { return pad4(P) + kJC * 4 + kJC * 2 + kJC * 2 + 8 * 32 + (kJC + 1) * kJS + 3; }
+__host__ __device__ inline int jw_fwd_floats(int P) { return pad4(P) + kWC * 4 + 64 + kWC * kJS; }
+__host__ __device__ inline int jw_bwd_floats(int P) { return pad4(P) + kWC * 4 + kWC * 2 + kWC * 2 + 8 * 32 + (kWC + 1) * kJS + 3; }
 
 // |x|, cos(theta), sin(theta) of the chunk's steps (theta = atan2(Q, I): cos = I / |x|, sin = Q / |x|), lane = time step
 __device__ __forceinline__ void jw_stage_inputs(float* ftab, const float2* xg, int t0, int T, int lane) {
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(64) void wide_pgjanet_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* ftab = smem + pad4(L.P);            // [64][4]: |x|, cos, sin of the chunk's steps
-    float* hb = ftab + kJC * 4;                // [32] h | [32] u, for the broadcast reads
+    float* hb = ftab + kWC * 4;                // [32] h | [32] u, for the broadcast reads
     float* hist = hb + 64;                     // [64][33]: h of the chunk's steps
     const bool vo = ju < H;
     // half A: rows of W_a, W_p1, W_p2 over h, their scalar-input column and bias; half B: rows of W_f, W_g over h (wh) and over u (wu)
@@ -61,8 +61,8 @@ __global__ __launch_bounds__(64) void wide_pgjanet_fwd_kernel(SeqArgs a) {
         float2* yg = reinterpret_cast<float2*>(a.y) + (size_t)b * T;
         float* sv = SAVE ? a.ckpt + (size_t)b * T * kJNS * 64 : nullptr;
         float h = 0.0f;                                  // (half B)
-        for (int t0 = 0; t0 < T; t0 += kJC) {
-            const int len = min(kJC, T - t0);
+        for (int t0 = 0; t0 < T; t0 += kWC) {
+            const int len = min(kWC, T - t0);
             wave_lds_fence();
             jw_stage_inputs(ftab, xg, t0, T, lane);
             wave_lds_fence();
@@ -128,13 +128,13 @@ __global__ __launch_bounds__(64) void wide_pgjanet_bwd_kernel(SeqArgs a) {
     const int lane = threadIdx.x & 63, ju = lane & 31, col = lane & 15, quad = lane >> 4;
     const bool hb_ = lane >= 32;
     const JanetLayout L = janet_layout(a.H);
-    const int H = L.H, T = a.T, NC = (T + kJC - 1) / kJC, H1 = H + 1, H2 = 2 * H;
+    const int H = L.H, T = a.T, NC = (T + kWC - 1) / kWC, H1 = H + 1, H2 = 2 * H;
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* ftab = smem + pad4(L.P);            // [64][4]  |x|, cos, sin of the chunk's steps
-    float* dxb = ftab + kJC * 4;               // [64][2]  dL/dx of the chunk's steps
-    float* dyb = dxb + kJC * 2;                // [64][2]  dL/dy of the chunk's steps
-    float* vb = dyb + kJC * 2;                 // [8][32]  the step's vectors: 0 d_f, 1 d_g, 2 d_a, 3 d_p1, 4 d_p2, 5 h(t-1), 6 u(t)
+    float* dxb = ftab + kWC * 4;               // [64][2]  dL/dx of the chunk's steps
+    float* dyb = dxb + kWC * 2;                // [64][2]  dL/dy of the chunk's steps
+    float* vb = dyb + kWC * 2;                 // [8][32]  the step's vectors: 0 d_f, 1 d_g, 2 d_a, 3 d_p1, 4 d_p2, 5 h(t-1), 6 u(t)
     float* hs = vb + 8 * 32;                   // [65][33] row i = h(t0 - 1 + i)
     const bool vo = ju < H;
     const float wo0 = (hb_ && vo) ? pl[L.o_wo + ju] : 0.0f, wo1 = (hb_ && vo) ? pl[L.o_wo + H + ju] : 0.0f;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(64) void wide_pgjanet_bwd_kernel(SeqArgs a) {
         const float* sv = a.ckpt + (size_t)b * T * kJNS * 64;
         float dh = 0.0f;                                 // (half B)
         for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * kJC, len = min(kJC, T - t0);
+            const int t0 = c * kWC, len = min(kWC, T - t0);
             wave_lds_fence();
             jw_stage_inputs(ftab, xg, t0, T, lane);
             float2 dyv = make_float2(0.0f, 0.0f);
@@ -270,11 +270,8 @@ __global__ __launch_bounds__(64) void wide_pgjanet_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int i = lane; i < L.P + kLossCols; i += 64) prow[i] = 0.0f;
-        __builtin_amdgcn_s_waitcnt(0);
-        wave_lds_fence();
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
+        float* prow = wide_partial_row(a.partials, L.P + kLossCols, lane);
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
         if (lane == 0) { prow[L.o_bo] = tb0; prow[L.o_bo + 1] = tb1; }
         if (vo) {
             if (hb_) {
@@ -308,22 +305,17 @@ __global__ __launch_bounds__(64) void wide_pgjanet_bwd_kernel(SeqArgs a) {
 // pgjanet of 17 .. 32 hidden units
 bool pgjanet_wide_ok(const odpd_model_t* m) { return m->backbone == ODPD_PGJANET && m->bits_w == 0 && m->hidden > 16 && m->hidden <= 32; }
 int64_t pgjanet_wide_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * T * kJNS * 64; }
-int pgjanet_wide_rows(const odpd_model_t*, int B) { const int cap = 4 * device_cus(); return B < cap ? B : cap; }
+int pgjanet_wide_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int pgjanet_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)jw_fwd_floats(janet_layout(m->hidden).P) * sizeof(float);
-    const int grid = pgjanet_wide_rows(m, a.B);
-    return a.ckpt ? launch_seq(st, wide_pgjanet_fwd_kernel<true>, grid, lds, a) : launch_seq(st, wide_pgjanet_fwd_kernel<false>, grid, lds, a);
+    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, wide_pgjanet_fwd_kernel<decltype(sv)::value>, lds, a); });
 }
 int pgjanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
     const size_t lds = (size_t)jw_bwd_floats(janet_layout(m->hidden).P) * sizeof(float);
-    const int grid = pgjanet_wide_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_seq(st, wide_pgjanet_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return launch_seq(st, wide_pgjanet_bwd_kernel<true, false>, grid, lds, a);
-    return launch_seq(st, wide_pgjanet_bwd_kernel<false, true>, grid, lds, a);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return wide_launch(st, wide_pgjanet_bwd_kernel<decltype(nw)::value, decltype(dx)::value>, lds, a); });
 }
 
 }  // namespace odpd

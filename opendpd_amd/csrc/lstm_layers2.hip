@@ -3,12 +3,11 @@
 // [[W_hh0, 0], [W_ih1, W_hh1]] per gate against the broadcast vector [h1(s-1) | h2(s-2)] — with lstm_wide.hip's step arithmetic (four gates i, f,
 // g, o whose input and hidden parts simply add; (h, c) per lane; gate o's row in a padded LDS copy in the forward pass).
 // Per-tick records (i, f, g, o, c, h of both layers) in HBM: B x (T + 1) x 6 x 64 floats.
-#include "odpd_seq.h"
+#include "odpd_wide.h"
 
 namespace odpd {
 namespace {
-constexpr int kLC = 64, kLS = 65, kLNS = 6;
-constexpr int kLHs = ((kLC + 1) * kLS + 3) & ~3;
+constexpr int kLNS = 6;
 
 struct Lstm2Layout { int H, o_w_ih0, o_w_hh0, o_b_ih0, o_b_hh0, o_w_ih1, o_w_hh1, o_b_ih1, o_b_hh1, o_w_out, o_b_out, P; };
 __host__ __device__ inline Lstm2Layout lstm2_layout(int H) {      // named_parameters() of nn.LSTM(2 -> H, num_layers 2) + fc_out
@@ -28,8 +27,8 @@ __host__ __device__ inline int lstm2_super_index(const Lstm2Layout& L, int g, in
     if (j < 32) return k < 32 ? L.o_w_hh0 + (g * H + ju) * H + ku : -1;
     return k < 32 ? L.o_w_ih1 + (g * H + ju) * H + ku : L.o_w_hh1 + (g * H + ju) * H + ku;
 }
-__host__ __device__ inline int lstm2_fwd_floats(int P) { return pad4(P) + kLC * 2 + 64 + kLC * kLS + 64 * kLS; }
-__host__ __device__ inline int lstm2_bwd_floats(int P) { return pad4(P) + 4 * 64 * 64 + kLC * 2 + kLC * 2 + kLC * 2 + 4 * 64 + kLHs; }
+__host__ __device__ inline int lstm2_fwd_floats(int P) { return pad4(P) + kWC * 2 + 64 + kWC * kWS + 64 * kWS; }
+__host__ __device__ inline int lstm2_bwd_floats(int P) { return pad4(P) + 4 * 64 * 64 + kWC * 2 + kWC * 2 + kWC * 2 + 4 * 64 + kWHs; }
 
 template <bool SAVE>
 __global__ __launch_bounds__(64) void lstm2_fwd_kernel(SeqArgs a) {
@@ -41,12 +40,12 @@ __global__ __launch_bounds__(64) void lstm2_fwd_kernel(SeqArgs a) {
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* xb = smem + pad4(L.P);              // [64][2]: I, Q of the chunk's steps
-    float* hb = xb + kLC * 2;                  // [64]: the state, for the broadcast reads
+    float* hb = xb + kWC * 2;                  // [64]: the state, for the broadcast reads
     float* hist = hb + 64;                     // [64][65]: h of the chunk's steps
-    float* wop = hist + kLC * kLS;             // [64][65]: gate o's block-matrix rows
+    float* wop = hist + kWC * kWS;             // [64][65]: gate o's block-matrix rows
     const bool vo = ju < H;
-    for (int i = lane; i < 64 * kLS; i += 64) {
-        const int j = i / kLS, k = i % kLS;
+    for (int i = lane; i < 64 * kWS; i += 64) {
+        const int j = i / kWS, k = i % kWS;
         const int idx = k < 64 ? lstm2_super_index(L, 3, j, k) : -1;
         wop[i] = idx >= 0 ? pl[idx] : 0.0f;
     }
@@ -67,8 +66,8 @@ __global__ __launch_bounds__(64) void lstm2_fwd_kernel(SeqArgs a) {
         float2* yg = reinterpret_cast<float2*>(a.y) + (size_t)b * T;
         float* sv = SAVE ? a.ckpt + (size_t)b * NT * kLNS * 64 : nullptr;
         float h = 0.0f, c = 0.0f;
-        for (int t0 = 0; t0 < NT; t0 += kLC) {
-            const int len = min(kLC, NT - t0);
+        for (int t0 = 0; t0 < NT; t0 += kWC) {
+            const int len = min(kWC, NT - t0);
             wave_lds_fence();
             reinterpret_cast<float2*>(xb)[lane] = t0 + lane < T ? xg[t0 + lane] : make_float2(0.0f, 0.0f);
             wave_lds_fence();
@@ -80,15 +79,11 @@ __global__ __launch_bounds__(64) void lstm2_fwd_kernel(SeqArgs a) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) pre[g] = __builtin_fmaf(wih[g][1], xv.y, __builtin_fmaf(wih[g][0], xv.x, bg[g]));
                 const float4* hb4 = reinterpret_cast<const float4*>(hb);
-                const float* wo = wop + lane * kLS;
+                const float* wo = wop + lane * kWS;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const float4 hv = hb4[q];
-#pragma unroll
-                    for (int g = 0; g < 3; ++g) {
-                        pre[g] = __builtin_fmaf(whh[g][4 * q], hv.x, pre[g]); pre[g] = __builtin_fmaf(whh[g][4 * q + 1], hv.y, pre[g]);
-                        pre[g] = __builtin_fmaf(whh[g][4 * q + 2], hv.z, pre[g]); pre[g] = __builtin_fmaf(whh[g][4 * q + 3], hv.w, pre[g]);
-                    }
+                    wide_fma4(pre, whh, q, hv);
                     pre[3] = __builtin_fmaf(wo[4 * q], hv.x, pre[3]); pre[3] = __builtin_fmaf(wo[4 * q + 1], hv.y, pre[3]);
                     pre[3] = __builtin_fmaf(wo[4 * q + 2], hv.z, pre[3]); pre[3] = __builtin_fmaf(wo[4 * q + 3], hv.w, pre[3]);
                 }
@@ -101,11 +96,11 @@ __global__ __launch_bounds__(64) void lstm2_fwd_kernel(SeqArgs a) {
                     s[0] = gi; s[64] = gf; s[128] = gg; s[192] = go; s[256] = cn; s[320] = hn;
                 }
                 c = cn; h = hn;
-                hist[tt * kLS + lane] = h;
+                hist[tt * kWS + lane] = h;
                 wave_lds_fence();
             }
             if (lane < len && t0 + lane >= 1) {      // outputs of the chunk's ticks, lane = tick: y(s - 1) = fc_out(h2(s - 1))
-                const float* hr = hist + lane * kLS + 32;
+                const float* hr = hist + lane * kWS + 32;
                 float y0 = pl[L.o_b_out], y1 = pl[L.o_b_out + 1];
                 for (int j = 0; j < H; ++j) {
                     const float hv = hr[j];
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
     const int lane = threadIdx.x & 63, ju = lane & 31, col = lane & 15, quad = lane >> 4;
     const bool l2 = lane >= 32;
     const Lstm2Layout L = lstm2_layout(a.H);
-    const int H = L.H, T = a.T, NT = T + 1, NC = (NT + kLC - 1) / kLC;
+    const int H = L.H, T = a.T, NT = T + 1, NC = (NT + kWC - 1) / kWC;
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* wsup = smem + pad4(L.P);            // [4][64][64]: the gates' block matrices (row j, column k), zero padded
@@ -133,9 +128,9 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
         wsup[i] = idx >= 0 ? pl[idx] : 0.0f;
     }
     float* xb = wsup + 4 * 64 * 64;            // [64][2]  I, Q of the chunk's ticks
-    float* dxb = xb + kLC * 2;                 // [64][2]  dL/dx of the chunk's steps
-    float* dyb = dxb + kLC * 2;                // [64][2]  dL/dy of the chunk's steps
-    float* dgb = dyb + kLC * 2;                // [4][64]  the step's gate gradients, for the broadcast reads
+    float* dxb = xb + kWC * 2;                 // [64][2]  dL/dx of the chunk's steps
+    float* dyb = dxb + kWC * 2;                // [64][2]  dL/dy of the chunk's steps
+    float* dgb = dyb + kWC * 2;                // [4][64]  the step's gate gradients, for the broadcast reads
     float* hs = dgb + 4 * 64;                  // [65][65] row i = h(t0 - 1 + i)
     const bool vo = ju < H;
     float wih[4][2];
@@ -146,12 +141,7 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
     }
     const float wo0 = (vo && l2) ? pl[L.o_w_out + ju] : 0.0f, wo1 = (vo && l2) ? pl[L.o_w_out + H + ju] : 0.0f;
     f32x16 acc[4][4];                          // dW_hh: gate g, the state rotated by 16 r lanes
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[g][r][i] = 0.0f;
+    wide_zero_acc(acc);
     float dwih[4][2], dbs[4] = {0.f, 0.f, 0.f, 0.f}, dwo0 = 0.0f, dwo1 = 0.0f, tb0 = 0.0f, tb1 = 0.0f;
 #pragma unroll
     for (int g = 0; g < 4; ++g) { dwih[g][0] = 0.0f; dwih[g][1] = 0.0f; }
@@ -163,7 +153,7 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
         const float* sv = a.ckpt + (size_t)b * NT * kLNS * 64;
         float dh = 0.0f, dc = 0.0f;
         for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * kLC, len = min(kLC, NT - t0);
+            const int t0 = c * kWC, len = min(kWC, NT - t0);
             wave_lds_fence();
             reinterpret_cast<float2*>(xb)[lane] = t0 + lane < T ? xg[t0 + lane] : make_float2(0.0f, 0.0f);
             float2 dyv = make_float2(0.0f, 0.0f);
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
             reinterpret_cast<float2*>(dyb)[lane] = dyv;
             if constexpr (NW) { tb0 += dyv.x; tb1 += dyv.y; }
             hs[lane] = t0 > 0 ? sv[(size_t)(t0 - 1) * kLNS * 64 + 320 + lane] : 0.0f;
-            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kLS + lane] = sv[(size_t)(t0 + tt) * kLNS * 64 + 320 + lane];
+            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kWS + lane] = sv[(size_t)(t0 + tt) * kLNS * 64 + 320 + lane];
             wave_lds_fence();
             // the chunk's steps in reverse, lane = unit (the next step's record is in flight while this one is worked on)
             float in_, fn_, gn_, on_, cn_, cpn_;
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
                     cpn_ = t0 + tt - 1 > 0 ? s[256 - kLNS * 64] : 0.0f;
                 }
                 const bool active = vo && (l2 ? t0 + tt >= 1 : t0 + tt < T);
-                const float hp = hs[tt * kLS + lane], ht = hs[(tt + 1) * kLS + lane];
+                const float hp = hs[tt * kWS + lane], ht = hs[(tt + 1) * kWS + lane];
                 const float2 d = reinterpret_cast<const float2*>(dyb)[tt];
                 const float dht = __builtin_fmaf(d.x, wo0, __builtin_fmaf(d.y, wo1, dh));      // (layer 1 lanes: wo = 0)
                 if constexpr (NW) { dwo0 = __builtin_fmaf(d.x, ht, dwo0); dwo1 = __builtin_fmaf(d.y, ht, dwo1); }
@@ -251,11 +241,8 @@ __global__ __launch_bounds__(64) void lstm2_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int i = lane; i < L.P + kLossCols; i += 64) prow[i] = 0.0f;
-        __builtin_amdgcn_s_waitcnt(0);
-        wave_lds_fence();
-        for (int o = 32; o > 0; o >>= 1) { tb0 += __shfl_xor(tb0, o); tb1 += __shfl_xor(tb1, o); }
+        float* prow = wide_partial_row(a.partials, L.P + kLossCols, lane);
+        tb0 = wave_sum64(tb0); tb1 = wave_sum64(tb1);
         if (lane == 0) { prow[L.o_b_out] = tb0; prow[L.o_b_out + 1] = tb1; }
         if (vo) {
             if (l2) { prow[L.o_w_out + ju] = dwo0; prow[L.o_w_out + H + ju] = dwo1; }
@@ -288,22 +275,17 @@ bool lstm2_ok(const odpd_model_t* m) {
 }
 int64_t lstm2_param_count(const odpd_model_t* m) { return lstm2_layout(m->hidden).P; }
 int64_t lstm2_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * (T + 1) * kLNS * 64; }
-int lstm2_rows(const odpd_model_t*, int B) { const int cap = 4 * device_cus(); return B < cap ? B : cap; }
+int lstm2_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int lstm2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm2_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)lstm2_fwd_floats(lstm2_layout(m->hidden).P) * sizeof(float);
-    const int grid = lstm2_rows(m, a.B);
-    return a.ckpt ? launch_seq(st, lstm2_fwd_kernel<true>, grid, lds, a) : launch_seq(st, lstm2_fwd_kernel<false>, grid, lds, a);
+    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, lstm2_fwd_kernel<decltype(sv)::value>, lds, a); });
 }
 int lstm2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm2_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
     const size_t lds = (size_t)lstm2_bwd_floats(lstm2_layout(m->hidden).P) * sizeof(float);
-    const int grid = lstm2_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_seq(st, lstm2_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return launch_seq(st, lstm2_bwd_kernel<true, false>, grid, lds, a);
-    return launch_seq(st, lstm2_bwd_kernel<false, true>, grid, lds, a);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return wide_launch(st, lstm2_bwd_kernel<decltype(nw)::value, decltype(dx)::value>, lds, a); });
 }
 
 }  // namespace odpd

@@ -1,10 +1,9 @@
 // odpd_f4s16.h — what the float 16-sequences-per-wave kernels of pgjanet, bojanet, apnrru, dvrjanet and mcldnn have in common (janet_s16.hip,
 // bojanet_s16.hip, apnrru_s16.hip, dvrjanet_s16.hip, mcldnn.hip): the weight-table build, the frame chunk with a halo of bojanet's and
-// apnrru's FIR banks, the backward epilogue's sum over the waves, and the host side's launch shape and dispatch.  The cells, the block
-// functions and the kernels' own loops stay in their files (docs/design/f4_backbones.md).
+// apnrru's FIR banks, the backward epilogue's sum over the waves, and the host side's launch shape (the backward's dispatch,
+// s16_bwd_dispatch, is in odpd_host.h).  The cells, the block functions and the kernels' own loops stay in their files
+// (docs/design/f4_backbones.md).
 #pragma once
-#include <type_traits>
-
 #include "odpd_s16.h"
 
 namespace odpd {
@@ -87,15 +86,6 @@ static inline LaunchShape s16_fwd_shape(int ngroups) { return s16_group_shape(ng
 // (either knob at 0 keeps it on the 16-sequences-per-wave kernel)
 static inline bool gp_eval_fits(const SeqArgs& a, int mode) {
     return mode == 1 && !a.ckpt && a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0;
-}
-// the backward's three instantiations: launch(NW, DX) with weight gradients and dL/dx, weight gradients alone, dL/dx alone
-template <typename F>
-static inline int s16_bwd_dispatch(const SeqArgs& a, F launch) {
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    if (nw && dx) return launch(std::true_type{}, std::true_type{});
-    if (nw) return launch(std::true_type{}, std::false_type{});
-    return launch(std::false_type{}, std::true_type{});
 }
 
 }  // namespace odpd

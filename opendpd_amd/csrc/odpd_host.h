@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/opendpd_hip.h"
 #include "odpd_device.h"
 
@@ -175,6 +177,17 @@ struct SeqArgs {
     const float* h0;
     float* dh0;
 };
+
+// the three instantiations of a sequence backward (the 16-sequences-per-wave kernels of odpd_f4s16.h, the lane-per-unit ones of odpd_wide.h):
+// launch(NW, DX) with weight gradients and dL/dx, weight gradients alone, dL/dx alone
+template <typename F>
+static inline int s16_bwd_dispatch(const SeqArgs& a, F launch) {
+    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
+    if (!nw && !dx) return ODPD_EINVAL;
+    if (nw && dx) return launch(std::true_type{}, std::true_type{});
+    if (nw) return launch(std::true_type{}, std::false_type{});
+    return launch(std::false_type{}, std::true_type{});
+}
 
 // one run of a lockstep sweep (K independent runs of one model shape advancing together: odpd_train_epoch_sweep, odpd_backbone_fwd_sweep);
 // the table lives in device memory, a sweep kernel's workgroup picks its entry by blockIdx.x / G

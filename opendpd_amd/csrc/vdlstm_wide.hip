@@ -10,12 +10,11 @@
 //             streams dL/d(a, cos, sin) are accumulated per SAMPLE in LDS over the whole frame and turned into dL/d(I, Q) at the end of the
 //             sequence (so dL/dx needs 3 T floats of LDS: frames up to ~5 000 samples; longer ones are refused for that mode).
 // Per-step records (i, f, g, o, c, h) in HBM: B x T x 6 x 64 floats.
-#include "odpd_seq.h"
+#include "odpd_wide.h"
 
 namespace odpd {
 namespace {
-constexpr int kVC = 64, kVS = 65, kVNS = 6, kVW = 68;      // chunk, row stride, record slots, window array length (3 halo + 64 + pad)
-constexpr int kVHs = ((kVC + 1) * kVS + 3) & ~3;
+constexpr int kVNS = 6, kVW = 68;      // record slots, window array length (3 halo + 64 + pad)
 
 __device__ __forceinline__ void vdw_elem(float2 xv, float& a, float& cw, float& sw) {
     const float a2 = __builtin_fmaf(xv.x, xv.x, xv.y * xv.y);
@@ -37,9 +36,9 @@ __device__ __forceinline__ void vdw_stage(float* av, float* cv, float* sn, const
         }
     }
 }
-__host__ __device__ inline int vdw_fwd_floats(int P) { return pad4(P) + 3 * kVW + 64 + kVC * kVS + 64 * kVS; }
+__host__ __device__ inline int vdw_fwd_floats(int P) { return pad4(P) + 3 * kVW + 64 + kWC * kWS + 64 * kWS; }
 __host__ __device__ inline int vdw_bwd_floats(int P, int T, bool dx) {
-    return pad4(P) + 3 * kVW + kVC * 2 + kVC * 8 + 4 * 64 + kVHs + kVC * kVS + (dx ? 3 * ((T + 3) & ~3) : 0);
+    return pad4(P) + 3 * kVW + kWC * 2 + kWC * 8 + 4 * 64 + kWHs + kWC * kWS + (dx ? 3 * ((T + 3) & ~3) : 0);
 }
 
 template <bool SAVE>
@@ -55,10 +54,10 @@ __global__ __launch_bounds__(64) void wide_vdlstm_fwd_kernel(SeqArgs a) {
     float* sn = cv + kVW;
     float* hb = sn + kVW;                      // [64]: the state, for the broadcast reads
     float* hist = hb + 64;                     // [64][65]: h of the chunk's steps
-    float* wop = hist + kVC * kVS;             // [64][65]: gate o's W_hh rows, zero padded
+    float* wop = hist + kWC * kWS;             // [64][65]: gate o's W_hh rows, zero padded
     const bool vo = lane < H;
-    for (int i = lane; i < 64 * kVS; i += 64) {
-        const int j = i / kVS, k = i % kVS;
+    for (int i = lane; i < 64 * kWS; i += 64) {
+        const int j = i / kWS, k = i % kWS;
         wop[i] = (j < H && k < H) ? pl[L.o_w_hh + (3 * H + j) * H + k] : 0.0f;
     }
     float whh[3][64], wih[4][4], bg[4];
@@ -78,8 +77,8 @@ __global__ __launch_bounds__(64) void wide_vdlstm_fwd_kernel(SeqArgs a) {
         float2* yg = reinterpret_cast<float2*>(a.y) + (size_t)b * T;
         float* sv = SAVE ? a.ckpt + (size_t)b * T * kVNS * 64 : nullptr;
         float h = 0.0f, c = 0.0f;
-        for (int t0 = 0; t0 < T; t0 += kVC) {
-            const int len = min(kVC, T - t0);
+        for (int t0 = 0; t0 < T; t0 += kWC) {
+            const int len = min(kWC, T - t0);
             wave_lds_fence();
             vdw_stage(av, cv, sn, xg, t0, T, lane);
             wave_lds_fence();
@@ -94,15 +93,11 @@ __global__ __launch_bounds__(64) void wide_vdlstm_fwd_kernel(SeqArgs a) {
                     for (int k = 0; k < 4; ++k) pre[g] = __builtin_fmaf(wih[g][k], av[tt + k], pre[g]);      // |x| of times t - 3 .. t
                 }
                 const float4* hb4 = reinterpret_cast<const float4*>(hb);
-                const float* wo = wop + lane * kVS;
+                const float* wo = wop + lane * kWS;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const float4 hv = hb4[q];
-#pragma unroll
-                    for (int g = 0; g < 3; ++g) {
-                        pre[g] = __builtin_fmaf(whh[g][4 * q], hv.x, pre[g]); pre[g] = __builtin_fmaf(whh[g][4 * q + 1], hv.y, pre[g]);
-                        pre[g] = __builtin_fmaf(whh[g][4 * q + 2], hv.z, pre[g]); pre[g] = __builtin_fmaf(whh[g][4 * q + 3], hv.w, pre[g]);
-                    }
+                    wide_fma4(pre, whh, q, hv);
                     pre[3] = __builtin_fmaf(wo[4 * q], hv.x, pre[3]); pre[3] = __builtin_fmaf(wo[4 * q + 1], hv.y, pre[3]);
                     pre[3] = __builtin_fmaf(wo[4 * q + 2], hv.z, pre[3]); pre[3] = __builtin_fmaf(wo[4 * q + 3], hv.w, pre[3]);
                 }
@@ -114,11 +109,11 @@ __global__ __launch_bounds__(64) void wide_vdlstm_fwd_kernel(SeqArgs a) {
                     s[0] = gi; s[64] = gf; s[128] = gg; s[192] = go; s[256] = cn; s[320] = hn;
                 }
                 c = cn; h = hn;
-                hist[tt * kVS + lane] = h;
+                hist[tt * kWS + lane] = h;
                 wave_lds_fence();
             }
             if (lane < len) {      // the chunk's outputs, lane = time step
-                const float* hr = hist + lane * kVS;
+                const float* hr = hist + lane * kWS;
                 float l1[4], l2[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { l1[k] = pl[L.o_b_l1 + k]; l2[k] = pl[L.o_b_l2 + k]; }
@@ -148,18 +143,18 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
     const LstmLayout L = lstm_layout(a.H, 1);
-    const int H = L.H, T = a.T, NC = (T + kVC - 1) / kVC, Tp = (T + 3) & ~3;
+    const int H = L.H, T = a.T, NC = (T + kWC - 1) / kWC, Tp = (T + 3) & ~3;
     float* pl = smem;
     stage_params(pl, a.params, L.P);
     float* av = smem + pad4(L.P);
     float* cv = av + kVW;
     float* sn = cv + kVW;
     float* dyb = sn + kVW;                     // [64][2]  dL/dy of the chunk's steps
-    float* dlb = dyb + kVC * 2;                // [64][8]  dL/d lambda_1[0..3], lambda_2[0..3] of the chunk's steps
-    float* dgb = dlb + kVC * 8;                // [4][64]  the step's gate gradients, for the broadcast reads
+    float* dlb = dyb + kWC * 2;                // [64][8]  dL/d lambda_1[0..3], lambda_2[0..3] of the chunk's steps
+    float* dgb = dlb + kWC * 8;                // [4][64]  the step's gate gradients, for the broadcast reads
     float* hs = dgb + 4 * 64;                  // [65][65] row i = h(t0 - 1 + i)
-    float* x1 = hs + kVHs;                     // [64][65] the head's dL/dh of the chunk's steps
-    float* gacc = x1 + kVC * kVS;              // DX: [3][Tp] dL/d(a, cos, sin) per sample of the frame
+    float* x1 = hs + kWHs;                     // [64][65] the head's dL/dh of the chunk's steps
+    float* gacc = x1 + kWC * kWS;              // DX: [3][Tp] dL/d(a, cos, sin) per sample of the frame
     const bool vo = lane < H;
     float wih[4][4];
 #pragma unroll
@@ -167,12 +162,7 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) wih[g][k] = vo ? pl[L.o_w_ih + (g * H + lane) * 4 + k] : 0.0f;
     f32x16 acc[4][4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[g][r][i] = 0.0f;
+    wide_zero_acc(acc);
     float dwih[4][4], dbs[4] = {0.f, 0.f, 0.f, 0.f}, dwl[8], tacc[26];      // per unit: W_ih rows, gate biases, fc_lambda columns; per time lane: fc_out (16 + 2), fc_lambda biases (8)
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -193,20 +183,20 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
             for (int i = lane; i < 3 * Tp; i += 64) gacc[i] = 0.0f;
         }
         for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * kVC, len = min(kVC, T - t0);
+            const int t0 = c * kWC, len = min(kWC, T - t0);
             wave_lds_fence();
             vdw_stage(av, cv, sn, xg, t0, T, lane);
             float2 dyv = make_float2(0.0f, 0.0f);
             if (lane < len) dyv = dyg[t0 + lane];
             reinterpret_cast<float2*>(dyb)[lane] = dyv;
             hs[lane] = t0 > 0 ? sv[(size_t)(t0 - 1) * kVNS * 64 + 320 + lane] : 0.0f;
-            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kVS + lane] = sv[(size_t)(t0 + tt) * kVNS * 64 + 320 + lane];
+            for (int tt = 0; tt < len; ++tt) hs[(tt + 1) * kWS + lane] = sv[(size_t)(t0 + tt) * kVNS * 64 + 320 + lane];
             wave_lds_fence();
             // ---- the head's gradients of the chunk, lane = time step ----
             {
                 float dl[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if (lane < len) {
-                    const float* hr = hs + (lane + 1) * kVS;
+                    const float* hr = hs + (lane + 1) * kWS;
                     float l1[4], l2[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) { l1[k] = pl[L.o_b_l1 + k]; l2[k] = pl[L.o_b_l2 + k]; }
@@ -247,13 +237,13 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) v = __builtin_fmaf(dl[k], pl[L.o_w_l1 + k * H + j], __builtin_fmaf(dl[4 + k], pl[L.o_w_l2 + k * H + j], v));
                     }
-                    x1[lane * kVS + j] = v;
+                    x1[lane * kWS + j] = v;
                 }
             }
             wave_lds_fence();
             if constexpr (NW) {      // the fc_lambda rows of this lane's unit over the chunk
                 for (int tt = 0; tt < len; ++tt) {
-                    const float ht = hs[(tt + 1) * kVS + lane];
+                    const float ht = hs[(tt + 1) * kWS + lane];
                     const float4 d0 = reinterpret_cast<const float4*>(dlb)[2 * tt], d1 = reinterpret_cast<const float4*>(dlb)[2 * tt + 1];
                     dwl[0] = __builtin_fmaf(d0.x, ht, dwl[0]); dwl[1] = __builtin_fmaf(d0.y, ht, dwl[1]); dwl[2] = __builtin_fmaf(d0.z, ht, dwl[2]);
                     dwl[3] = __builtin_fmaf(d0.w, ht, dwl[3]); dwl[4] = __builtin_fmaf(d1.x, ht, dwl[4]); dwl[5] = __builtin_fmaf(d1.y, ht, dwl[5]);
@@ -274,8 +264,8 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
                     in_ = s[0]; fn_ = s[64]; gn_ = s[128]; on_ = s[192]; cn_ = s[256];
                     cpn_ = t0 + tt - 1 > 0 ? s[256 - kVNS * 64] : 0.0f;
                 }
-                const float hp = hs[tt * kVS + lane];
-                const float dht = dh + x1[tt * kVS + lane];
+                const float hp = hs[tt * kWS + lane];
+                const float dht = dh + x1[tt * kWS + lane];
                 const float tc = tanhf_(ct);
                 const float dct = __builtin_fmaf(dht * go, __builtin_fmaf(-tc, tc, 1.0f), dc);      // dL/dc(t)
                 const float dpi = vo ? (dct * gg) * (gi * (1.0f - gi)) : 0.0f;
@@ -346,13 +336,8 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
         wave_lds_fence();
     }
     if constexpr (NW) {
-        float* prow = a.partials + (size_t)blockIdx.x * (L.P + kLossCols);
-        for (int i = lane; i < L.P + kLossCols; i += 64) prow[i] = 0.0f;
-        __builtin_amdgcn_s_waitcnt(0);
-        wave_lds_fence();
-#pragma unroll
-        for (int i = 0; i < 26; ++i)
-            for (int o = 32; o > 0; o >>= 1) tacc[i] += __shfl_xor(tacc[i], o);
+        float* prow = wide_partial_row(a.partials, L.P + kLossCols, lane);
+        wide_sum_lanes(tacc);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) prow[L.o_w_out + k] = tacc[k];
@@ -383,34 +368,23 @@ __global__ __launch_bounds__(64) void wide_vdlstm_bwd_kernel(SeqArgs a) {
                     }
     }
 }
-
-template <typename K>
-int vdw_launch(hipStream_t st, K k, int grid, size_t lds, const SeqArgs& a) {
-    if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    return launch_seq(st, k, grid, lds, a);
-}
 }  // namespace
 
 // float vdlstm of 33 .. 64 hidden units
 bool vdlstm_wide_ok(const odpd_model_t* m) { return m->backbone == ODPD_VDLSTM && m->bits_w == 0 && m->hidden > 32 && m->hidden <= 64; }
 int64_t vdlstm_wide_ckpt_floats(const odpd_model_t*, int B, int T) { return (int64_t)B * T * kVNS * 64; }
-int vdlstm_wide_rows(const odpd_model_t*, int B) { const int cap = 4 * device_cus(); return B < cap ? B : cap; }
+int vdlstm_wide_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int vdlstm_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!vdlstm_wide_ok(m)) return ODPD_EUNSUPPORTED;
     if (a.T < 3) return ODPD_EINVAL;      // the circular pad takes the frame's own last three samples (vdlstm.py:66-74)
     const size_t lds = (size_t)vdw_fwd_floats(lstm_layout(m->hidden, 1).P) * sizeof(float);
-    const int grid = vdlstm_wide_rows(m, a.B);
-    return a.ckpt ? vdw_launch(st, wide_vdlstm_fwd_kernel<true>, grid, lds, a) : vdw_launch(st, wide_vdlstm_fwd_kernel<false>, grid, lds, a);
+    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, wide_vdlstm_fwd_kernel<decltype(sv)::value>, lds, a); });
 }
 int vdlstm_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!vdlstm_wide_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt || a.T < 3) return ODPD_EINVAL;
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    const size_t lds = (size_t)vdw_bwd_floats(lstm_layout(m->hidden, 1).P, a.T, dx) * sizeof(float);
-    const int grid = vdlstm_wide_rows(m, a.B);
-    if (nw && dx) return vdw_launch(st, wide_vdlstm_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return vdw_launch(st, wide_vdlstm_bwd_kernel<true, false>, grid, lds, a);
-    return vdw_launch(st, wide_vdlstm_bwd_kernel<false, true>, grid, lds, a);
+    const size_t lds = (size_t)vdw_bwd_floats(lstm_layout(m->hidden, 1).P, a.T, a.dx != nullptr) * sizeof(float);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return wide_launch(st, wide_vdlstm_bwd_kernel<decltype(nw)::value, decltype(dx)::value>, lds, a); });
 }
 
 }  // namespace odpd
