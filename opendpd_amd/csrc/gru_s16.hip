@@ -482,7 +482,7 @@ template <int FM, bool DG, int OCC, bool PACK, bool NW = true, bool DX = false>
 __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid, const int nbl) {
     constexpr int F = S16Cfg<FM>::F, NCH = S16Cfg<FM>::NCH, S = kCkptStride;
     constexpr int kGroups = DX ? kS16GroupsDx : kS16Groups;
-    constexpr int kWave = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? kS16Tiles * kTileFloats : 0);
+    constexpr int kWave = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? kS16Tiles * kTileFloats : 0) + kStageRowFloats;
     static_assert(NCH <= 2, "operand tables and dwf accumulators are sized for two K-chunks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
@@ -501,6 +501,9 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
     float2* ts = xs + 16 * kChunkPad;
     float2* dxs = DX ? ts + 16 * kChunkPad : nullptr;
     float* tiles = reinterpret_cast<float*>(ts + (DX ? 2 : 1) * 16 * kChunkPad);
+    unsigned long long* rows = reinterpret_cast<unsigned long long*>(wbase + kWave - kStageRowFloats);   // row offsets of the group (stage_rows)
+    const bool bf16 = a.frames_bf16 != 0;
+    const float2 kFillX = make_float2(0.5f, 0.5f), kFillT = make_float2(0.0f, 0.0f);
     if constexpr (NW)
         for (int i = lane; i < kTileFloats; i += 64) tiles[6 * kTileFloats + i] = 0.0f;   // unused feature columns stay 0
     S16Grad<DG> G;
@@ -511,6 +514,9 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
         const int b0 = grp * 16;
         const bool valid = b0 + n < a.B;
         float4* ck = reinterpret_cast<float4*>(a.ckpt) + (size_t)grp * a.nck * 64 + lane;
+        wave_lds_fence();
+        stage_rows(rows, b0, a.B, a.T, lane, a.frame_idx, a.frame_stride);      // the 21 staging calls of the group (T = 200) read these
+        wave_lds_fence();
         // ---- forward: cell only, checkpoint every S steps ----
         {
             S16Fw<FM> w;
@@ -518,8 +524,10 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
             f32x4 h = {0.f, 0.f, 0.f, 0.f};
             for (int t0 = 0; t0 < a.T; t0 += kChunk) {
                 const int len = min(kChunk, a.T - t0);
+                StagedChunk<1> xc;
+                stage_issue<1>(xc, {a.x}, rows, b0, a.B, t0, len, lane, {kFillX}, bf16);
                 wave_lds_fence();
-                stage_in<16>(xs, a.x, b0, a.B, a.T, t0, len, lane, make_float2(0.5f, 0.5f), a.frame_idx, a.frame_stride, a.frames_bf16 != 0);
+                stage_commit<1>(xc, {xs}, b0, a.B, len, lane, bf16);
                 wave_lds_fence();
                 int tt = 0;
                 for (; tt + S <= len; tt += S) {
@@ -574,10 +582,11 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
                         stage_out<16>(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
                     }
                 }
-                wave_lds_fence();
                 const int len = min(kChunk, a.T - t0);
-                stage_in<16>(xs, a.x, b0, a.B, a.T, t0, len, lane, make_float2(0.5f, 0.5f), a.frame_idx, a.frame_stride, a.frames_bf16 != 0);
-                stage_in<16>(ts, a.target, b0, a.B, a.T, t0, len, lane, make_float2(0.0f, 0.0f), a.frame_idx, a.frame_stride, a.frames_bf16 != 0);
+                StagedChunk<2> xt;      // x and the target: one batch of loads, one wait (no block state is live here)
+                stage_issue<2>(xt, {a.x, a.target}, rows, b0, a.B, t0, len, lane, {kFillX, kFillT}, bf16);
+                wave_lds_fence();
+                stage_commit<2>(xt, {xs, ts}, b0, a.B, len, lane, bf16);
                 wave_lds_fence();
                 cur_chunk = chunk;
             }
@@ -837,7 +846,7 @@ static int s16_param_count(int H, int FM, bool DG) {
     return gru_layout(H, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
 }
 static size_t s16_lds_bytes(int P, int waves) {
-    size_t nbytes = ((size_t)pad4(P) + s16_tab_floats(kS16Groups) + (size_t)waves * kS16WaveFloats) * sizeof(float);
+    size_t nbytes = ((size_t)pad4(P) + s16_tab_floats(kS16Groups) + (size_t)waves * (kS16WaveFloats + kStageRowFloats)) * sizeof(float);
     const size_t red = reduce_scratch_bytes(P, waves);
     return nbytes > red ? nbytes : red;
 }
@@ -880,7 +889,7 @@ static int launch_s16(hipStream_t st, const SeqArgs& a, int P) {
 template <int FM, bool DG, int OCC, bool PACK>
 static int launch_s16_lossdx(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = s16_shape(a.ngroups);
-    const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16GroupsDx) + (size_t)ls.waves * 3 * 2 * 16 * kChunkPad) * sizeof(float);
+    const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16GroupsDx) + (size_t)ls.waves * (3 * 2 * 16 * kChunkPad + kStageRowFloats)) * sizeof(float);
     auto k = gru16_train_kernel<FM, DG, OCC, PACK, false, true>;
     if (int e = allow_big_lds(k, lds)) return e;
     hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);

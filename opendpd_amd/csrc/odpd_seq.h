@@ -69,8 +69,10 @@ __device__ __forceinline__ float2 ld_iq(const float* g, size_t i, bool bf16) {
     return reinterpret_cast<const float2*>(g)[i];
 }
 // `fidx` (nullable): frames are windows of a resident stream, row b starts at sample fidx[b] * fstride; `bf16`: its sample format
-// BATCHED: the loads of one call in two passes (see below) — 2 N more live registers at the call site, so the register-capped two-wave kernels
-// keep the element-at-a-time form, whose exposed latency their partner wave covers
+// BATCHED: the loads of one call in two passes (see below) — 2 N more live registers at the call site.  The element-at-a-time form exposes 2 N
+// dependent round trips per call, and a partner wave does NOT cover them where the waves of a SIMD run the same work in lockstep and reach every
+// chunk boundary together: the fused train kernel of gru_s16.hip stages through stage_rows / stage_issue / stage_commit below instead
+// (profiles/staging.md); the split kernels and the other families still call this form
 template <int SPW, bool BATCHED = false>
 __device__ __forceinline__ void stage_in(float2* lds, const float* g, int b0, int B, int T, int t0, int len, int lane,
                                          float2 fill, const long long* fidx = nullptr, int fstride = 0, bool bf16 = false) {
@@ -133,6 +135,79 @@ __device__ __forceinline__ void stage_in(float2* lds, const float* g, int b0, in
         lds[(e / kChunk) * kChunkPad + e % kChunk] = v[j];
     }
 }
+// -------------------------------------------------------------------------------------------------
+// The same staging in three parts, for a kernel that stages many chunks of the same 16 rows (gru16_train_body: 21 calls per group at T = 200):
+//   stage_rows    once per group: the sample offset of each row's first step into a 128-byte LDS slot of the wave — no frame-index load per chunk
+//   stage_issue   the N loads of every stream of a chunk back to back into registers, nothing waited for (x and the target of a backward chunk
+//                 are ONE batch: one wait for 2 N loads)
+//   stage_commit  registers -> LDS; the first use of the registers is where the wave waits.  (Requesting the forward pass's next chunk a chunk
+//                 ahead measured 0.3 % — inside the run-to-run spread; a block ahead in the backward pass costs 220 B of scratch: neither is done,
+//                 profiles/staging.md)
+// Rows beyond the batch are never dereferenced: their offset is that of row B - 1 (frame index) and their loads stay behind the guard.
+// -------------------------------------------------------------------------------------------------
+constexpr int kStageRowFloats = 32;      // 16 x 64-bit offsets
+template <int NS>
+struct StagedChunk { float2 v[NS][16 * kChunk / 64]; };      // (bf16 storage: the word in .x until stage_commit widens it)
+
+__device__ __forceinline__ void stage_rows(unsigned long long* rows, int b0, int B, int T, int lane, const long long* fidx, int fstride) {
+    if (lane < 16) {
+        unsigned long long r = (unsigned long long)(b0 + lane) * T;
+        if (fidx) r = (unsigned long long)fidx[min(b0 + lane, B - 1)] * fstride;
+        rows[lane] = r;
+    }
+}
+template <int NS>
+__device__ __forceinline__ void stage_issue(StagedChunk<NS>& s, const float* const (&g)[NS], const unsigned long long* rows, int b0, int B, int t0,
+                                            int len, int lane, const float2 (&fill)[NS], bool bf16) {
+    constexpr int N = 16 * kChunk / 64, MS = 64 / kChunk;      // element j of the lane: sequence lane / kChunk + MS j, step lane % kChunk
+    static_assert(64 % kChunk == 0, "a lane keeps its step over its elements");
+    const int tt = lane % kChunk, m0 = lane / kChunk;
+    size_t off[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) off[j] = (size_t)rows[m0 + MS * j] + t0 + tt;
+#ifndef ODPD_NO_BF16_FRAMES
+    if (bf16) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const unsigned* g1 = reinterpret_cast<const unsigned*>(g[k]);
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                s.v[k][j] = fill[k];
+                if (tt < len && b0 + m0 + MS * j < B) s.v[k][j].x = __uint_as_float(g1[off[j]]);
+            }
+        }
+        return;
+    }
+#endif
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const float2* g2 = reinterpret_cast<const float2*>(g[k]);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            s.v[k][j] = fill[k];      // (guard, not `?:`: see stage_in_ch)
+            if (tt < len && b0 + m0 + MS * j < B) s.v[k][j] = g2[off[j]];
+        }
+    }
+}
+template <int NS>
+__device__ __forceinline__ void stage_commit(const StagedChunk<NS>& s, float2* const (&lds)[NS], int b0, int B, int len, int lane, bool bf16) {
+    constexpr int N = 16 * kChunk / 64, MS = 64 / kChunk;
+    const int tt = lane % kChunk, m0 = lane / kChunk;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            float2 v = s.v[k][j];
+#ifndef ODPD_NO_BF16_FRAMES
+            if (bf16 && tt < len && b0 + m0 + MS * j < B) {      // the widening of ld_iq
+                const unsigned w = __float_as_uint(v.x);
+                v = make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u));
+            }
+#endif
+            lds[k][(m0 + MS * j) * kChunkPad + tt] = v;
+        }
+}
+
 template <int SPW>
 __device__ __forceinline__ void stage_out(const float2* lds, float* g, int b0, int B, int T, int t0, int len, int lane) {
     float2* g2 = reinterpret_cast<float2*>(g);
