@@ -605,11 +605,7 @@ extern "C" int odpd_train_fwd_bwd_framed(void* stream, const odpd_model_t* m, in
     return framed_train_launch((hipStream_t)stream, m, a);
 }
 
-// Native epoch loop (replaces the Python `for batch in loader` of net_train, train_funcs.py:28-48, for a single
-// backbone with a fused kernel): every step = fused fwd+loss+bwd on frames addressed inside the resident streams,
-// reduction, clip + AdamW; three launches per step issued back to back from C++, no host synchronisation, no
-// gather kernels, no Python between steps.  losses_out[i] = mean loss of batch i (device).
-// opt_kind < 0: AdamW with the given hyper-parameters; otherwise an enum odpd_optimizer kind with project.py's own
+// rank `rank` of `world` takes items [lo, hi) of n: contiguous shares, the first n % world ranks one item more
 extern "C" void odpd_shard_range(int64_t n, int rank, int world, int64_t* lo, int64_t* hi) {
     const int64_t base = n / world, rem = n % world;
     *lo = rank * base + (rank < rem ? rank : rem);
@@ -640,107 +636,9 @@ extern "C" int odpd_clip_optim_step_dp(void* stream, void* comm, int opt_kind, i
     return dp_clip_step((hipStream_t)stream, comm, opt_kind < 0 ? -1 : opt_kind, P, params, grad, state1, state2, step, lr, beta1, beta2, eps,
                         weight_decay, max_norm, norm_out, nullptr, 0.0f, skip);
 }
-// comm != NULL: every global batch sharded over the communicator's ranks, one all-reduce of grad[0 .. P+4) per step
-static int train_epoch_impl(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, float* params, float* grad,
-                            float* state1, float* state2, int64_t first_step, int opt_kind, double lr, double beta1, double beta2, double eps,
-                            double weight_decay, double max_norm, float* partials, float* workspace, float* losses_out, void* comm = nullptr) {
-    if (!model_ok(m) || !fr || !fr->x_stream || !fr->y_stream || !fr->order || fr->n_frames <= 0 || fr->frame_length <= 0 ||
-        fr->stride <= 0 || batch <= 0 || !params || !grad || !state1 || !state2 || !partials || !losses_out || first_step <= 0)
-        return ODPD_EINVAL;
-    const int T = fr->frame_length;
-    if (!frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;
-    const int rank = comm ? comm_rank(comm) : 0, world = comm ? comm_world(comm) : 1;
-    {   // every (shard of a) batch of the epoch — the full ones and the tail — must have a frame-reading fused kernel
-        const int64_t full = fr->n_frames < batch ? fr->n_frames : batch, tail = fr->n_frames % batch;
-        for (int64_t gb : {full, tail}) {
-            if (!gb) continue;
-            int64_t lo, hi;
-            odpd_shard_range(gb, rank, world, &lo, &hi);
-            if (hi > lo && !framed_train_ok_shape(m, (int)(hi - lo), T)) return ODPD_EUNSUPPORTED;
-        }
-    }
-    const int64_t P = odpd_param_count(m);
-    hipStream_t st = (hipStream_t)stream;
-    int64_t step = first_step;
-    for (int64_t f0 = 0, i = 0; f0 < fr->n_frames; f0 += batch, ++i, ++step) {
-        const int64_t GB = (fr->n_frames - f0) < batch ? (fr->n_frames - f0) : batch;      // the global batch
-        int64_t lo, hi;
-        odpd_shard_range(GB, rank, world, &lo, &hi);
-        const int B = (int)(hi - lo);                                                       // this rank's frames of it
-        const int64_t count = GB * T * 2;                                                   // loss mean over the GLOBAL batch
-        const float inv_count = (float)(1.0 / (double)count);
-        int rc;
-        if (B > 0) {
-            const int64_t rows = odpd_partial_rows(m, B, T, 1);
-            if (rows <= 0) return rows < 0 ? (int)rows : ODPD_EUNSUPPORTED;
-            SeqArgs a = make_args(m, B, T);
-            a.params = params; a.x = fr->x_stream; a.target = fr->y_stream; a.partials = partials; a.ckpt = workspace;
-            a.frame_idx = (const long long*)(fr->order + f0 + lo); a.frame_stride = fr->stride;
-            a.frames_bf16 = fr->sample_format == ODPD_SAMPLES_BF16;
-            a.inv_count = inv_count; a.loss_kind = loss_kind;
-            rc = framed_train_launch(st, m, a);
-            if (rc) return rc;
-            rc = odpd_reduce_partials(stream, rows, P, partials, grad, 0);
-            if (rc) return rc;
-        } else {      // an empty shard of a short last batch: zeros into the sum
-            rc = (int)hipMemsetAsync(grad, 0, (size_t)(P + kLossCols) * sizeof(float), st);
-            if (rc) return rc;
-        }
-        rc = dp_clip_step(st, comm, opt_kind, P, params, grad, state1, state2, step, lr, beta1, beta2, eps, weight_decay, max_norm, nullptr,
-                          losses_out + i, inv_count, nullptr);
-        if (rc) return rc;
-    }
-    return 0;
-}
-// ---- native epoch loop of train_dpd at the reference's batch sizes: the one-launch cascade step (gru_cascade.hip) on frames read in place ----
-// comm != NULL: every global batch sharded over the communicator's ranks (as train_epoch_impl), one all-reduce of grad[0 .. P+4) per step
-extern "C" int odpd_train_epoch_cascade(void* stream, void* comm, const odpd_model_t* dpd, const odpd_model_t* pa, int loss_kind,
-                                        const odpd_frames_t* fr, int batch, int opt_kind, float* dpd_params, const float* pa_params, float* grad,
-                                        float* state1, float* state2, int64_t first_step, double lr, double beta1, double beta2, double eps,
-                                        double weight_decay, double max_norm, const unsigned char* skip, float* partials, double* dpd_stats,
-                                        float* losses_out) {
-    if (!model_ok(dpd) || !model_ok(pa) || !fr || !fr->x_stream || !fr->y_stream || !fr->order || fr->n_frames <= 0 || fr->frame_length <= 0 ||
-        fr->stride <= 0 || batch <= 0 || !dpd_params || !pa_params || !grad || !state1 || !state2 || !partials || !losses_out || first_step <= 0 ||
-        opt_kind > ODPD_OPT_RMSPROP)
-        return ODPD_EINVAL;
-    if (fr->sample_format != ODPD_SAMPLES_F32) return ODPD_EUNSUPPORTED;
-    const int T = fr->frame_length;
-    const int rank = comm ? comm_rank(comm) : 0, world = comm ? comm_world(comm) : 1;
-    const int64_t full = fr->n_frames < batch ? fr->n_frames : batch, tail = fr->n_frames % batch;
-    for (int64_t gb : {full, tail}) {
-        if (!gb) continue;
-        int64_t lo, hi;
-        odpd_shard_range(gb, rank, world, &lo, &hi);
-        if (hi > lo && odpd_cascade_rows(dpd, pa, (int)(hi - lo), T) <= 0) return ODPD_EUNSUPPORTED;
-    }
-    const int64_t P = odpd_param_count(dpd);
-    hipStream_t st = (hipStream_t)stream;
-    int64_t step = first_step;
-    for (int64_t f0 = 0, i = 0; f0 < fr->n_frames; f0 += batch, ++i, ++step) {
-        const int64_t GB = (fr->n_frames - f0) < batch ? (fr->n_frames - f0) : batch;      // the global batch
-        int64_t lo, hi;
-        odpd_shard_range(GB, rank, world, &lo, &hi);
-        const int B = (int)(hi - lo);                                                       // this rank's frames of it
-        const int64_t count = GB * T * 2;                                                   // loss mean over the GLOBAL batch
-        const float inv_count = (float)(1.0 / (double)count);
-        int rc;
-        if (B > 0) {
-            rc = odpd_cascade_fwd_bwd(stream, dpd, pa, loss_kind, B, T, count, dpd_params, pa_params, fr->x_stream, fr->y_stream,
-                                      fr->order + f0 + lo, fr->stride, partials, dpd_stats);
-            if (rc) return rc;
-            rc = odpd_reduce_partials(stream, odpd_cascade_rows(dpd, pa, B, T), P, partials, grad, 0);
-            if (rc) return rc;
-        } else {      // an empty shard of a short last batch: zeros into the sum
-            rc = (int)hipMemsetAsync(grad, 0, (size_t)(P + kLossCols) * sizeof(float), st);
-            if (rc) return rc;
-        }
-        rc = dp_clip_step(st, comm, opt_kind, P, dpd_params, grad, state1, state2, step, lr, beta1, beta2, eps, weight_decay, max_norm, nullptr,
-                          losses_out + i, inv_count, skip);
-        if (rc) return rc;
-    }
-    return 0;
-}
-// ---- native epoch loop for backbones without a fused train kernel at this shape (the split chain of train_funcs.py:33-44) ----------
+
+// ---- the native epoch loops: every step of an epoch issued back to back from C++, no host synchronisation, no Python between steps.  One driver:
+// epoch_frames_ok, epoch_shapes_served (an epoch that will be refused launches nothing), epoch_steps (batch and shard arithmetic), run_epoch ----
 namespace {
 // frames order[f0 .. f0 + B) of the two streams gathered into (B,T,2) tensors (what IQFrameDataset + the DataLoader's collate build)
 __global__ void gather_frames_kernel(const float2* __restrict__ xs, const float2* __restrict__ ys, const long long* __restrict__ order,
@@ -754,56 +652,191 @@ __global__ void gather_frames_kernel(const float2* __restrict__ xs, const float2
 }
 // grad[P] = mean loss * count: the loss travels with the gradient (column P) exactly as in the Python-driven step
 __global__ void loss_sum_kernel(float* grad_p, const float* loss_mean, float count) { grad_p[0] = loss_mean[0] * count; }
+// an odpd_frames_t as an epoch loop takes it.  need_order: the loop visits the frames in fr->order (the sweeps take one order per run)
+inline bool epoch_frames_ok(const odpd_frames_t* fr, int batch, bool need_order) {
+    return fr && fr->x_stream && fr->y_stream && (fr->order || !need_order) && fr->n_frames > 0 && fr->frame_length > 0 && fr->stride > 0 && batch > 0;
+}
+struct EpochStep {
+    int64_t i, f0;         // index of the step; position in `order` of the first frame of its global batch
+    int64_t GB, lo, hi;    // size of the global batch (the last one may be short); this rank's frames [lo, hi) of it
+    int B;                 // = hi - lo; 0: an empty shard of a short last batch
+    int64_t count;         // GB * T * 2: the loss is a mean over the GLOBAL batch ...
+    float inv_count;       // ... and its gradient is scaled by 1 / count
+};
+// body(step) for every step of an epoch in global batches of `batch`, each sharded over `world` ranks (one process: 0 of 1); a non-zero return ends it
+template <class Body>
+inline int epoch_steps(const odpd_frames_t* fr, int batch, int rank, int world, Body&& body) {
+    const int64_t n = fr->n_frames;
+    EpochStep s;
+    for (s.f0 = 0, s.i = 0; s.f0 < n; s.f0 += batch, ++s.i) {
+        s.GB = (n - s.f0) < batch ? (n - s.f0) : batch;
+        odpd_shard_range(s.GB, rank, world, &s.lo, &s.hi);
+        s.B = (int)(s.hi - s.lo);
+        s.count = s.GB * fr->frame_length * 2;
+        s.inv_count = (float)(1.0 / (double)s.count);
+        if (int rc = body(s)) return rc;
+    }
+    return 0;
+}
+// every (shard of a) batch of the epoch — the full ones and the tail — must be served: served(B) for this rank's share of both
+template <class Served>
+inline bool epoch_shapes_served(const odpd_frames_t* fr, int batch, int rank, int world, Served&& served) {
+    const int64_t full = fr->n_frames < batch ? fr->n_frames : batch, tail = fr->n_frames % batch;
+    for (int64_t gb : {full, tail}) {
+        if (!gb) continue;
+        int64_t lo, hi;
+        odpd_shard_range(gb, rank, world, &lo, &hi);
+        if (hi > lo && !served((int)(hi - lo))) return false;
+    }
+    return true;
+}
+// how a step ends: the rows its launches left in `partials` summed into grad[0 .. P+4), then dp_clip_step (whose arguments these are)
+struct StepTail {
+    void* comm;                   // NULL: one process
+    int opt_kind; int64_t P;
+    float *params, *grad, *state1, *state2;
+    double lr, beta1, beta2, eps, weight_decay, max_norm;
+    const unsigned char* skip;    // NULL: every parameter is stepped
+    float* partials;
+    const float* loss_mean;       // the split chain: its loss kernel leaves the batch's mean loss here, not in column P of the rows (else NULL)
+};
+// One epoch.  Refused up front (ODPD_EUNSUPPORTED) unless served(B) holds for every batch shape of it; then per step launch(step, &rows) —
+// forward + loss + backward of this rank's frames, `rows` partial-gradient rows — and the step's tail; losses_out[i] = mean loss of batch i.
+template <class Served, class Launch>
+inline int run_epoch(hipStream_t st, const odpd_frames_t* fr, int batch, int64_t first_step, const StepTail& t, float* losses_out,
+                     Served&& served, Launch&& launch) {
+    const int rank = t.comm ? comm_rank(t.comm) : 0, world = t.comm ? comm_world(t.comm) : 1;
+    if (!epoch_shapes_served(fr, batch, rank, world, served)) return ODPD_EUNSUPPORTED;
+    return epoch_steps(fr, batch, rank, world, [&](const EpochStep& s) -> int {
+        if (s.B > 0) {
+            int64_t rows = 0;
+            if (int rc = launch(s, &rows)) return rc;
+            if (int rc = odpd_reduce_partials(st, rows, t.P, t.partials, t.grad, 0)) return rc;
+            if (t.loss_mean) hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1), 0, st, t.grad + t.P, t.loss_mean, (float)s.count);
+        } else if (int rc = (int)hipMemsetAsync(t.grad, 0, (size_t)(t.P + kLossCols) * sizeof(float), st)) {
+            return rc;      // (an empty shard of a short last batch: zeros into the sum)
+        }
+        return dp_clip_step(st, t.comm, t.opt_kind, t.P, t.params, t.grad, t.state1, t.state2, first_step + s.i, t.lr, t.beta1, t.beta2, t.eps,
+                            t.weight_decay, t.max_norm, nullptr, losses_out + s.i, s.inv_count, t.skip);
+    });
+}
 }  // namespace
+// Native epoch loop (replaces the Python `for batch in loader` of net_train, train_funcs.py:28-48, for a single
+// backbone with a fused kernel): every step = fused fwd+loss+bwd on frames addressed inside the resident streams,
+// reduction, clip + AdamW; three launches per step.  losses_out[i] = mean loss of batch i (device).
+// opt_kind < 0: AdamW with the given hyper-parameters; otherwise an enum odpd_optimizer kind with project.py's own.
+// comm != NULL: every global batch sharded over the communicator's ranks, one all-reduce of grad[0 .. P+4) per step
+static int train_epoch_impl(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, float* params, float* grad,
+                            float* state1, float* state2, int64_t first_step, int opt_kind, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, double max_norm, float* partials, float* workspace, float* losses_out, void* comm = nullptr) {
+    if (!model_ok(m) || !epoch_frames_ok(fr, batch, true) || !params || !grad || !state1 || !state2 || !partials || !losses_out || first_step <= 0)
+        return ODPD_EINVAL;
+    if (!frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;      // (bf16 frames: the float GRU family)
+    const int T = fr->frame_length;
+    const StepTail tail{comm, opt_kind, odpd_param_count(m), params, grad, state1, state2, lr, beta1, beta2, eps, weight_decay, max_norm,
+                        /*skip*/ nullptr, partials, nullptr};
+    return run_epoch((hipStream_t)stream, fr, batch, first_step, tail, losses_out, [&](int B) { return framed_train_ok_shape(m, B, T); },
+                     [&](const EpochStep& s, int64_t* rows) -> int {
+                         *rows = odpd_partial_rows(m, s.B, T, 1);
+                         if (*rows <= 0) return *rows < 0 ? (int)*rows : ODPD_EUNSUPPORTED;
+                         return odpd_train_fwd_bwd_framed(stream, m, loss_kind, fr, s.f0 + s.lo, s.B, s.count, params, partials, workspace);
+                     });
+}
+extern "C" int odpd_train_epoch(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch,
+                                float* params, float* grad, float* exp_avg, float* exp_avg_sq, int64_t first_step, double lr,
+                                double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                float* partials, float* workspace, float* losses_out) {
+    return train_epoch_impl(stream, m, loss_kind, fr, batch, params, grad, exp_avg, exp_avg_sq, first_step, -1, lr, beta1, beta2, eps, weight_decay,
+                            max_norm, partials, workspace, losses_out);
+}
+extern "C" int odpd_train_epoch_dp(void* stream, void* comm, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, int opt_kind,
+                                   float* params, float* grad, float* state1, float* state2, int64_t first_step, double lr, double beta1,
+                                   double beta2, double eps, double weight_decay, double max_norm, float* partials, float* workspace,
+                                   float* losses_out) {
+    if (!comm || opt_kind > ODPD_OPT_RMSPROP) return ODPD_EINVAL;
+    return train_epoch_impl(stream, m, loss_kind, fr, batch, params, grad, state1, state2, first_step, opt_kind < 0 ? -1 : opt_kind, lr, beta1, beta2,
+                            eps, weight_decay, max_norm, partials, workspace, losses_out, comm);
+}
+extern "C" int odpd_train_epoch_opt(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, int opt_kind,
+                                    float* params, float* grad, float* state1, float* state2, int64_t first_step, double lr,
+                                    double max_norm, float* partials, float* workspace, float* losses_out) {
+    if (opt_kind < ODPD_OPT_ADAMW || opt_kind > ODPD_OPT_RMSPROP) return ODPD_EINVAL;
+    return train_epoch_impl(stream, m, loss_kind, fr, batch, params, grad, state1, state2, first_step, opt_kind, lr, 0, 0, 0, 0, max_norm, partials,
+                            workspace, losses_out);
+}
+// ---- native epoch loop of train_dpd at the reference's batch sizes: the one-launch cascade step (gru_cascade.hip) on frames read in place;
+// comm != NULL: sharded as train_epoch_impl ----
+extern "C" int odpd_train_epoch_cascade(void* stream, void* comm, const odpd_model_t* dpd, const odpd_model_t* pa, int loss_kind,
+                                        const odpd_frames_t* fr, int batch, int opt_kind, float* dpd_params, const float* pa_params, float* grad,
+                                        float* state1, float* state2, int64_t first_step, double lr, double beta1, double beta2, double eps,
+                                        double weight_decay, double max_norm, const unsigned char* skip, float* partials, double* dpd_stats,
+                                        float* losses_out) {
+    if (!model_ok(dpd) || !model_ok(pa) || !epoch_frames_ok(fr, batch, true) || !dpd_params || !pa_params || !grad || !state1 || !state2 ||
+        !partials || !losses_out || first_step <= 0 || opt_kind > ODPD_OPT_RMSPROP)
+        return ODPD_EINVAL;
+    if (fr->sample_format != ODPD_SAMPLES_F32) return ODPD_EUNSUPPORTED;
+    const int T = fr->frame_length;
+    const StepTail tail{comm, opt_kind, odpd_param_count(dpd), dpd_params, grad, state1, state2, lr, beta1, beta2, eps, weight_decay, max_norm,
+                        skip, partials, nullptr};
+    return run_epoch((hipStream_t)stream, fr, batch, first_step, tail, losses_out, [&](int B) { return odpd_cascade_rows(dpd, pa, B, T) > 0; },
+                     [&](const EpochStep& s, int64_t* rows) -> int {
+                         *rows = odpd_cascade_rows(dpd, pa, s.B, T);
+                         return odpd_cascade_fwd_bwd(stream, dpd, pa, loss_kind, s.B, T, s.count, dpd_params, pa_params, fr->x_stream, fr->y_stream,
+                                                     fr->order + s.f0 + s.lo, fr->stride, partials, dpd_stats);
+                     });
+}
+// ---- native epoch loop for backbones without a fused train kernel at this shape (the split chain of train_funcs.py:33-44: gather, forward,
+// loss, backward per step); one process, and not the state route ----
 extern "C" int odpd_train_epoch_split(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, int opt_kind,
                                       float* params, float* grad, float* state1, float* state2, int64_t first_step, double lr, double beta1,
                                       double beta2, double eps, double weight_decay, double max_norm, const unsigned char* skip,
                                       float* xbuf, float* tbuf, float* ybuf, float* dybuf, float* ckpt, float* partials, float* loss_scratch,
                                       double* stats, float* losses_out) {
-    if (!model_ok(m) || !fr || !fr->x_stream || !fr->y_stream || !fr->order || fr->n_frames <= 0 || fr->frame_length <= 0 ||
-        fr->stride <= 0 || batch <= 0 || !params || !grad || !state1 || !state2 || !xbuf || !tbuf || !ybuf || !dybuf || !partials ||
-        !loss_scratch || !losses_out || first_step <= 0 || opt_kind > ODPD_OPT_RMSPROP)
+    if (!model_ok(m) || !epoch_frames_ok(fr, batch, true) || !params || !grad || !state1 || !state2 || !xbuf || !tbuf || !ybuf || !dybuf ||
+        !partials || !loss_scratch || !losses_out || first_step <= 0 || opt_kind > ODPD_OPT_RMSPROP)
         return ODPD_EINVAL;
     if (fr->sample_format != ODPD_SAMPLES_F32 || init_state(m)) return ODPD_EUNSUPPORTED;
     const int T = fr->frame_length;
     const int64_t P = odpd_param_count(m);
     if (P <= 0) return P < 0 ? (int)P : ODPD_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    int64_t step = first_step;
-    for (int64_t f0 = 0, i = 0; f0 < fr->n_frames; f0 += batch, ++i, ++step) {
-        const int B = (int)((fr->n_frames - f0) < batch ? (fr->n_frames - f0) : batch);
-        const int64_t rows = odpd_partial_rows(m, B, T, 0), n = (int64_t)B * T * 2;
-        if (rows <= 0) return rows < 0 ? (int)rows : ODPD_EUNSUPPORTED;
-        const long long work = (long long)B * T;
-        const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
-        hipLaunchKernelGGL(gather_frames_kernel, dim3(grid), dim3(256), 0, st, (const float2*)fr->x_stream, (const float2*)fr->y_stream,
-                           (const long long*)(fr->order + f0), fr->stride, B, T, (float2*)xbuf, (float2*)tbuf);
-        int rc = (int)hipGetLastError();
-        if (rc) return rc;
-        rc = odpd_backbone_fwd(stream, m, B, T, params, xbuf, ybuf, ckpt, stats);
-        if (rc) return rc;
-        rc = odpd_loss_fwd_bwd(stream, loss_kind, n, n, ybuf, tbuf, dybuf, loss_scratch);
-        if (rc) return rc;
-        rc = odpd_backbone_bwd(stream, m, B, T, params, xbuf, dybuf, ckpt, partials, nullptr);
-        if (rc) return rc;
-        rc = odpd_reduce_partials(stream, rows, P, partials, grad, 0);
-        if (rc) return rc;
-        hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1), 0, st, grad + P, loss_scratch, (float)n);
-        const float inv = (float)(1.0 / (double)n);
-        rc = opt_kind < 0 ? launch_clip_adamw(st, P, params, grad, state1, state2, step, lr, beta1, beta2, eps, weight_decay, max_norm, nullptr,
-                                              losses_out + i, inv, skip)
-                          : launch_clip_optim(st, opt_kind, P, params, grad, state1, state2, step, lr, max_norm, nullptr, losses_out + i, inv, skip);
-        if (rc) return rc;
-    }
-    return 0;
+    const StepTail tail{/*comm*/ nullptr, opt_kind, P, params, grad, state1, state2, lr, beta1, beta2, eps, weight_decay, max_norm,
+                        skip, partials, /*loss_mean*/ loss_scratch};
+    return run_epoch(st, fr, batch, first_step, tail, losses_out, [&](int B) { return odpd_partial_rows(m, B, T, 0) > 0; },
+                     [&](const EpochStep& s, int64_t* rows) -> int {
+                         *rows = odpd_partial_rows(m, s.B, T, 0);
+                         if (*rows <= 0) return *rows < 0 ? (int)*rows : ODPD_EUNSUPPORTED;
+                         const long long work = (long long)s.B * T;
+                         const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
+                         hipLaunchKernelGGL(gather_frames_kernel, dim3(grid), dim3(256), 0, st, (const float2*)fr->x_stream,
+                                            (const float2*)fr->y_stream, (const long long*)(fr->order + s.f0), fr->stride, s.B, T, (float2*)xbuf,
+                                            (float2*)tbuf);
+                         if (int rc = (int)hipGetLastError()) return rc;
+                         if (int rc = odpd_backbone_fwd(stream, m, s.B, T, params, xbuf, ybuf, ckpt, stats)) return rc;
+                         if (int rc = odpd_loss_fwd_bwd(stream, loss_kind, s.count, s.count, ybuf, tbuf, dybuf, loss_scratch)) return rc;
+                         return odpd_backbone_bwd(stream, m, s.B, T, params, xbuf, dybuf, ckpt, partials, nullptr);
+                     });
 }
 // ---- lockstep sweeps: K independent runs of ONE model shape (the seeds of bash_scripts/train_all_pa.sh:26-57) advance together — per step
-// one fused train launch of K x grid workgroups, one row reduction, one clip + AdamW launch; each run bit-identical to its solo epoch ----
-extern "C" int64_t odpd_sweep_scratch_bytes(int K, int64_t n_steps) {
+// one fused train launch of K x grid workgroups, one row reduction, one clip + AdamW launch; each run bit-identical to its solo epoch.
+// scratch: run table | PA parameter pointers (the cascade sweep only) | K step sizes per step of the epoch ----
+namespace {
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+inline size_t sweep_pa_off(int K) { return align256((size_t)K * sizeof(SweepRun)); }
+inline size_t sweep_ss_off(int K, bool pa_table) { return sweep_pa_off(K) + (pa_table ? align256((size_t)K * sizeof(float*)) : 0); }
+inline int64_t sweep_scratch_bytes(int K, int64_t n_steps, bool pa_table) {
     if (K <= 0 || n_steps < 0) return ODPD_EINVAL;
-    return (int64_t)K * (int64_t)sizeof(SweepRun) + (int64_t)K * n_steps * (int64_t)sizeof(float) + 256;
+    return (int64_t)sweep_ss_off(K, pa_table) + (int64_t)K * n_steps * (int64_t)sizeof(float) + 256;
 }
-static int upload_sweep(hipStream_t st, int K, const odpd_sweep_run_t* runs, double weight_decay, void* scratch, SweepRun** dev_out) {
+// the pointers every run of a training sweep needs, and extra(k) on top of them
+template <class Extra>
+inline bool sweep_runs_ok(int K, const odpd_sweep_run_t* runs, Extra&& extra) {
+    for (int k = 0; k < K; ++k)
+        if (const odpd_sweep_run_t& r = runs[k]; !r.params || !r.grad || !r.exp_avg || !r.exp_avg_sq || !r.partials || !r.losses_out || !r.order || !extra(k))
+            return false;
+    return true;
+}
+inline int upload_sweep(hipStream_t st, int K, const odpd_sweep_run_t* runs, double weight_decay, void* scratch, SweepRun** dev_out) {
     std::vector<SweepRun> h((size_t)K);
     for (int k = 0; k < K; ++k) {
         const odpd_sweep_run_t& r = runs[k];
@@ -814,6 +847,36 @@ static int upload_sweep(hipStream_t st, int K, const odpd_sweep_run_t* runs, dou
     *dev_out = reinterpret_cast<SweepRun*>(scratch);
     return (int)hipMemcpyAsync(scratch, h.data(), (size_t)K * sizeof(SweepRun), hipMemcpyHostToDevice, st);      // (pageable source: staged before the call returns)
 }
+// per-step, per-run step sizes lr_k / (1 - beta1^step) of an epoch, at ss_dev: double arithmetic rounded once, exactly launch_clip_adamw's
+inline int sweep_step_sizes(hipStream_t st, int K, const odpd_sweep_run_t* runs, int64_t n_steps, int64_t first_step, double beta1, float* ss_dev) {
+    std::vector<float> ss((size_t)(K * n_steps));
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const double bc1 = 1.0 - pow(beta1, (double)(first_step + i));
+        for (int k = 0; k < K; ++k) ss[(size_t)(i * K + k)] = (float)(runs[k].lr / bc1);
+    }
+    return (int)hipMemcpyAsync(ss_dev, ss.data(), ss.size() * sizeof(float), hipMemcpyHostToDevice, st);      // (pageable source, as above)
+}
+// One lockstep epoch: the run table, every run's PA parameter pointer (pa_params; NULL: no such table) and the step sizes into `scratch`, then
+// per step launch(step, run table, PA table, &rows) — the K runs' forward + loss + backward — one row reduction, one clip + AdamW launch
+template <class Launch>
+inline int run_sweep_epoch(hipStream_t st, int K, const odpd_sweep_run_t* runs, const float* const* pa_params, const odpd_frames_t* fr, int batch,
+                           int64_t P, int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                           void* scratch, Launch&& launch) {
+    SweepRun* dev = nullptr;
+    if (int rc = upload_sweep(st, K, runs, weight_decay, scratch, &dev)) return rc;
+    const float** pa_dev = reinterpret_cast<const float**>(reinterpret_cast<char*>(scratch) + sweep_pa_off(K));
+    if (pa_params) ODPD_CHECK_HIP(hipMemcpyAsync(pa_dev, pa_params, (size_t)K * sizeof(float*), hipMemcpyHostToDevice, st));      // (pageable source, as above)
+    float* ss_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + sweep_ss_off(K, pa_params != nullptr));
+    if (int rc = sweep_step_sizes(st, K, runs, (fr->n_frames + batch - 1) / batch, first_step, beta1, ss_dev)) return rc;
+    return epoch_steps(fr, batch, 0, 1, [&](const EpochStep& s) -> int {
+        int64_t rows = 0;
+        if (int rc = launch(s, dev, pa_dev, &rows)) return rc;
+        if (int rc = launch_reduce_sweep(st, dev, K, rows, P)) return rc;
+        return launch_clip_adamw_sweep(st, dev, K, P, ss_dev + s.i * K, first_step + s.i, s.i, beta1, beta2, eps, max_norm, s.inv_count);
+    });
+}
+}  // namespace
+extern "C" int64_t odpd_sweep_scratch_bytes(int K, int64_t n_steps) { return sweep_scratch_bytes(K, n_steps, false); }
 extern "C" int odpd_sweep_train_supported(const odpd_model_t* m, int B, int T) {
     return model_ok(m) && family_of(m) == FAM_GRU && !lane_per_unit_model(m) && gru_sweep_train_ok(m, B, T) ? 1 : 0;
 }
@@ -837,104 +900,60 @@ extern "C" int64_t odpd_sweep_workspace_floats(const odpd_model_t* m, int B, int
 extern "C" int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int loss_kind, const odpd_frames_t* fr,
                                       int batch, int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,
                                       int flags, void* scratch) {
-    if (!model_ok(m) || K <= 0 || !runs || !fr || !fr->x_stream || !fr->y_stream || fr->n_frames <= 0 || fr->frame_length <= 0 || fr->stride <= 0 ||
-        batch <= 0 || first_step <= 0 || !scratch)
-        return ODPD_EINVAL;
-    for (int k = 0; k < K; ++k)
-        if (!runs[k].params || !runs[k].grad || !runs[k].exp_avg || !runs[k].exp_avg_sq || !runs[k].partials || !runs[k].losses_out || !runs[k].order)
-            return ODPD_EINVAL;
+    if (!model_ok(m) || K <= 0 || !runs || !epoch_frames_ok(fr, batch, false) || first_step <= 0 || !scratch) return ODPD_EINVAL;
+    if (!sweep_runs_ok(K, runs, [](int) { return true; })) return ODPD_EINVAL;
     const int T = fr->frame_length;
-    const int64_t n = fr->n_frames, n_steps = (n + batch - 1) / batch, tail = n - (n_steps - 1) * batch;
     const bool s16 = (flags & ODPD_SWEEP_S16) != 0;
-    if (family_of(m) != FAM_GRU || lane_per_unit_model(m) || !frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;
-    if (s16) {
+    if (family_of(m) != FAM_GRU || lane_per_unit_model(m) || !frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;      // (bf16 frames: served)
+    if (s16) {      // the 16-sequences-per-wave kernel: any batch shape, checkpoints in every run's workspace
         if (!gru_s16_sweep_ok(m)) return ODPD_EUNSUPPORTED;
         for (int k = 0; k < K; ++k)
             if (!runs[k].workspace) return ODPD_EINVAL;
-    } else if (!gru_sweep_train_ok(m, (int)(n < batch ? n : batch), T) || !gru_sweep_train_ok(m, (int)tail, T)) {
+    } else if (!epoch_shapes_served(fr, batch, 0, 1, [&](int B) { return gru_sweep_train_ok(m, B, T); })) {
         return ODPD_EUNSUPPORTED;
     }
-    const int64_t P = odpd_param_count(m);
     hipStream_t st = (hipStream_t)stream;
-    SweepRun* dev = nullptr;
-    if (int rc = upload_sweep(st, K, runs, weight_decay, scratch, &dev)) return rc;
-    // per-step, per-run step sizes lr_k / (1 - beta1^step): double arithmetic rounded once, exactly launch_clip_adamw's
-    float* ss_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (((size_t)K * sizeof(SweepRun) + 255) & ~(size_t)255));
-    std::vector<float> ss((size_t)(K * n_steps));
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const double bc1 = 1.0 - pow(beta1, (double)(first_step + i));
-        for (int k = 0; k < K; ++k) ss[(size_t)(i * K + k)] = (float)(runs[k].lr / bc1);
-    }
-    ODPD_CHECK_HIP(hipMemcpyAsync(ss_dev, ss.data(), ss.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    for (int64_t f0 = 0, i = 0; f0 < n; f0 += batch, ++i) {
-        const int B = (int)((n - f0) < batch ? (n - f0) : batch);
-        SeqArgs a = make_args(m, B, T);
-        a.x = fr->x_stream; a.target = fr->y_stream; a.frame_stride = fr->stride; a.frames_bf16 = fr->sample_format == ODPD_SAMPLES_BF16;
-        const float inv_count = (float)(1.0 / (double)((int64_t)B * T * 2));
-        a.inv_count = inv_count; a.loss_kind = loss_kind;
-        if (s16) a.nck = num_ckpt(T);
-        if (int rc = s16 ? gru_s16_sweep_train(st, m, a, dev, K, (long long)f0) : gru_sweep_train(st, m, a, dev, K, (long long)f0)) return rc;
-        if (int rc = launch_reduce_sweep(st, dev, K, s16 ? gru_s16_rows(m, B) : gru_sweep_train_rows(m, B, T), P)) return rc;
-        if (int rc = launch_clip_adamw_sweep(st, dev, K, P, ss_dev + i * K, first_step + i, i, beta1, beta2, eps, max_norm, inv_count)) return rc;
-    }
-    return 0;
+    return run_sweep_epoch(st, K, runs, /*pa_params*/ nullptr, fr, batch, odpd_param_count(m), first_step, beta1, beta2, eps, weight_decay, max_norm,
+                           scratch, [&](const EpochStep& s, SweepRun* dev, const float**, int64_t* rows) -> int {
+                               SeqArgs a = make_args(m, s.B, T);
+                               a.x = fr->x_stream; a.target = fr->y_stream; a.frame_stride = fr->stride; a.inv_count = s.inv_count;
+                               a.frames_bf16 = fr->sample_format == ODPD_SAMPLES_BF16; a.loss_kind = loss_kind;
+                               if (s16) a.nck = num_ckpt(T);
+                               *rows = s16 ? gru_s16_rows(m, s.B) : gru_sweep_train_rows(m, s.B, T);
+                               return s16 ? gru_s16_sweep_train(st, m, a, dev, K, (long long)s.f0) : gru_sweep_train(st, m, a, dev, K, (long long)s.f0);
+                           });
 }
 // ---- lockstep train_dpd sweeps (the seeds of bash_scripts/train_all_dpd.sh): K runs of one float (DPD, PA) pair on the one-launch cascade step.
 // The step gives every frame a workgroup with a CU('s LDS) to itself, so at batch 64 one run leaves three quarters of the chip idle: here
-// the launch that fills the chip IS the bit-exact one (workgroups of different runs never interact).  scratch: run table | PA table | step sizes
-static size_t casc_sweep_pa_off(int K) { return ((size_t)K * sizeof(SweepRun) + 255) & ~(size_t)255; }
-static size_t casc_sweep_ss_off(int K) { return casc_sweep_pa_off(K) + (((size_t)K * sizeof(float*) + 255) & ~(size_t)255); }
+// the launch that fills the chip IS the bit-exact one (workgroups of different runs never interact) ----
 extern "C" int odpd_sweep_cascade_supported(const odpd_model_t* dpd, const odpd_model_t* pa, int B, int T) {
     if (!dpd || !pa || !model_ok(dpd) || !model_ok(pa) || dpd->bits_w != 0) return 0;
     if (family_of(dpd) == FAM_QAT) return 0;
     return odpd_cascade_rows(dpd, pa, B, T) > 0 ? 1 : 0;
 }
-extern "C" int64_t odpd_sweep_cascade_scratch_bytes(int K, int64_t n_steps) {
-    if (K <= 0 || n_steps < 0) return ODPD_EINVAL;
-    return (int64_t)casc_sweep_ss_off(K) + (int64_t)K * n_steps * (int64_t)sizeof(float) + 256;
-}
+extern "C" int64_t odpd_sweep_cascade_scratch_bytes(int K, int64_t n_steps) { return sweep_scratch_bytes(K, n_steps, true); }
 extern "C" int odpd_train_epoch_cascade_sweep(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
                                               const float* const* pa_params, int loss_kind, const odpd_frames_t* fr, int batch, int64_t first_step,
                                               double beta1, double beta2, double eps, double weight_decay, double max_norm, void* scratch) {
-    if (!dpd || !pa || !model_ok(dpd) || !model_ok(pa) || K <= 0 || !runs || !pa_params || !fr || !fr->x_stream || !fr->y_stream || fr->n_frames <= 0 ||
-        fr->frame_length <= 0 || fr->stride <= 0 || batch <= 0 || first_step <= 0 || !scratch)
+    if (!dpd || !pa || !model_ok(dpd) || !model_ok(pa) || K <= 0 || !runs || !pa_params || !epoch_frames_ok(fr, batch, false) || first_step <= 0 ||
+        !scratch)
         return ODPD_EINVAL;
-    for (int k = 0; k < K; ++k)
-        if (!runs[k].params || !runs[k].grad || !runs[k].exp_avg || !runs[k].exp_avg_sq || !runs[k].partials || !runs[k].losses_out || !runs[k].order ||
-            !pa_params[k] || (reinterpret_cast<uintptr_t>(runs[k].workspace) & 7))      // (workspace: double counters)
-            return ODPD_EINVAL;
+    // (on top of the common pointers: every run's PA; workspace = a delta DPD's sparsity counters — doubles — or NULL)
+    if (!sweep_runs_ok(K, runs, [&](int k) { return pa_params[k] && !(reinterpret_cast<uintptr_t>(runs[k].workspace) & 7); })) return ODPD_EINVAL;
     if (fr->sample_format != ODPD_SAMPLES_F32) return ODPD_EUNSUPPORTED;
     const int T = fr->frame_length;
-    const int64_t n = fr->n_frames, n_steps = (n + batch - 1) / batch, tail = n - (n_steps - 1) * batch;
-    if (!odpd_sweep_cascade_supported(dpd, pa, (int)(n < batch ? n : batch), T) || !odpd_sweep_cascade_supported(dpd, pa, (int)tail, T))
-        return ODPD_EUNSUPPORTED;
-    const int64_t P = odpd_param_count(dpd);
+    if (!epoch_shapes_served(fr, batch, 0, 1, [&](int B) { return odpd_sweep_cascade_supported(dpd, pa, B, T) != 0; })) return ODPD_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    SweepRun* dev = nullptr;
-    if (int rc = upload_sweep(st, K, runs, weight_decay, scratch, &dev)) return rc;
-    const float** pa_dev = reinterpret_cast<const float**>(reinterpret_cast<char*>(scratch) + casc_sweep_pa_off(K));
-    ODPD_CHECK_HIP(hipMemcpyAsync(pa_dev, pa_params, (size_t)K * sizeof(float*), hipMemcpyHostToDevice, st));      // (pageable source: staged before the call returns)
-    // per-step, per-run step sizes lr_k / (1 - beta1^step): double arithmetic rounded once, exactly launch_clip_adamw's
-    float* ss_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + casc_sweep_ss_off(K));
-    std::vector<float> ss((size_t)(K * n_steps));
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const double bc1 = 1.0 - pow(beta1, (double)(first_step + i));
-        for (int k = 0; k < K; ++k) ss[(size_t)(i * K + k)] = (float)(runs[k].lr / bc1);
-    }
-    ODPD_CHECK_HIP(hipMemcpyAsync(ss_dev, ss.data(), ss.size() * sizeof(float), hipMemcpyHostToDevice, st));
     CascArgs a{};
     a.thx = dpd->thx; a.thh = dpd->thh; a.bits_w = dpd->bits_w; a.bits_a = dpd->bits_a;
     a.x = fr->x_stream; a.target = fr->y_stream; a.frame_stride = fr->stride;
     a.loss_kind = loss_kind; a.T = T; a.Hd = dpd->hidden; a.Hp = pa->hidden;
-    for (int64_t f0 = 0, i = 0; f0 < n; f0 += batch, ++i) {
-        const int B = (int)((n - f0) < batch ? (n - f0) : batch);
-        const float inv_count = (float)(1.0 / (double)((int64_t)B * T * 2));
-        a.B = B; a.inv_count = inv_count;
-        if (int rc = gru_cascade_sweep_train(st, dpd, pa, a, dev, pa_dev, K, (long long)f0)) return rc;
-        if (int rc = launch_reduce_sweep(st, dev, K, odpd_cascade_rows(dpd, pa, B, T), P)) return rc;
-        if (int rc = launch_clip_adamw_sweep(st, dev, K, P, ss_dev + i * K, first_step + i, i, beta1, beta2, eps, max_norm, inv_count)) return rc;
-    }
-    return 0;
+    return run_sweep_epoch(st, K, runs, pa_params, fr, batch, odpd_param_count(dpd), first_step, beta1, beta2, eps, weight_decay, max_norm, scratch,
+                           [&](const EpochStep& s, SweepRun* dev, const float** pa_dev, int64_t* rows) -> int {
+                               a.B = s.B; a.inv_count = s.inv_count;
+                               *rows = odpd_cascade_rows(dpd, pa, s.B, T);
+                               return gru_cascade_sweep_train(st, dpd, pa, a, dev, pa_dev, K, (long long)s.f0);
+                           });
 }
 extern "C" int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int B, int T, const float* x,
                                        void* scratch) {
@@ -942,33 +961,9 @@ extern "C" int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int 
     for (int k = 0; k < K; ++k)
         if (!runs[k].params || !runs[k].y) return ODPD_EINVAL;
     if (family_of(m) != FAM_GRU || lane_per_unit_model(m) || !gru_sweep_eval_ok(m, B, T)) return ODPD_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
     SweepRun* dev = nullptr;
-    if (int rc = upload_sweep(st, K, runs, 0.0, scratch, &dev)) return rc;
+    if (int rc = upload_sweep((hipStream_t)stream, K, runs, 0.0, scratch, &dev)) return rc;
     SeqArgs a = make_args(m, B, T);
     a.x = x;
-    return gru_sweep_eval(st, m, a, dev, K);
-}
-
-extern "C" int odpd_train_epoch(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch,
-                                float* params, float* grad, float* exp_avg, float* exp_avg_sq, int64_t first_step, double lr,
-                                double beta1, double beta2, double eps, double weight_decay, double max_norm,
-                                float* partials, float* workspace, float* losses_out) {
-    return train_epoch_impl(stream, m, loss_kind, fr, batch, params, grad, exp_avg, exp_avg_sq, first_step, -1, lr, beta1, beta2, eps, weight_decay,
-                            max_norm, partials, workspace, losses_out);
-}
-extern "C" int odpd_train_epoch_dp(void* stream, void* comm, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, int opt_kind,
-                                   float* params, float* grad, float* state1, float* state2, int64_t first_step, double lr, double beta1,
-                                   double beta2, double eps, double weight_decay, double max_norm, float* partials, float* workspace,
-                                   float* losses_out) {
-    if (!comm || opt_kind > ODPD_OPT_RMSPROP) return ODPD_EINVAL;
-    return train_epoch_impl(stream, m, loss_kind, fr, batch, params, grad, state1, state2, first_step, opt_kind < 0 ? -1 : opt_kind, lr, beta1, beta2,
-                            eps, weight_decay, max_norm, partials, workspace, losses_out, comm);
-}
-extern "C" int odpd_train_epoch_opt(void* stream, const odpd_model_t* m, int loss_kind, const odpd_frames_t* fr, int batch, int opt_kind,
-                                    float* params, float* grad, float* state1, float* state2, int64_t first_step, double lr,
-                                    double max_norm, float* partials, float* workspace, float* losses_out) {
-    if (opt_kind < ODPD_OPT_ADAMW || opt_kind > ODPD_OPT_RMSPROP) return ODPD_EINVAL;
-    return train_epoch_impl(stream, m, loss_kind, fr, batch, params, grad, state1, state2, first_step, opt_kind, lr, 0, 0, 0, 0, max_norm, partials,
-                            workspace, losses_out);
+    return gru_sweep_eval((hipStream_t)stream, m, a, dev, K);
 }

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from .models import CascadedModel, CoreModel
 from .project import Project, count_net_params
-from .train_funcs import FusedAdamW, _loss_kind, _sample_format
+from .train_funcs import FusedAdamW, _epoch_shape, _loss_kind, _sample_format
 
 
 class _Rng:
@@ -77,6 +77,40 @@ def _group_key(run):
             p.dataset_label, p.frame_storage, p.grad_clip_val)
 
 
+def _epoch_tables(runs, n, T, n_steps, dev, workspace):
+    """What both lockstep epoch entry points take for the runs of a group: the odpd_sweep_run_t table — every run's epoch order (its own
+    shuffle, drawn from its own RNG stream), fresh per-step losses and `workspace(run)` (a tensor or None) in the `workspace` slot — the
+    odpd_frames_t over the shared train streams (the orders are per run) and the tail of AdamW arguments: first step, betas, eps, weight
+    decay of run 0 (the group key makes them the group's), clip norm."""
+    table = (_lib.SweepRun * len(runs))()
+    for k, r in enumerate(runs):
+        r.net.train()
+        with r.rng:
+            r.order = r.loaders[0].epoch_order()
+        r.losses = torch.empty(n_steps, dtype=torch.float32, device=dev)
+        ws = workspace(r)
+        table[k] = _lib.SweepRun(r.opt.backbone.flat_params(full_check=True).data_ptr(), r.opt.grad.data_ptr(), r.opt.exp_avg.data_ptr(),
+                                 r.opt.exp_avg_sq.data_ptr(), r.partials.data_ptr(), r.losses.data_ptr(), None,
+                                 ws.data_ptr() if ws is not None else None, r.order.data_ptr(), float(r.opt.param_groups[0]["lr"]))
+    opt0, train0 = runs[0].opt, runs[0].loaders[0]
+    assert all(r.opt.step_count == opt0.step_count for r in runs)
+    fr = _lib.Frames(train0.x.data_ptr(), train0.y.data_ptr(), None, n, T, train0.stride, _sample_format(train0.x, train0.y), 0)
+    g0 = opt0.param_groups[0]
+    return table, fr, (opt0.step_count + 1, float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), float(g0["weight_decay"]),
+                       float(runs[0].proj.grad_clip_val or 0.0))
+
+
+def _epoch_done(runs, n_steps):
+    """after a lockstep epoch was issued: the K epoch means — each the reduction its solo run makes (train_funcs.net_train), queued back to
+    back and read with ONE synchronisation — into the runs' logs, and the optimisers' bookkeeping of train_funcs' own epoch loops"""
+    means = torch.stack([r.losses.double().mean() for r in runs]).cpu() if n_steps else None
+    for k, r in enumerate(runs):
+        r.opt.step_count += n_steps
+        r.opt.last_epoch_losses = r.losses
+        r.opt._keepalive = r.order     # the launches read `order` asynchronously
+        r.proj.log_train["loss"] = float(means[k].item()) if means is not None else float("nan")
+
+
 class _Group:
     """runs of one model shape on one dataset: what one sweep launch can carry"""
 
@@ -85,9 +119,8 @@ class _Group:
         r0 = runs[0]
         lib = _lib.load()
         train = r0.loaders[0]
-        self.T, self.n, self.B = train.frame_length, train.n, min(train.batch_size, train.n)
-        self.n_steps = (self.n + self.B - 1) // self.B
-        last = self.n - (self.n_steps - 1) * self.B
+        self.T, self.n = train.frame_length, train.n
+        self.B, self.n_steps, self.last = _epoch_shape(train)
         bb = r0.net.backbone
         self.desc = getattr(bb, "desc", None)
         fused = all(isinstance(r.opt, FusedAdamW) and r.opt.kind == "adamw" and r.opt.pa is None and r.opt.world_size() == 1
@@ -99,7 +132,7 @@ class _Group:
         # takes at this batch size (its frame state fills a CU's LDS: no more than one run's worth of frames is ever resident)
         self.flags = _lib.SWEEP_S16 if (ok and not exact and train.x.dtype == torch.float32 and lib.odpd_sweep_s16_supported(C.byref(self.desc))) else 0
         self.train_sweep = bool(ok and (self.flags or (lib.odpd_sweep_train_supported(C.byref(self.desc), self.B, self.T)
-                                                       and lib.odpd_sweep_train_supported(C.byref(self.desc), last, self.T))))
+                                                       and lib.odpd_sweep_train_supported(C.byref(self.desc), self.last, self.T))))
         self.dev = train.x.device if hasattr(train, "x") else None
         self.scratch = None
         self._tuning_gen = None
@@ -111,11 +144,10 @@ class _Group:
         (a stale buffer under a larger grid would be a device out-of-bounds write)"""
         lib = _lib.load()
         runs, bb = self.runs, self.runs[0].net.backbone
-        last = self.n - (self.n_steps - 1) * self.B
         self._tuning_gen = int(lib.odpd_tuning_generation())
         if self.train_sweep:
-            rows = max(int(lib.odpd_sweep_partial_rows(C.byref(self.desc), b, self.T, self.flags)) for b in {self.B, last})
-            ws = max(int(lib.odpd_sweep_workspace_floats(C.byref(self.desc), b, self.T, self.flags)) for b in {self.B, last})
+            rows = max(int(lib.odpd_sweep_partial_rows(C.byref(self.desc), b, self.T, self.flags)) for b in {self.B, self.last})
+            ws = max(int(lib.odpd_sweep_workspace_floats(C.byref(self.desc), b, self.T, self.flags)) for b in {self.B, self.last})
             P = bb.n_flat
             for r in runs:
                 r.opt._ensure(self.dev)
@@ -134,33 +166,11 @@ class _Group:
         lib = _lib.load()
         if int(lib.odpd_tuning_generation()) != self._tuning_gen:
             self._size_buffers()
-        K = len(self.runs)
-        table = (_lib.SweepRun * K)()
-        train0 = self.runs[0].loaders[0]
-        for k, r in enumerate(self.runs):
-            r.net.train()
-            with r.rng:
-                r.order = r.loaders[0].epoch_order()           # the run's own shuffle, drawn from the run's own RNG stream
-            r.losses = torch.empty(self.n_steps, dtype=torch.float32, device=self.dev)
-            g = r.opt.param_groups[0]
-            flat = r.net.backbone.flat_params(full_check=True)
-            table[k] = _lib.SweepRun(flat.data_ptr(), r.opt.grad.data_ptr(), r.opt.exp_avg.data_ptr(), r.opt.exp_avg_sq.data_ptr(),
-                                     r.partials.data_ptr(), r.losses.data_ptr(), None, r.workspace.data_ptr() if r.workspace is not None else None,
-                                     r.order.data_ptr(), float(g["lr"]))
-        g0 = self.runs[0].opt.param_groups[0]
-        assert all(r.opt.step_count == self.runs[0].opt.step_count for r in self.runs)
-        fr = _lib.Frames(train0.x.data_ptr(), train0.y.data_ptr(), None, self.n, self.T, train0.stride, _sample_format(train0.x, train0.y), 0)
-        rc = lib.odpd_train_epoch_sweep(_lib.stream_ptr(), C.byref(self.desc), K, table, _lib.LOSS_IDS[self.kind], C.byref(fr), self.B,
-                                        self.runs[0].opt.step_count + 1, float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]),
-                                        float(g0["weight_decay"]), float(self.runs[0].proj.grad_clip_val or 0.0), self.flags,
-                                        C.c_void_p(self.scratch.data_ptr()))
+        table, fr, adamw = _epoch_tables(self.runs, self.n, self.T, self.n_steps, self.dev, lambda r: r.workspace)
+        rc = lib.odpd_train_epoch_sweep(_lib.stream_ptr(), C.byref(self.desc), len(self.runs), table, _lib.LOSS_IDS[self.kind], C.byref(fr), self.B,
+                                        *adamw, self.flags, C.c_void_p(self.scratch.data_ptr()))
         _lib.check(rc, "odpd_train_epoch_sweep")
-        # the K epoch means: each the reduction its solo run makes (train_funcs.net_train), queued back to back and read with ONE synchronisation
-        means = torch.stack([r.losses.double().mean() for r in self.runs]).cpu() if self.n_steps else None
-        for k, r in enumerate(self.runs):
-            r.opt.step_count += self.n_steps
-            r.opt.last_epoch_losses = r.losses
-            r.proj.log_train["loss"] = float(means[k].item()) if means is not None else float("nan")
+        _epoch_done(self.runs, self.n_steps)
 
     # ---- validation + test of every run of the group (train_funcs.net_eval_pair, the K forwards as one launch per batch pair) ----
     def eval_epoch(self):
@@ -394,9 +404,8 @@ class _DpdGroup:
         self.runs = runs
         r0 = runs[0]
         train = r0.loaders[0]
-        self.T, self.n, self.B = train.frame_length, train.n, min(train.batch_size, train.n)
-        self.n_steps = (self.n + self.B - 1) // self.B
-        self.last = self.n - (self.n_steps - 1) * self.B
+        self.T, self.n = train.frame_length, train.n
+        self.B, self.n_steps, self.last = _epoch_shape(train)
         self.dev = train.x.device if hasattr(train, "x") else None
         self.kind = _loss_kind(r0.criterion)
         fused = all(isinstance(r.opt, FusedAdamW) and r.opt.kind == "adamw" and r.opt.pa is not None and r.opt.world_size() == 1
@@ -436,40 +445,14 @@ class _DpdGroup:
                 with r.rng:
                     r.net = net_train(r.proj.log_train, r.net, r.loaders[0], r.opt, r.criterion, r.proj.grad_clip_val, r.proj.device)
             return
-        K = len(self.runs)
-        table = (_lib.SweepRun * K)()
-        pa_tab = (C.c_void_p * K)()
-        train0 = self.runs[0].loaders[0]
-        keep = []
-        for k, r in enumerate(self.runs):
-            r.net.train()
-            with r.rng:
-                r.order = r.loaders[0].epoch_order()           # the run's own shuffle, drawn from the run's own RNG stream
-            r.losses = torch.empty(self.n_steps, dtype=torch.float32, device=self.dev)
-            g = r.opt.param_groups[0]
-            dpd, pa = r.opt.backbone, r.opt.pa
-            flat, pa_flat = dpd.flat_params(full_check=True), pa.flat_params(full_check=True)
-            stats = dpd._stats_buffer(self.dev)               # delta DPDs: the four sparsity counters (None while switched off)
-            keep.append((pa_flat, stats))
-            table[k] = _lib.SweepRun(flat.data_ptr(), r.opt.grad.data_ptr(), r.opt.exp_avg.data_ptr(), r.opt.exp_avg_sq.data_ptr(),
-                                     r.partials.data_ptr(), r.losses.data_ptr(), None, stats.data_ptr() if stats is not None else None,
-                                     r.order.data_ptr(), float(g["lr"]))
-            pa_tab[k] = pa_flat.data_ptr()
-        g0 = self.runs[0].opt.param_groups[0]
-        assert all(r.opt.step_count == self.runs[0].opt.step_count for r in self.runs)
-        fr = _lib.Frames(train0.x.data_ptr(), train0.y.data_ptr(), None, self.n, self.T, train0.stride, _sample_format(train0.x, train0.y), 0)
-        rc = lib.odpd_train_epoch_cascade_sweep(_lib.stream_ptr(), C.byref(self.dpd_desc), C.byref(self.pa_desc), K, table, pa_tab,
-                                                _lib.LOSS_IDS[self.kind], C.byref(fr), self.B, self.runs[0].opt.step_count + 1,
-                                                float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), float(g0["weight_decay"]),
-                                                float(self.runs[0].proj.grad_clip_val or 0.0), C.c_void_p(self.scratch.data_ptr()))
+        # workspace slot: a delta DPD's four sparsity counters (None while switched off)
+        table, fr, adamw = _epoch_tables(self.runs, self.n, self.T, self.n_steps, self.dev, lambda r: r.opt.backbone._stats_buffer(self.dev))
+        pa_flat = [r.opt.pa.flat_params(full_check=True) for r in self.runs]
+        pa_tab = (C.c_void_p * len(self.runs))(*(f.data_ptr() for f in pa_flat))
+        rc = lib.odpd_train_epoch_cascade_sweep(_lib.stream_ptr(), C.byref(self.dpd_desc), C.byref(self.pa_desc), len(self.runs), table, pa_tab,
+                                                _lib.LOSS_IDS[self.kind], C.byref(fr), self.B, *adamw, C.c_void_p(self.scratch.data_ptr()))
         _lib.check(rc, "odpd_train_epoch_cascade_sweep")
-        # the K epoch means: each the reduction its solo run makes (train_funcs.net_train), queued back to back and read with ONE synchronisation
-        means = torch.stack([r.losses.double().mean() for r in self.runs]).cpu() if self.n_steps else None
-        for k, r in enumerate(self.runs):
-            r.opt.step_count += self.n_steps
-            r.opt.last_epoch_losses = r.losses
-            r.opt._keepalive = r.order
-            r.proj.log_train["loss"] = float(means[k].item()) if means is not None else float("nan")
+        _epoch_done(self.runs, self.n_steps)
 
     # ---- validation + test of every run of the group: what train_funcs.net_eval_pair computes for each run ----
     def eval_epoch(self):

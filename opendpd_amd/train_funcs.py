@@ -11,7 +11,9 @@ as three launches on the current stream and never synchronises with the host:
  -> [one RCCL all-reduce of P+4 floats when the batch is sharded over ranks]
  -> odpd_clip_adamw_step (global-norm clip + AdamW).
 """
+import contextlib
 import ctypes as C
+import types
 
 import numpy as np
 import torch
@@ -38,6 +40,34 @@ def _loss_kind(criterion):
     if criterion in ("l2", "l1"):
         return criterion
     return None
+
+
+def _resident(loader):
+    """True for a loader whose (N,2) streams are resident on the device: the native epoch loops read its frames in place"""
+    return all(hasattr(loader, k) for k in ("epoch_order", "x", "y", "frame_length", "stride", "batch_size")) and loader.x.is_cuda
+
+
+def _epoch_shape(loader):
+    """(B, n_steps, last) of one epoch over the loader's frames: the size of the full batches, their number with the tail, the tail's size"""
+    B = min(loader.batch_size, loader.n)
+    n_steps = (loader.n + B - 1) // B
+    return B, n_steps, loader.n - (n_steps - 1) * B
+
+
+def _skip_mask(bb):
+    """bb.frozen_mask — the parameters torch.optim.AdamW would skip (grad is None) — as the optimiser kernels read it: one byte per
+    parameter, resident next to the parameters (the kernel skips those columns: no host sync, no extra launch); None without one"""
+    frozen = getattr(bb, "frozen_mask", None)
+    if frozen is not None:
+        dev = bb.flat_params().device
+        if frozen.device != dev or frozen.dtype != torch.uint8:
+            bb.frozen_mask = frozen = frozen.to(device=dev, dtype=torch.uint8).contiguous()
+    return frozen
+
+
+# project.py:274-297's other optimisers, with the hyper-parameters the reference builds them with: constants of the fused kernels
+_FIXED_HYPER = {"adam": dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0), "sgd": dict(momentum=0.9, weight_decay=0.0),
+                "rmsprop": dict(alpha=0.99, eps=1e-8, weight_decay=0.0)}
 
 
 class FusedAdamW:
@@ -244,56 +274,38 @@ class FusedAdamW:
     def apply(self, max_norm, stream=None, comm=None):
         """clip (max_norm, 0 = off) + AdamW on the flat buffers; self.grad must hold the global gradient — or, with `comm` (a
         dist.NativeComm), this rank's share of it: the library then sums over the ranks first."""
+        kind, lr, *rest = self._hyper()
         lib = _lib.load()
-        g = self.param_groups[0]
         self.step_count += 1
         flat = self.backbone.flat_params()
         if stream is None:
             stream = _lib.stream_ptr()
+        frozen = _skip_mask(self.backbone)
+        tail = (float(max_norm or 0.0), _lib.ptr(self.norm), _lib.ptr(frozen))
+        state = (self.backbone.n_flat, _lib.ptr(flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), self.step_count)
         if comm is not None:
-            frozen = getattr(self.backbone, "frozen_mask", None)
-            if frozen is not None and (frozen.device != flat.device or frozen.dtype != torch.uint8):
-                self.backbone.frozen_mask = frozen = frozen.to(device=flat.device, dtype=torch.uint8).contiguous()
-            adamw = self.kind == "adamw"
-            rc = lib.odpd_clip_optim_step_dp(stream, comm.handle, -1 if adamw else _lib.OPTIMIZER_IDS[self.kind], self.backbone.n_flat,
-                                             _lib.ptr(flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                             self.step_count, float(g["lr"]), float(g["betas"][0]) if adamw else 0.0,
-                                             float(g["betas"][1]) if adamw else 0.0, float(g["eps"]) if adamw else 0.0,
-                                             float(g["weight_decay"]) if adamw else 0.0, float(max_norm or 0.0), _lib.ptr(self.norm),
-                                             _lib.ptr(frozen) if frozen is not None else None)
-            if rc:
-                _lib.check(rc, "odpd_clip_optim_step_dp")
-            return
-        frozen = getattr(self.backbone, "frozen_mask", None)     # parameters torch.optim.AdamW would skip (grad is None)
-        if frozen is not None and (frozen.device != flat.device or frozen.dtype != torch.uint8):
-            # one byte per parameter, resident next to the parameters: the kernel skips those columns (no host sync, no extra launch)
-            self.backbone.frozen_mask = frozen = frozen.to(device=flat.device, dtype=torch.uint8).contiguous()
-        if self.kind != "adamw":            # project.py:274-297's other optimisers, with the hyper-parameters the reference builds them with
-            # (those hyper-parameters are constants of the kernel: an edited param_group other than `lr` would be ignored — say so)
-            fixed = {"adam": dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0), "sgd": dict(momentum=0.9, weight_decay=0.0),
-                     "rmsprop": dict(alpha=0.99, eps=1e-8, weight_decay=0.0)}[self.kind]
-            for key, val in fixed.items():
-                if key in g and g[key] != val:
-                    raise NotImplementedError(f"Fused{self.kind.upper()}: param_groups[0]['{key}'] = {g[key]!r}, but the fused step is built with the "
-                                              f"reference's {key} = {val!r} (project.py:274-297); only 'lr' can be changed")
-            rc = lib.odpd_clip_optim_step(stream, _lib.OPTIMIZER_IDS[self.kind], self.backbone.n_flat, _lib.ptr(flat), _lib.ptr(self.grad),
-                                          _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), self.step_count, float(g["lr"]),
-                                          float(max_norm or 0.0), _lib.ptr(self.norm), _lib.ptr(frozen) if frozen is not None else None)
-            if rc:
-                _lib.check(rc, "odpd_clip_optim_step")
-            return
-        rc = lib.odpd_clip_adamw_step_masked(stream, self.backbone.n_flat, _lib.ptr(flat), _lib.ptr(self.grad),
-                                             _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), self.step_count,
-                                             float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                             float(g["weight_decay"]), float(max_norm or 0.0), _lib.ptr(self.norm),
-                                             _lib.ptr(frozen) if frozen is not None else None)
-        if rc:
-            _lib.check(rc, "odpd_clip_adamw_step")
+            _lib.check(lib.odpd_clip_optim_step_dp(stream, comm.handle, kind, *state, lr, *rest, *tail), "odpd_clip_optim_step_dp")
+        elif kind >= 0:
+            _lib.check(lib.odpd_clip_optim_step(stream, kind, *state, lr, *tail), "odpd_clip_optim_step")
+        else:
+            _lib.check(lib.odpd_clip_adamw_step_masked(stream, *state, lr, *rest, *tail), "odpd_clip_adamw_step")
+
+    def _hyper(self):
+        """(optimiser kind, lr, beta1, beta2, eps, weight_decay) as every entry point of the library takes them: kind -1 = AdamW with these
+        hyper-parameters, else an enum odpd_optimizer kind, whose other hyper-parameters are constants of the kernel (the reference's) —
+        an edited param_group other than `lr` would be ignored: say so, before anything is launched"""
+        g = self.param_groups[0]
+        if self.kind == "adamw":
+            return -1, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"])
+        for key, val in _FIXED_HYPER[self.kind].items():
+            if key in g and g[key] != val:
+                raise NotImplementedError(f"Fused{self.kind.upper()}: param_groups[0]['{key}'] = {g[key]!r}, but the fused step is built with the "
+                                          f"reference's {key} = {val!r} (project.py:274-297); only 'lr' can be changed")
+        return _lib.OPTIMIZER_IDS[self.kind], float(g["lr"]), 0.0, 0.0, 0.0, 0.0
 
     def can_run_epoch(self, loader):
         """True when odpd_train_epoch can drive a whole epoch: single fused backbone, one process, resident streams."""
-        if not (self.pa is None and getattr(self.backbone, "frozen_mask", None) is None
-                and all(hasattr(loader, k) for k in ("epoch_order", "x", "y", "frame_length", "stride", "batch_size")) and loader.x.is_cuda):
+        if not (self.pa is None and getattr(self.backbone, "frozen_mask", None) is None and _resident(loader)):
             return False
         if loader.x.dtype == torch.bfloat16 and not self.reads_bf16_frames():
             return False
@@ -321,8 +333,8 @@ class FusedAdamW:
     @staticmethod
     def _epoch_batches(loader):
         """the batch sizes of one epoch: the full batches and the tail"""
-        B = min(loader.batch_size, loader.n)
-        return {B, loader.n - (loader.n - 1) // B * B}
+        B, _, last = _epoch_shape(loader)
+        return {B, last}
 
     def reads_frames(self, B, T):
         """True when the backbone's fused kernel for this batch shape addresses frames inside resident streams
@@ -337,59 +349,56 @@ class FusedAdamW:
         """True when odpd_train_epoch_split can drive a whole epoch: a single backbone WITHOUT a frame-reading fused kernel for the
         epoch's batch shapes, one process, resident streams (the forward / loss / backward / reduce / optimiser chain per step then
         runs from C++ instead of from Python)."""
-        return (self.pa is None and self.world_size() == 1 and not self.can_run_epoch(loader)
-                and all(hasattr(loader, k) for k in ("epoch_order", "x", "y", "frame_length", "stride", "batch_size"))
-                and loader.x.is_cuda and loader.x.dtype == torch.float32 and hasattr(self.backbone, "desc"))
+        return (self.pa is None and self.world_size() == 1 and not self.can_run_epoch(loader) and _resident(loader)
+                and loader.x.dtype == torch.float32 and hasattr(self.backbone, "desc"))
+
+    @contextlib.contextmanager
+    def _epoch(self, loader):
+        """The frame of the three native epoch loops: the batch arithmetic (B, n_steps, last = the tail batch), the epoch's order, the
+        odpd_frames_t over the resident streams and the per-step losses on the way in; the step count on the way out of an epoch
+        that was issued."""
+        dev, T = loader.x.device, loader.frame_length
+        B, n_steps, last = _epoch_shape(loader)
+        self._ensure(dev)
+        order = loader.epoch_order()
+        fr = _lib.Frames(loader.x.data_ptr(), loader.y.data_ptr(), order.data_ptr(), loader.n, T, loader.stride, _sample_format(loader.x, loader.y), 0)
+        yield types.SimpleNamespace(dev=dev, T=T, B=B, last=last, first_step=self.step_count + 1, fr=C.byref(fr),
+                                    losses=torch.empty(n_steps, dtype=torch.float32, device=dev))
+        self.step_count += n_steps
+        self._keepalive = order     # the launches read `order` asynchronously
 
     def train_epoch_split(self, loader, loss_kind, max_norm):
         """One epoch through odpd_train_epoch_split: returns the per-batch mean losses (device tensor)."""
+        hyper = self._hyper()
         lib = _lib.load()
         bb = self.backbone
-        dev, T, n = loader.x.device, loader.frame_length, loader.n
-        B = min(loader.batch_size, n)
-        self._ensure(dev)
-        n_steps = (n + B - 1) // B
-        last = n - (n_steps - 1) * B
-        if bb.dx_needs_flag:               # as _cascade_train_step: the trained model is never asked for dL/dx here
-            bb.desc.flags &= ~_lib.FLAG_NEED_DX
-        if hasattr(bb, "sync_mode"):
-            bb.sync_mode()
-        key = (B, T, last, "split-epoch")
-        if key not in self._partials:
-            rows = [int(lib.odpd_partial_rows(C.byref(bb.desc), b, T, 0)) for b in {B, last}]
-            _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
-            mk = lambda: torch.empty(B, T, 2, dtype=torch.float32, device=dev)
-            self._partials[key] = (torch.empty(max(rows), bb.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev), mk(), mk())
-        part, xbuf, tbuf = self._partials[key]
-        buf = self.cascade_buffers(B, T, dev)
-        order = loader.epoch_order()
-        losses = torch.empty(n_steps, dtype=torch.float32, device=dev)
-        fr = _lib.Frames(loader.x.data_ptr(), loader.y.data_ptr(), order.data_ptr(), n, T, loader.stride, _sample_format(loader.x, loader.y), 0)
-        g = self.param_groups[0]
-        flat = bb.flat_params(full_check=True)
-        frozen = getattr(bb, "frozen_mask", None)
-        if frozen is not None and (frozen.device != flat.device or frozen.dtype != torch.uint8):
-            bb.frozen_mask = frozen = frozen.to(device=flat.device, dtype=torch.uint8).contiguous()
-        adamw = self.kind == "adamw"
-        rc = lib.odpd_train_epoch_split(_lib.stream_ptr(), C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], C.byref(fr), B,
-                                        -1 if adamw else _lib.OPTIMIZER_IDS[self.kind], _lib.ptr(flat), _lib.ptr(self.grad),
-                                        _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), self.step_count + 1, float(g["lr"]),
-                                        float(g["betas"][0]) if adamw else 0.0, float(g["betas"][1]) if adamw else 0.0,
-                                        float(g["eps"]) if adamw else 0.0, float(g["weight_decay"]) if adamw else 0.0,
-                                        float(max_norm or 0.0), _lib.ptr(frozen) if frozen is not None else None,
-                                        _lib.ptr(xbuf), _lib.ptr(tbuf), _lib.ptr(buf["u"]), _lib.ptr(buf["dy"]), _lib.ptr(buf["ck_d"]),
-                                        _lib.ptr(part), _lib.ptr(buf["loss"]), _lib.ptr(bb._stats_buffer(dev)), _lib.ptr(losses))
-        _lib.check(rc, "odpd_train_epoch_split")
-        self.step_count += n_steps
-        self._keepalive = order     # the launches read `order` asynchronously
-        return losses
+        with self._epoch(loader) as e:
+            B, T, dev = e.B, e.T, e.dev
+            if bb.dx_needs_flag:               # as _cascade_train_step: the trained model is never asked for dL/dx here
+                bb.desc.flags &= ~_lib.FLAG_NEED_DX
+            if hasattr(bb, "sync_mode"):
+                bb.sync_mode()
+            key = (B, T, e.last, "split-epoch")
+            if key not in self._partials:
+                rows = [int(lib.odpd_partial_rows(C.byref(bb.desc), b, T, 0)) for b in {B, e.last}]
+                _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
+                mk = lambda: torch.empty(B, T, 2, dtype=torch.float32, device=dev)
+                self._partials[key] = (torch.empty(max(rows), bb.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev), mk(), mk())
+            part, xbuf, tbuf = self._partials[key]
+            buf = self.cascade_buffers(B, T, dev)
+            flat = bb.flat_params(full_check=True)
+            rc = lib.odpd_train_epoch_split(_lib.stream_ptr(), C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], e.fr, B, hyper[0], _lib.ptr(flat),
+                                            _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), e.first_step, *hyper[1:],
+                                            float(max_norm or 0.0), _lib.ptr(_skip_mask(bb)), _lib.ptr(xbuf), _lib.ptr(tbuf), _lib.ptr(buf["u"]),
+                                            _lib.ptr(buf["dy"]), _lib.ptr(buf["ck_d"]), _lib.ptr(part), _lib.ptr(buf["loss"]),
+                                            _lib.ptr(bb._stats_buffer(dev)), _lib.ptr(e.losses))
+            _lib.check(rc, "odpd_train_epoch_split")
+        return e.losses
 
     def can_run_cascade_epoch(self, loader):
         """True when odpd_train_epoch_cascade can drive a whole train_dpd epoch: frozen PA behind the trained DPD, every batch of the epoch
         served by the one-launch cascade step, one process, resident streams."""
-        if not (self.pa is not None
-                and all(hasattr(loader, k) for k in ("epoch_order", "x", "y", "frame_length", "stride", "batch_size")) and loader.x.is_cuda
-                and loader.x.dtype == torch.float32):
+        if not (self.pa is not None and _resident(loader) and loader.x.dtype == torch.float32):
             return False
         for bb in (self.backbone, self.pa):       # quantised models: the descriptor's ODPD_FLAG_EVAL must say what the module says NOW
             if hasattr(bb, "sync_mode"):          # (an evaluation pass leaves it set; the one-launch step serves train mode only)
@@ -403,91 +412,59 @@ class FusedAdamW:
 
     def train_epoch_cascade(self, loader, loss_kind, max_norm):
         """One train_dpd epoch through odpd_train_epoch_cascade: returns the per-batch mean losses (device tensor)."""
+        hyper = self._hyper()
         lib = _lib.load()
         dpd, pa = self.backbone, self.pa
-        dev, T, n = loader.x.device, loader.frame_length, loader.n
-        B = min(loader.batch_size, n)
-        self._ensure(dev)
-        n_steps = (n + B - 1) // B
-        comm = self.native_comm()
-        sizes = self._shard_sizes(loader) if comm is not None else self._epoch_batches(loader)
-        if sizes:
-            part = max((self.cascade_one_launch(b, T, dev) for b in sizes), key=lambda p: p.shape[0])
-        else:       # a rank all of whose shards are empty (global batch smaller than the world): it still joins every all-reduce
-            part = torch.empty(1, dpd.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev)
-        order = loader.epoch_order()
-        losses = torch.empty(n_steps, dtype=torch.float32, device=dev)
-        fr = _lib.Frames(loader.x.data_ptr(), loader.y.data_ptr(), order.data_ptr(), n, T, loader.stride, _sample_format(loader.x, loader.y), 0)
-        g = self.param_groups[0]
-        adamw = self.kind == "adamw"
-        flat = dpd.flat_params(full_check=True)
-        frozen = getattr(dpd, "frozen_mask", None)     # parameters torch.optim.AdamW would skip (grad is None): the QAT models' 16-bit output scales
-        if frozen is not None and (frozen.device != flat.device or frozen.dtype != torch.uint8):
-            dpd.frozen_mask = frozen = frozen.to(device=flat.device, dtype=torch.uint8).contiguous()
-        for bb in (dpd, pa):       # quantised models: train / eval mode of the module -> ODPD_FLAG_EVAL
-            if hasattr(bb, "sync_mode"):
-                bb.sync_mode()
-        rc = lib.odpd_train_epoch_cascade(_lib.stream_ptr(), comm.handle if comm is not None else None, C.byref(dpd.desc), C.byref(pa.desc), _lib.LOSS_IDS[loss_kind], C.byref(fr), B,
-                                          -1 if adamw else _lib.OPTIMIZER_IDS[self.kind], _lib.ptr(dpd.flat_params(full_check=True)),
-                                          _lib.ptr(pa.flat_params(full_check=True)), _lib.ptr(self.grad), _lib.ptr(self.exp_avg),
-                                          _lib.ptr(self.exp_avg_sq), self.step_count + 1, float(g["lr"]), float(g["betas"][0]) if adamw else 0.0,
-                                          float(g["betas"][1]) if adamw else 0.0, float(g["eps"]) if adamw else 0.0,
-                                          float(g["weight_decay"]) if adamw else 0.0, float(max_norm or 0.0),
-                                          _lib.ptr(frozen) if frozen is not None else None, _lib.ptr(part),
-                                          _lib.ptr(dpd._stats_buffer(dev)), _lib.ptr(losses))
-        _lib.check(rc, "odpd_train_epoch_cascade")
-        self.step_count += n_steps
-        self._keepalive = order     # the launches read `order` asynchronously
-        return losses
+        with self._epoch(loader) as e:
+            comm = self.native_comm()
+            sizes = self._shard_sizes(loader) if comm is not None else self._epoch_batches(loader)
+            if sizes:
+                part = max((self.cascade_one_launch(b, e.T, e.dev) for b in sizes), key=lambda p: p.shape[0])
+            else:       # a rank all of whose shards are empty (global batch smaller than the world): it still joins every all-reduce
+                part = torch.empty(1, dpd.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=e.dev)
+            flat, pa_flat = dpd.flat_params(full_check=True), pa.flat_params(full_check=True)
+            frozen = _skip_mask(dpd)      # (the QAT models' 16-bit output scales)
+            for bb in (dpd, pa):       # quantised models: train / eval mode of the module -> ODPD_FLAG_EVAL
+                if hasattr(bb, "sync_mode"):
+                    bb.sync_mode()
+            rc = lib.odpd_train_epoch_cascade(_lib.stream_ptr(), comm.handle if comm is not None else None, C.byref(dpd.desc), C.byref(pa.desc),
+                                              _lib.LOSS_IDS[loss_kind], e.fr, e.B, hyper[0], _lib.ptr(flat), _lib.ptr(pa_flat), _lib.ptr(self.grad),
+                                              _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), e.first_step, *hyper[1:], float(max_norm or 0.0),
+                                              _lib.ptr(frozen), _lib.ptr(part), _lib.ptr(dpd._stats_buffer(e.dev)), _lib.ptr(e.losses))
+            _lib.check(rc, "odpd_train_epoch_cascade")
+        return e.losses
 
     def train_epoch(self, loader, loss_kind, max_norm):
-        """One epoch through the native loop (odpd_train_epoch): returns the per-batch mean losses (device tensor)."""
+        """One epoch through the native loop (odpd_train_epoch, _opt for the other optimisers, _dp when sharded): returns the per-batch mean
+        losses (device tensor)."""
+        kind, lr, *rest = self._hyper()
         lib = _lib.load()
-        dev, T, n = loader.x.device, loader.frame_length, loader.n
-        B = min(loader.batch_size, n)
-        self._ensure(dev)
-        n_steps = (n + B - 1) // B
-        last = n - (n_steps - 1) * B
+        bb = self.backbone
         comm = self.native_comm()
-        key = (B, T, last, "epoch", comm is not None, self._mode())
-        if key not in self._partials:
-            sizes = self._shard_sizes(loader) if comm is not None else {B, last}
-            rows = [int(lib.odpd_partial_rows(C.byref(self.backbone.desc), b, T, 1)) for b in sizes] or [1]
-            _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
-            ws = max([int(lib.odpd_train_workspace_floats(C.byref(self.backbone.desc), b, T)) for b in sizes] or [0])
-            self._partials[key] = (torch.empty(max(rows), self.backbone.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev),
-                                   torch.empty(ws, dtype=torch.float32, device=dev) if ws > 0 else None)
-        part, ws = self._partials[key]
-        if ws is None and (self.backbone.dx_needs_flag or getattr(self.backbone, "fused_stats", False)):      # delta backbones: `workspace` = the sparsity counters (see train_workspace)
-            ws = self.backbone._stats_buffer(dev)
-        order = loader.epoch_order()
-        losses = torch.empty(n_steps, dtype=torch.float32, device=dev)
-        fr = _lib.Frames(loader.x.data_ptr(), loader.y.data_ptr(), order.data_ptr(), n, T, loader.stride, _sample_format(loader.x, loader.y), 0)
-        g = self.param_groups[0]
-        flat = self.backbone.flat_params(full_check=True)
-        if comm is not None:
-            adamw = self.kind == "adamw"
-            rc = lib.odpd_train_epoch_dp(_lib.stream_ptr(), comm.handle, C.byref(self.backbone.desc), _lib.LOSS_IDS[loss_kind], C.byref(fr), B,
-                                         -1 if adamw else _lib.OPTIMIZER_IDS[self.kind], _lib.ptr(flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg),
-                                         _lib.ptr(self.exp_avg_sq), self.step_count + 1, float(g["lr"]), float(g["betas"][0]) if adamw else 0.0,
-                                         float(g["betas"][1]) if adamw else 0.0, float(g["eps"]) if adamw else 0.0,
-                                         float(g["weight_decay"]) if adamw else 0.0, float(max_norm or 0.0), _lib.ptr(part), _lib.ptr(ws),
-                                         _lib.ptr(losses))
-        elif self.kind == "adamw":
-            rc = lib.odpd_train_epoch(_lib.stream_ptr(), C.byref(self.backbone.desc), _lib.LOSS_IDS[loss_kind], C.byref(fr), B,
-                                      _lib.ptr(flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                      self.step_count + 1, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                                      float(g["eps"]), float(g["weight_decay"]), float(max_norm or 0.0), _lib.ptr(part),
-                                      _lib.ptr(ws), _lib.ptr(losses))
-        else:
-            rc = lib.odpd_train_epoch_opt(_lib.stream_ptr(), C.byref(self.backbone.desc), _lib.LOSS_IDS[loss_kind], C.byref(fr), B,
-                                          _lib.OPTIMIZER_IDS[self.kind], _lib.ptr(flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg),
-                                          _lib.ptr(self.exp_avg_sq), self.step_count + 1, float(g["lr"]), float(max_norm or 0.0),
-                                          _lib.ptr(part), _lib.ptr(ws), _lib.ptr(losses))
-        _lib.check(rc, "odpd_train_epoch")
-        self.step_count += n_steps
-        self._keepalive = order     # the launches read `order` asynchronously
-        return losses
+        with self._epoch(loader) as e:
+            B, T, dev = e.B, e.T, e.dev
+            key = (B, T, e.last, "epoch", comm is not None, self._mode())
+            if key not in self._partials:
+                sizes = self._shard_sizes(loader) if comm is not None else {B, e.last}
+                rows = [int(lib.odpd_partial_rows(C.byref(bb.desc), b, T, 1)) for b in sizes] or [1]
+                _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
+                ws = max([int(lib.odpd_train_workspace_floats(C.byref(bb.desc), b, T)) for b in sizes] or [0])
+                self._partials[key] = (torch.empty(max(rows), bb.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev),
+                                       torch.empty(ws, dtype=torch.float32, device=dev) if ws > 0 else None)
+            part, ws = self._partials[key]
+            if ws is None and (bb.dx_needs_flag or getattr(bb, "fused_stats", False)):      # delta backbones: `workspace` = the sparsity counters (see train_workspace)
+                ws = bb._stats_buffer(dev)
+            head = (C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], e.fr, B)
+            state = (_lib.ptr(bb.flat_params(full_check=True)), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), e.first_step)
+            tail = (float(max_norm or 0.0), _lib.ptr(part), _lib.ptr(ws), _lib.ptr(e.losses))
+            if comm is not None:
+                rc = lib.odpd_train_epoch_dp(_lib.stream_ptr(), comm.handle, *head, kind, *state, lr, *rest, *tail)
+            elif kind < 0:
+                rc = lib.odpd_train_epoch(_lib.stream_ptr(), *head, *state, lr, *rest, *tail)
+            else:
+                rc = lib.odpd_train_epoch_opt(_lib.stream_ptr(), *head, kind, *state, lr, *tail)
+            _lib.check(rc, "odpd_train_epoch")
+        return e.losses
 
     def step(self, max_norm=0.0):
         """Generic-path step: gathers p.grad (set by autograd) into the flat gradient, then apply()."""
@@ -691,24 +668,15 @@ def _net_train(log, net, dataloader, optimizer, criterion, grad_clip_val, device
     losses = []
     kind = _loss_kind(criterion)
     fast = isinstance(optimizer, FusedAdamW) and optimizer.net is net and kind is not None
-    if fast and optimizer.can_run_epoch(dataloader):
-        # whole epoch in the native loop: frames read in place from the resident streams, 3 launches per step, no Python
-        losses = optimizer.train_epoch(dataloader, kind, grad_clip_val)
-        optimizer.last_epoch_losses = losses          # per-step mean losses of the epoch (device tensor): the reference only logs their mean
-        log["loss"] = float(losses.double().mean().item()) if losses.numel() else float("nan")
-        return net
-    if fast and optimizer.can_run_cascade_epoch(dataloader):
-        # train_dpd at the reference's batch sizes, GRU-family DPD and PA: one launch per step body, the epoch issued from the native loop
-        losses = optimizer.train_epoch_cascade(dataloader, kind, grad_clip_val)
-        optimizer.last_epoch_losses = losses          # per-step mean losses of the epoch (device tensor): the reference only logs their mean
-        log["loss"] = float(losses.double().mean().item()) if losses.numel() else float("nan")
-        return net
-    if fast and optimizer.can_run_split_epoch(dataloader):
-        # no fused kernel for these batch shapes: the split chain of every step, issued from the native loop as well
-        losses = optimizer.train_epoch_split(dataloader, kind, grad_clip_val)
-        optimizer.last_epoch_losses = losses          # per-step mean losses of the epoch (device tensor): the reference only logs their mean
-        log["loss"] = float(losses.double().mean().item()) if losses.numel() else float("nan")
-        return net
+    # a whole epoch from one of the native loops, no Python between steps: frames read in place by the fused kernel (3 launches per step);
+    # train_dpd at the reference's batch sizes (the one-launch cascade step); no fused kernel for these batch shapes (the split chain)
+    for can_run, run in ((optimizer.can_run_epoch, optimizer.train_epoch), (optimizer.can_run_cascade_epoch, optimizer.train_epoch_cascade),
+                         (optimizer.can_run_split_epoch, optimizer.train_epoch_split)) if fast else ():
+        if can_run(dataloader):
+            losses = run(dataloader, kind, grad_clip_val)
+            optimizer.last_epoch_losses = losses          # per-step mean losses of the epoch (device tensor): the reference only logs their mean
+            log["loss"] = float(losses.double().mean().item()) if losses.numel() else float("nan")
+            return net
     world = optimizer.world_size() if isinstance(optimizer, FusedAdamW) else 1
     if world > 1 and not fast:
         raise RuntimeError("data-parallel training needs the fused step (FusedAdamW on this net, mean l1 / l2 loss)")

@@ -280,11 +280,21 @@ def test_one_launch_cascade_follows_the_chained_launches():
 def test_native_cascade_epoch_equals_the_python_driven_steps(dpd_bb, dpd_h, pa_bb, pa_h, opt_kind):
     """odpd_train_epoch_cascade (frames read in place from the resident streams, every step issued from C++) against fused_train_step on the
     loader's gathered batches: same launches, same order -> bit-identical parameters; a full batch and a shorter tail; net_train takes it."""
+    _cascade_epoch_case(dpd_bb, dpd_h, pa_bb, pa_h, opt_kind, n_s=700, T=50, B=64)
+
+
+@pytest.mark.parametrize("frames", [7, 3], ids=["tail", "one_short_batch"])
+def test_native_cascade_epoch_on_a_tail_and_on_one_short_batch(frames):
+    """where the loop's batch arithmetic can go wrong, at the smallest shape (dgru H13 -> gru H11, T = 20, batches of 4): 7 frames = a full
+    batch and a tail of 3, 3 frames = an epoch of one short batch"""
+    _cascade_epoch_case("dgru", 13, "gru", 11, "adamw", n_s=frames + 20 - 1, T=20, B=4)
+
+
+def _cascade_epoch_case(dpd_bb, dpd_h, pa_bb, pa_h, opt_kind, n_s, T, B):
     from opendpd_amd import CascadedModel, CoreModel
     from opendpd_amd.project import DeviceFrameLoader
     from opendpd_amd.train_funcs import FusedAdamW, FusedSGD, fused_train_step, net_train
     rng = np.random.RandomState(5)
-    n_s, T, B = 700, 50, 64
     amp, ph = 0.05 + 0.85 * rng.rand(n_s), 2 * np.pi * rng.rand(n_s)
     x = np.stack([amp * np.cos(ph), amp * np.sin(ph)], -1)
     y = 0.7 * x + 0.05 * rng.randn(n_s, 2)

@@ -158,6 +158,15 @@ def test_swept_epoch_equals_the_solo_epochs_bit_for_bit(dpd_bb, dpd_h, pa_bb, pa
     _assert_same(r.solo(loss, max_norm), r.swept(loss, max_norm), r.delta)
 
 
+@pytest.mark.parametrize("frames", [7, 3], ids=["tail", "one_short_batch"])
+def test_swept_epoch_on_a_tail_and_on_one_short_batch(frames):
+    """where the sweep's batch arithmetic can go wrong, at the smallest shape (K = 2, dgru H13 -> gru H11, T = 20, batches of 4): 7 frames =
+    a full batch and a tail of 3, 3 frames = an epoch of one short batch"""
+    r = _Runs("dgru", 13, "gru", 11, K=2, T=20, n_frames=frames, stride=1, batch=4, n_samples=frames + 20 - 1)
+    max_norm = 0.7 * max(r.first_step_norms("l2"))      # (clips at least one run's first step)
+    _assert_same(r.solo("l2", max_norm), r.swept("l2", max_norm), r.delta)
+
+
 def test_more_workgroups_than_the_chip_holds_at_once():
     """K = 9 runs of batch 64: 576 workgroups, each with a CU's LDS to itself — they queue, and nothing may depend on their being resident"""
     r = _Runs("gru", 8, "dgru", 8, K=9, T=20, n_frames=64, stride=1, batch=64, n_samples=128)

@@ -121,12 +121,22 @@ def test_native_epoch_loop_equals_per_step_loop(bb, H, F, B):
     """odpd_train_epoch (frames read in place from the resident streams, C++ loop) == the Python per-batch loop over
     gathered frame tensors: same kernels, same order, bit-identical parameters and per-epoch loss.  (bojanet / apnrru / dvrjanet / mcldnn:
     their one-frame-per-workgroup fused kernels address the frames in place too.)"""
+    _native_epoch_vs_per_step(bb, H, F, B, n=3000)
+
+
+@pytest.mark.parametrize("frames", [7, 3], ids=["tail", "one_short_batch"])
+def test_native_epoch_loop_on_a_tail_and_on_one_short_batch(frames):
+    """where the loop's batch arithmetic can go wrong, at the smallest shape (dgru H13, T = 20, batches of 4): 7 frames = a full batch and a
+    tail of 3, 3 frames = an epoch of one short batch"""
+    _native_epoch_vs_per_step("dgru", 13, 20, 4, n=frames + 20 - 1)
+
+
+def _native_epoch_vs_per_step(bb, H, F, B, n):
     import torch
     from opendpd_amd import CoreModel
     from opendpd_amd.project import DeviceFrameLoader
     from opendpd_amd.train_funcs import FusedAdamW, net_train
     rng = np.random.RandomState(3)
-    n = 3000
     ph = np.cumsum(rng.randn(n) * 0.2)
     amp = 0.1 + 0.7 * np.abs(np.sin(np.arange(n) * 0.01 + rng.rand()))
     x = np.stack([amp * np.cos(ph), amp * np.sin(ph)], 1).astype(np.float32)

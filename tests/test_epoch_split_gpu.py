@@ -53,11 +53,17 @@ def test_split_epoch_loop_serves_the_lane_per_unit_and_two_layer_kernels(bb, H, 
     _split_epoch_case(bb, H, kw, "adamw")
 
 
-def _split_epoch_case(bb, H, kw, opt_kind):
+@pytest.mark.parametrize("frames", [7, 3], ids=["tail", "one_short_batch"])
+def test_split_epoch_loop_on_a_tail_and_on_one_short_batch(frames):
+    """where the loop's batch arithmetic can go wrong, at the smallest shape (gru H48, T = 20, batches of 4): 7 frames = a full batch and a
+    tail of 3, 3 frames = an epoch of one short batch"""
+    _split_epoch_case("gru", 48, {}, "adamw", n_s=frames + 20 - 1, T=20, B=4)
+
+
+def _split_epoch_case(bb, H, kw, opt_kind, n_s=700, T=24, B=64):
     from opendpd_amd.project import DeviceFrameLoader
     from opendpd_amd.train_funcs import FusedAdamW, FusedSGD, fused_train_step
     rng = np.random.RandomState(5)
-    n_s, T, B = 700, 24, 64
     amp, ph = 0.05 + 0.85 * rng.rand(n_s), 2 * np.pi * rng.rand(n_s)
     x = np.stack([amp * np.cos(ph), amp * np.sin(ph)], -1)
     y = 0.7 * x + 0.05 * rng.randn(n_s, 2)

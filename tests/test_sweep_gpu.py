@@ -60,6 +60,50 @@ def test_swept_runs_equal_their_solo_runs_bit_for_bit(workdir, bb, H, batch, T):
         _same_files(a, b)
 
 
+@pytest.mark.parametrize("frames", [7, 3], ids=["tail", "one_short_batch"])
+def test_swept_epoch_on_a_tail_and_on_one_short_batch(frames):
+    """odpd_train_epoch_sweep against K = 2 calls of odpd_train_epoch, bit for bit, where the sweep's batch arithmetic can go wrong, at the
+    smallest shape (dgru H13, T = 20, batches of 4): 7 frames = a full batch and a tail of 3, 3 frames = an epoch of one short batch"""
+    from opendpd_amd import CoreModel, _lib
+    lib, K, T, B = _lib.load(), 2, 20, 4
+    n_steps, sizes = (frames + B - 1) // B, {min(B, frames), frames - (frames - 1) // B * B}
+    rng = np.random.RandomState(frames)
+    x, y = (torch.from_numpy((0.5 * rng.randn(frames + T - 1, 2)).astype(np.float32)).cuda() for _ in range(2))
+    fr = lambda order: _lib.Frames(x.data_ptr(), y.data_ptr(), order, frames, T, 1, _lib.SAMPLES_F32, 0)
+    nets = []
+    for k in range(K):
+        torch.manual_seed(100 + k)
+        nets.append(CoreModel(2, 13, 1, "dgru").cuda())
+    desc, P = nets[0].backbone.desc, nets[0].backbone.n_flat
+    assert all(lib.odpd_sweep_train_supported(C.byref(desc), b, T) == 1 for b in sizes)
+    orders = [torch.randperm(frames, generator=torch.Generator().manual_seed(k)).cuda() for k in range(K)]
+    lrs, hyper = [1e-3, 2e-3], (0.9, 0.999, 1e-8, 0.01, 0.05)      # betas, eps, weight decay, a clip norm that clips
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device="cuda")
+
+    def fresh(k, rows):
+        return dict(p=nets[k].backbone.flat_params().detach().clone(), g=z(P + _lib.LOSS_COLS), m=z(P), v=z(P), losses=z(n_steps),
+                    part=torch.empty(rows, P + _lib.LOSS_COLS, dtype=torch.float32, device="cuda"))
+    rows = max(int(lib.odpd_partial_rows(C.byref(desc), b, T, 1)) for b in sizes)
+    ws = max(int(lib.odpd_train_workspace_floats(C.byref(desc), b, T)) for b in sizes)
+    solo = [fresh(k, rows) for k in range(K)]
+    for k, b in enumerate(solo):
+        b["ws"] = z(ws) if ws > 0 else None
+        _lib.check(lib.odpd_train_epoch(_lib.stream_ptr(), C.byref(desc), 0, C.byref(fr(orders[k].data_ptr())), B, _lib.ptr(b["p"]), _lib.ptr(b["g"]),
+                                        _lib.ptr(b["m"]), _lib.ptr(b["v"]), 1, lrs[k], *hyper, _lib.ptr(b["part"]), _lib.ptr(b["ws"]),
+                                        _lib.ptr(b["losses"])), "odpd_train_epoch")
+    swept = [fresh(k, max(int(lib.odpd_sweep_partial_rows(C.byref(desc), b, T, 0)) for b in sizes)) for k in range(K)]
+    table = (_lib.SweepRun * K)(*(_lib.SweepRun(b["p"].data_ptr(), b["g"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), b["part"].data_ptr(),
+                                                b["losses"].data_ptr(), None, None, orders[k].data_ptr(), lrs[k]) for k, b in enumerate(swept)))
+    scratch = torch.empty(int(lib.odpd_sweep_scratch_bytes(K, n_steps)), dtype=torch.uint8, device="cuda")
+    _lib.check(lib.odpd_train_epoch_sweep(_lib.stream_ptr(), C.byref(desc), K, table, 0, C.byref(fr(None)), B, 1, *hyper, 0,
+                                          C.c_void_p(scratch.data_ptr())), "odpd_train_epoch_sweep")
+    torch.cuda.synchronize()
+    for k, (a, b) in enumerate(zip(solo, swept)):
+        for key in ("p", "m", "v", "losses"):
+            assert torch.equal(a[key], b[key]), (k, key)
+        assert torch.isfinite(a["losses"]).all() and not torch.equal(a["p"], nets[k].backbone.flat_params())
+
+
 def test_mixed_hidden_sizes_form_one_group_per_shape(workdir):
     import opendpd_amd as od
     kw = dict(dataset_name="DPA_200MHz", PA_backbone="dgru", n_epochs=2, batch_size=64, frame_length=50, lr=1e-3, accelerator="cuda")
