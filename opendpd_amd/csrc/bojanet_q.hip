@@ -412,17 +412,14 @@ int bojanet_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (a.T < kQM - 1) return ODPD_EINVAL;       // the reference cuts its 15-sample zero pad from the frame itself (bojanet.py:72-77)
     const size_t lds = (size_t)bjq_fwd_floats(bjq_layout(m->hidden).P) * sizeof(float);
     const int cap = 6 * device_cus(), grid = a.B < cap ? a.B : cap;
-    return a.ckpt ? launch_seq(st, bjq_fwd_kernel<true>, grid, lds, a) : launch_seq(st, bjq_fwd_kernel<false>, grid, lds, a);
+    return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, bjq_fwd_kernel<sv()>, grid, lds, a); });
 }
 int bojanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!bojanet_q_ok(m)) return ODPD_EUNSUPPORTED;
     if (a.T < kQM - 1 || !a.ckpt) return ODPD_EINVAL;
     const size_t lds = (size_t)bjq_bwd_floats(bjq_layout(m->hidden).P) * sizeof(float);
     const int grid = bojanet_q_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_seq(st, bjq_bwd_kernel<true, true>, grid, lds, a);
-    if (nw) return launch_seq(st, bjq_bwd_kernel<true, false>, grid, lds, a);
-    return launch_seq(st, bjq_bwd_kernel<false, true>, grid, lds, a);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_seq(st, bjq_bwd_kernel<nw(), dx()>, grid, lds, a); });
 }
 
 }  // namespace odpd

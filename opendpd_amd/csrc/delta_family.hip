@@ -913,20 +913,12 @@ template <bool TRES>
 static int delta_launch_fwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = persistent_shape(a.ngroups, 8);
     const size_t lds = delta_lds_bytes(P, ls.waves, false);
-    auto k = delta_fwd_kernel<TRES>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, delta_fwd_kernel<TRES>, ls.grid, 64 * ls.waves, lds, a);
 }
 template <bool TRES>
 static int delta_launch_eval(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = ((size_t)pad4(P) + kDTabFloats + kEvalChunk * 8 + kEvalChunk * kDEvalHistStride + 32) * sizeof(float);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
-    return a.ckpt ? launch(delta_eval_kernel<TRES, true>) : launch(delta_eval_kernel<TRES, false>);
+    return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, delta_eval_kernel<TRES, sv()>, a.B, lds, a); });
 }
 template <bool TRES>
 static int delta_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
@@ -934,10 +926,7 @@ static int delta_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
     if (a.partials == nullptr) return ODPD_EINVAL;
     const LaunchShape ls = delta_bwd_shape(a.ngroups);
     const size_t lds = delta_lds_bytes(P, ls.waves, true);
-    auto k = delta_bwd_kernel<TRES>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, delta_bwd_kernel<TRES>, ls.grid, 64 * ls.waves, lds, a);
 }
 
 // the gate-parallel backward kernel: one sequence per single-wave workgroup, the frame's parked state in LDS
@@ -950,16 +939,11 @@ static bool delta_bwd_uses_gp(const odpd_model_t* m, int B, int T) {
 }
 static int delta_gp_rows(const odpd_model_t* m, int B, int T) {
     const int P = delta_layout(m->hidden, m->backbone == ODPD_TRES_DELTAGRU).P;
-    const long cap = (long)device_cus() * (kMaxLds / delta_gp_lds_bytes(P, T));
-    return B < cap ? B : (int)cap;
+    return gp_rows(B, (int)(kMaxLds / delta_gp_lds_bytes(P, T)));
 }
 template <bool TRES>
 static int delta_launch_gp_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, int P) {
-    const size_t lds = delta_gp_lds_bytes(P, a.T);
-    auto k = delta_gp_bwd_kernel<TRES>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(delta_gp_rows(m, a.B, a.T)), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_seq(st, delta_gp_bwd_kernel<TRES>, delta_gp_rows(m, a.B, a.T), delta_gp_lds_bytes(P, a.T), a);
 }
 
 // deltajanet's home is delta_s16.hip (every batch, dL/dx, hidden <= 32); at the reference's own batch sizes — every sequence on a SIMD of its
@@ -976,15 +960,11 @@ static bool jan_train_uses_gp(const odpd_model_t* m, int B, int T) {
     return gp_batch_fits(B, delta_gp_blocks_per_cu(jan_P(m), T), 3);
 }
 static int jan_gp_rows(const odpd_model_t* m, int B, int T) {
-    const long cap = (long)device_cus() * (kMaxLds / delta_gp_lds_bytes(jan_P(m), T));
-    return B < cap ? B : (int)cap;
+    return gp_rows(B, (int)(kMaxLds / delta_gp_lds_bytes(jan_P(m), T)));
 }
 static int jan_launch_eval(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = ((size_t)pad4(P) + kDTabFloats + kEvalChunk * 8 + kEvalChunk * kDEvalHistStride + 32) * sizeof(float);
-    auto k = delta_eval_kernel<false, false, true>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_seq(st, delta_eval_kernel<false, false, true>, a.B, lds, a);
 }
 // ---- fused train step at the reference's batch sizes (one frame per single-wave workgroup): delta_gp_bwd_kernel<.., FUSED> ----
 bool delta_train_uses_gp(const odpd_model_t* m, int B, int T) {
@@ -1002,11 +982,7 @@ int delta_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool jan = m->backbone == ODPD_DELTAJANET, tres = m->backbone == ODPD_TRES_DELTAGRU;
     const int P = jan ? jan_P(m) : delta_layout(m->hidden, tres).P;
     const size_t lds = delta_gp_lds_bytes(P, a.T);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(delta_gp_train_rows(m, a.B, a.T)), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_seq(st, k, delta_gp_train_rows(m, a.B, a.T), lds, a); };
     if (jan) return launch(delta_gp_bwd_kernel<false, true, true>);
     return tres ? launch(delta_gp_bwd_kernel<true, false, true>) : launch(delta_gp_bwd_kernel<false, false, true>);
 }
@@ -1017,19 +993,13 @@ int delta_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (m->hidden > 16) return ODPD_EUNSUPPORTED;
     const bool tres = m->backbone == ODPD_TRES_DELTAGRU;
     const int P = delta_layout(m->hidden, tres).P;
-    if (a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0)          // sequences that each get a SIMD of their own (inference / checkpoint-writing forward)
+    if (gp_eval_batch_fits(a.B))          // sequences that each get a SIMD of their own (inference / checkpoint-writing forward)
         return tres ? delta_launch_eval<true>(st, a, P) : delta_launch_eval<false>(st, a, P);
     return tres ? delta_launch_fwd<true>(st, a, P) : delta_launch_fwd<false>(st, a, P);
 }
 int delta_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (a.dx == nullptr && a.partials != nullptr && jan_train_uses_gp(m, a.B, a.T)) {
-        const int P = jan_P(m);
-        const size_t lds = delta_gp_lds_bytes(P, a.T);
-        auto k = delta_gp_bwd_kernel<false, true>;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(jan_gp_rows(m, a.B, a.T)), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    }
+    if (a.dx == nullptr && a.partials != nullptr && jan_train_uses_gp(m, a.B, a.T))
+        return launch_seq(st, delta_gp_bwd_kernel<false, true>, jan_gp_rows(m, a.B, a.T), delta_gp_lds_bytes(jan_P(m), a.T), a);
     if (delta_uses_s16(m, a.B)) return delta_s16_launch(st, m, a, 2);
     if (m->hidden > 16) return ODPD_EUNSUPPORTED;
     const bool tres = m->backbone == ODPD_TRES_DELTAGRU;

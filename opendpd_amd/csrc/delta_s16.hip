@@ -938,9 +938,7 @@ bool delta_uses_s16(const odpd_model_t* m, int B) {
     if (m->backbone == ODPD_DELTAJANET) return m->hidden <= 32;               // deltajanet lives in these kernels only
     if ((m->backbone != ODPD_DELTAGRU && m->backbone != ODPD_TRES_DELTAGRU) || m->hidden > 32) return false;
     if (m->hidden > 16 || (m->flags & ODPD_FLAG_NEED_DX)) return true;      // dL/dx lives in these kernels only
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = 16L * 4 * device_cus();
-    return B >= min_batch;
+    return B >= s16_min_batch_or(16L * 4 * device_cus());
 }
 // `per_cu`: workgroups of eight waves a CU holds (2 = the four-waves-per-SIMD forward of deltagru_tcnskip)
 static LaunchShape d16_fwd_shape(int ngroups, int nt, int per_cu = 1) {
@@ -988,10 +986,7 @@ static int d16_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, 
     if (mode == 1) {
         const LaunchShape ls = d16_fwd_shape(a.ngroups, NT, D16Fwd<TRES, NT>::LEAN ? 2 : 1);
         const size_t lds = ((size_t)pad4(P) + s16_tab_floats(T::NG) + (size_t)ls.waves * D16Fwd<TRES, NT>::kWave) * sizeof(float);
-        auto k = delta16_fwd_kernel<TRES, NT, JAN>;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
+        return launch_lds(st, delta16_fwd_kernel<TRES, NT, JAN>, ls.grid, 64 * ls.waves, lds, a);
     }
     // the weight gradients ride along in every backward launch: partials are required (a frozen model passes a scratch buffer)
     if (a.partials == nullptr) return ODPD_EINVAL;
@@ -1001,11 +996,7 @@ static int d16_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, 
     const LaunchShape ls = d16_bwd_shape(m, a.ngroups);
     const size_t lds = d16_bwd_lds(P, NT, ls.waves, dxf);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_lds(st, k, ls.grid, 64 * ls.waves, lds, a); };
     if (int e = a.dx == nullptr ? launch(delta16_bwd_kernel<TRES, NT, false, JAN>) : launch(delta16_bwd_kernel<TRES, NT, true, JAN>)) return e;
     if (TRES) {
         hipLaunchKernelGGL(tres_skip_wgrad_kernel, dim3(kTcnRows), dim3(kTcnThreads), 0, st, a.x, a.dy, a.params,

@@ -398,7 +398,7 @@ int delta_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!delta_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const bool tres = m->backbone == ODPD_TRES_DELTAGRU;
     const size_t lds = (size_t)dw_fwd_floats(delta_layout(m->hidden, tres).P) * sizeof(float);
-    return wide_fwd_dispatch(a, [&](auto sv) {
+    return ckpt_dispatch(a, [&](auto sv) {
         constexpr bool SAVE = decltype(sv)::value;
         return tres ? wide_launch(st, wide_delta_fwd_kernel<true, SAVE>, lds, a) : wide_launch(st, wide_delta_fwd_kernel<false, SAVE>, lds, a);
     });

@@ -316,7 +316,7 @@ int deltajanet_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a)
     if (!deltajanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)dj_fwd_floats(dj_params(m)) * sizeof(float);
     const bool qh = m->bits_w > 0;
-    return wide_fwd_dispatch(a, [&](auto sv) {
+    return ckpt_dispatch(a, [&](auto sv) {
         constexpr bool SAVE = decltype(sv)::value;
         return qh ? wide_launch(st, wide_deltajanet_fwd_kernel<SAVE, true>, lds, a) : wide_launch(st, wide_deltajanet_fwd_kernel<SAVE, false>, lds, a);
     });

@@ -423,7 +423,7 @@ int dvrjanet_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const int K = dvq_units(m);
     const size_t lds = (size_t)dvq_fwd_floats(dvq_layout(m->hidden, K).P) * sizeof(float);
     const int cap = 8 * device_cus(), grid = a.B < cap ? a.B : cap;
-    return a.ckpt ? launch_seq(st, dvq_fwd_kernel<true>, grid, lds, a, K) : launch_seq(st, dvq_fwd_kernel<false>, grid, lds, a, K);
+    return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, dvq_fwd_kernel<sv()>, grid, lds, a, K); });
 }
 int dvrjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!dvrjanet_q_ok(m)) return ODPD_EUNSUPPORTED;
@@ -431,10 +431,7 @@ int dvrjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const int K = dvq_units(m);
     const size_t lds = (size_t)dvq_bwd_floats(dvq_layout(m->hidden, K).P) * sizeof(float);
     const int grid = dvrjanet_q_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_seq(st, dvq_bwd_kernel<true, true>, grid, lds, a, K);
-    if (nw) return launch_seq(st, dvq_bwd_kernel<true, false>, grid, lds, a, K);
-    return launch_seq(st, dvq_bwd_kernel<false, true>, grid, lds, a, K);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_seq(st, dvq_bwd_kernel<nw(), dx()>, grid, lds, a, K); });
 }
 
 }  // namespace odpd

@@ -314,11 +314,7 @@ int casc_grid(const CascCfg& c, int B, int T) {
 template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
 int casc_launch(hipStream_t st, const CascArgs& a, const CascCfg& c) {
     const size_t lds = casc_lds<NBD, FMD, DGD, PV, FMP, DGP>(a.T, c.Pd, c.Pp);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(casc_grid(c, a.B, a.T)), dim3(128), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_lds(st, k, casc_grid(c, a.B, a.T), 128, lds, a); };
     if constexpr (FMD == kDpdDelta || FMD == kDpdTres) return launch(delta_cascade_kernel<FMD == kDpdTres, PV, FMP, DGP>);
     else if constexpr (FMD == kDpdLstm) return launch(lstm_cascade_kernel<PV, FMP, DGP>);
     else return launch(gru_cascade_kernel<NBD, FMD, DGD, PV, FMP, DGP>);
@@ -328,11 +324,7 @@ template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
 int casc_sweep_launch(hipStream_t st, const CascArgs& a, const CascCfg& c, const SweepRun* runs, const float* const* pa_tab, int K, long long first) {
     const size_t lds = casc_lds<NBD, FMD, DGD, PV, FMP, DGP>(a.T, c.Pd, c.Pp);
     const int G = casc_grid(c, a.B, a.T);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)G * (unsigned)K), dim3(128), lds, st, a, runs, pa_tab, G, first);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_lds(st, k, G * K, 128, lds, a, runs, pa_tab, G, first); };      // (G K < 2^31: checked by the caller)
     if constexpr (FMD == kDpdDelta || FMD == kDpdTres) return launch(delta_cascade_sweep_kernel<FMD == kDpdTres, PV, FMP, DGP>);
     else if constexpr (FMD == kDpdLstm) return launch(lstm_cascade_sweep_kernel<PV, FMP, DGP>);
     else return launch(gru_cascade_sweep_kernel<NBD, FMD, DGD, PV, FMP, DGP>);

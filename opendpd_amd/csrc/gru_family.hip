@@ -1309,29 +1309,20 @@ template <int R, int FM, bool DG>
 static int launch_fwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = persistent_shape(a.ngroups, kFwdWavesPerCU);
     const size_t lds = gru_lds_bytes(P, R, DG, ls.waves, 2 * 2 * (4 / R) * kChunkPad, false);
-    auto k = gru_fwd_kernel<R, FM, DG>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru_fwd_kernel<R, FM, DG>, ls.grid, 64 * ls.waves, lds, a);
 }
 template <int R, int FM, bool DG, bool NW, bool DX>
 static int launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = bwd_shape(R, a.ngroups);
     const size_t lds = gru_lds_bytes(P, R, DG, ls.waves, 3 * 2 * (4 / R) * kChunkPad, NW);
-    auto k = gru_bwd_kernel<R, FM, DG, NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru_bwd_kernel<R, FM, DG, NW, DX>, ls.grid, 64 * ls.waves, lds, a);
 }
 template <int R, int FM, bool DG>
 static int launch_train(hipStream_t st, const SeqArgs& a, int P) {
     size_t lds = 0;
     const LaunchShape ls = train_shape(P, R, DG, a.ngroups, a.T, &lds);
     if (ls.grid <= 0) return ODPD_EUNSUPPORTED;  // frame too long for LDS-resident BPTT state
-    auto k = gru_train_kernel<R, FM, DG>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru_train_kernel<R, FM, DG>, ls.grid, 64 * ls.waves, lds, a);
 }
 
 // frozen PA of a cascade: forward + loss + dL/du in one launch (a.x = u, a.target, a.dx = du, a.partials = loss rows)
@@ -1340,27 +1331,35 @@ static int launch_lossdx(hipStream_t st, const SeqArgs& a, int P) {
     size_t lds = 0;
     const LaunchShape ls = train_shape(P, R, DG, a.ngroups, a.T, &lds, true);
     if (ls.grid <= 0) return ODPD_EUNSUPPORTED;
-    auto k = gru_train_kernel<R, FM, DG, false, true>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru_train_kernel<R, FM, DG, false, true>, ls.grid, 64 * ls.waves, lds, a);
 }
 
-#define ODPD_GRU_DISPATCH(R_, FM_, DG_, CALL) \
-    if (R == R_ && FM == FM_ && DG == DG_) return CALL;
-#define ODPD_GRU_DISPATCH_ALL(FN, ...)                                              \
-    ODPD_GRU_DISPATCH(1, FEAT_RAW2, false, (FN<1, FEAT_RAW2, false>(__VA_ARGS__)))  \
-    ODPD_GRU_DISPATCH(2, FEAT_RAW2, false, (FN<2, FEAT_RAW2, false>(__VA_ARGS__)))  \
-    ODPD_GRU_DISPATCH(1, FEAT_DGRU6, true, (FN<1, FEAT_DGRU6, true>(__VA_ARGS__)))  \
-    ODPD_GRU_DISPATCH(2, FEAT_DGRU6, true, (FN<2, FEAT_DGRU6, true>(__VA_ARGS__)))  \
-    ODPD_GRU_DISPATCH(1, FEAT_Q4, false, (FN<1, FEAT_Q4, false>(__VA_ARGS__)))      \
-    ODPD_GRU_DISPATCH(2, FEAT_Q4, false, (FN<2, FEAT_Q4, false>(__VA_ARGS__)))      \
-    ODPD_GRU_DISPATCH(1, FEAT_A4, false, (FN<1, FEAT_A4, false>(__VA_ARGS__)))      \
-    ODPD_GRU_DISPATCH(2, FEAT_A4, false, (FN<2, FEAT_A4, false>(__VA_ARGS__)))
+// the kernels' template axes from the model, as integral constants: f(FM, DG) — DG: the fc_hid head, dgru alone has it ...
+template <typename F>
+static int gru_feat_dispatch(int FM, F f) {
+    switch (FM) {
+    case FEAT_RAW2: return f(int_c<FEAT_RAW2>{}, std::false_type{});
+    case FEAT_DGRU6: return f(int_c<FEAT_DGRU6>{}, std::true_type{});
+    case FEAT_Q4: return f(int_c<FEAT_Q4>{}, std::false_type{});
+    case FEAT_A4: return f(int_c<FEAT_A4>{}, std::false_type{});
+    default: return ODPD_EUNSUPPORTED;
+    }
+}
+// ... f(R, FM, DG) for the row-rotated and the fused kernels, f(NB, FM, DG) for the evaluation and sweep kernels.  Two of them, because the
+// order of the calls is the order in which the kernels are instantiated and laid out in the code object: rows innermost / blocks outermost
+template <typename F>
+static int gru_dispatch(int R, int FM, F f) {
+    return gru_feat_dispatch(FM, [&](auto fm, auto dg) { return R == 1 ? f(int_c<1>{}, fm, dg) : R == 2 ? f(int_c<2>{}, fm, dg) : ODPD_EUNSUPPORTED; });
+}
+template <typename F>
+static int gru_nb_dispatch(int NB, int FM, F f) {
+    if (NB == 1) return gru_feat_dispatch(FM, [&](auto fm, auto dg) { return f(int_c<1>{}, fm, dg); });
+    return NB == 2 ? gru_feat_dispatch(FM, [&](auto fm, auto dg) { return f(int_c<2>{}, fm, dg); }) : ODPD_EUNSUPPORTED;
+}
 
 template <int R, int FM, bool DG>
 static int launch_bwd_mode(hipStream_t st, const SeqArgs& a, int P) {
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
+    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;      // (not s16_bwd_dispatch: its order would lay the three kernels out in another order)
     if (nw && !dx) return launch_bwd<R, FM, DG, true, false>(st, a, P);
     if (!nw && dx) return launch_bwd<R, FM, DG, false, true>(st, a, P);
     if (nw && dx) return launch_bwd<R, FM, DG, true, true>(st, a, P);
@@ -1379,9 +1378,7 @@ static bool gru_setup(const odpd_model_t* m, int& FM, bool& DG, int& R, int& P) 
 bool gru_uses_s16n(const odpd_model_t* m, int B) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || R != 2) return false;
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = 8L * 4 * device_cus();    // measured crossover (DGRU-23, T = 200): 1.54 vs 1.33 ms at 8192
-    return B >= min_batch;
+    return B >= s16_min_batch_or(8L * 4 * device_cus());    // measured crossover (DGRU-23, T = 200): 1.54 vs 1.33 ms at 8192
 }
 
 // The split kernels switch to the 16-sequences-per-wave mapping at the same batch size as the fused one.  Forward
@@ -1389,50 +1386,31 @@ bool gru_uses_s16n(const odpd_model_t* m, int B) {
 bool gru_split_uses_s16(const odpd_model_t* m, int B) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || R != 1) return false;
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = 16L * 4 * device_cus();
-    return B >= min_batch;
+    return B >= s16_min_batch_or(16L * 4 * device_cus());
 }
 
 // inference on a few long sequences (no checkpoints asked for): the gate-parallel evaluation kernel, one sequence per wave
 template <int NB, int FM, bool DG>
 static int launch_eval(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = ((size_t)pad4(P) + GruTabs<NB, DG>::kFloats + GruEvalLds<NB>::kFloats) * sizeof(float);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
     if constexpr (NB == 2)
-        if (a.H <= 24) return a.ckpt ? launch(gru_eval_kernel<NB, FM, DG, true, true>) : launch(gru_eval_kernel<NB, FM, DG, false, true>);
-    return a.ckpt ? launch(gru_eval_kernel<NB, FM, DG, true>) : launch(gru_eval_kernel<NB, FM, DG, false>);
+        if (a.H <= 24) return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, gru_eval_kernel<NB, FM, DG, sv(), true>, a.B, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, gru_eval_kernel<NB, FM, DG, sv()>, a.B, lds, a); });
 }
 bool gru_uses_eval_kernel(const odpd_model_t* m, int B, int T, bool want_ckpt) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || tuning().s16_min_batch == 0 || tuning().gp_max_batch == 0) return false;
     // a few long sequences (net_eval / run_dpd), or any batch whose sequences each get a SIMD of their own before the S16 kernels take over
     // (then also as the checkpoint-writing forward of the split train path)
-    return (!want_ckpt && B <= 8 && T >= 256) || (B <= 2 * device_cus() && !gru_split_uses_s16(m, B) && !gru_uses_s16n(m, B));
+    return (!want_ckpt && B <= 8 && T >= 256) || (gp_eval_batch_fits(B) && !gru_split_uses_s16(m, B) && !gru_uses_s16n(m, B));
 }
 int gru_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_uses_eval_kernel(m, a.B, a.T, a.ckpt != nullptr)) {
-        if (R == 1) {
-            if (FM == FEAT_RAW2) return launch_eval<1, FEAT_RAW2, false>(st, a, P);
-            if (FM == FEAT_DGRU6) return launch_eval<1, FEAT_DGRU6, true>(st, a, P);
-            if (FM == FEAT_Q4) return launch_eval<1, FEAT_Q4, false>(st, a, P);
-            return launch_eval<1, FEAT_A4, false>(st, a, P);
-        }
-        if (FM == FEAT_RAW2) return launch_eval<2, FEAT_RAW2, false>(st, a, P);
-        if (FM == FEAT_DGRU6) return launch_eval<2, FEAT_DGRU6, true>(st, a, P);
-        if (FM == FEAT_Q4) return launch_eval<2, FEAT_Q4, false>(st, a, P);
-        return launch_eval<2, FEAT_A4, false>(st, a, P);
-    }
+    if (gru_uses_eval_kernel(m, a.B, a.T, a.ckpt != nullptr)) return gru_nb_dispatch(R, FM, [&](auto nb, auto fm, auto dg) { return launch_eval<nb(), fm(), dg()>(st, a, P); });
     if (gru_split_uses_s16(m, a.B)) return gru_s16_fwd(st, m, a);
     if (gru_uses_s16n(m, a.B)) return gru_s16x_train_ok(m) ? gru_s16x_fwd(st, m, a) : gru_s16n_launch(st, m, a, 1);
-    ODPD_GRU_DISPATCH_ALL(launch_fwd, st, a, P)
-    return ODPD_EUNSUPPORTED;
+    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_fwd<r(), fm(), dg()>(st, a, P); });
 }
 static bool gru_bwd_uses_gp(const odpd_model_t* m, int B, int T);
 static int gp_grid(int P, int R, bool DG, int B, int T);
@@ -1445,7 +1423,7 @@ int gru_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (gru_uses_s16n(m, a.B)) return gru_s16x_train_ok(m) ? gru_s16x_bwd(st, m, a, gru_s16n_rows(m, a.B)) : gru_s16n_launch(st, m, a, 2);
     if (gru_bwd_uses_gp(m, a.B, a.T)) {
         // weight gradients only: the fused one-sequence-per-wave kernel with dL/dy given (it runs its own forward; the checkpoints stay unread)
-        if (a.partials != nullptr && a.dx == nullptr) { ODPD_GRU_DISPATCH_ALL(launch_gp_train, st, a, P) }
+        if (a.partials != nullptr && a.dx == nullptr) return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_gp_train<r(), fm(), dg()>(st, a, P); });
         // dL/dx asked for: the row-rotated kernel writes fewer rows than the caller's buffer holds — the rest are zero
         if (a.partials != nullptr) {
             const int have = bwd_shape(R, a.ngroups).grid, rows = gp_grid(P, R, DG, a.B, a.T);
@@ -1453,8 +1431,7 @@ int gru_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
                 ODPD_CHECK_HIP(hipMemsetAsync(a.partials + (size_t)have * (P + kLossCols), 0, (size_t)(rows - have) * (P + kLossCols) * sizeof(float), st));
         }
     }
-    ODPD_GRU_DISPATCH_ALL(launch_bwd_mode, st, a, P)
-    return ODPD_EUNSUPPORTED;
+    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_bwd_mode<r(), fm(), dg()>(st, a, P); });
 }
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, BPTT state of the whole frame in LDS
 static size_t gp_lds_bytes(int P, int R, bool DG, int T, bool pg) {
@@ -1479,19 +1456,14 @@ static bool gru_bwd_uses_gp(const odpd_model_t* m, int B, int T) {
 }
 static int gp_grid(int P, int R, bool DG, int B, int T) {
     const bool pg = gp_parks_gates(P, R, DG, B, T);
-    const long cap = (long)device_cus() * (kMaxLds / gp_lds_bytes(P, R, DG, T, pg));
-    return B < cap ? B : (int)cap;
+    return gp_rows(B, (int)(kMaxLds / gp_lds_bytes(P, R, DG, T, pg)));
 }
 template <int R, int FM, bool DG>
 static int launch_gp_train(hipStream_t st, const SeqArgs& a, int P) {
     const bool pg = gp_parks_gates(P, R, DG, a.B, a.T);
     const size_t lds = gp_lds_bytes(P, R, DG, a.T, pg);
     const int grid = gp_grid(P, R, DG, a.B, a.T);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_seq(st, k, grid, lds, a); };
     if constexpr (R == 2)
         if (a.H <= 24) return pg ? launch(gru_gp_train_kernel<R, FM, DG, true, false, true>) : launch(gru_gp_train_kernel<R, FM, DG, false, false, true>);
     return pg ? launch(gru_gp_train_kernel<R, FM, DG, true>) : launch(gru_gp_train_kernel<R, FM, DG, false>);
@@ -1508,11 +1480,7 @@ static int launch_gp_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepR
     const bool pg = gp_parks_gates(P, R, DG, a.B, a.T);
     const size_t lds = gp_lds_bytes(P, R, DG, a.T, pg);
     const int G = gp_grid(P, R, DG, a.B, a.T);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)G * K), dim3(64), lds, st, a, runs, G, first);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_seq(st, k, G * K, lds, a, runs, G, first); };
     if constexpr (R == 2)
         if (a.H <= 24) return pg ? launch(gru_gp_train_sweep_kernel<R, FM, DG, true, true>) : launch(gru_gp_train_sweep_kernel<R, FM, DG, false, true>);
     return pg ? launch(gru_gp_train_sweep_kernel<R, FM, DG, true, false>) : launch(gru_gp_train_sweep_kernel<R, FM, DG, false, false>);
@@ -1520,44 +1488,21 @@ static int launch_gp_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepR
 int gru_sweep_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, const SweepRun* runs, int K, long long first) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || !gru_sweep_train_ok(m, a.B, a.T) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
-    if (R == 1) {
-        if (FM == FEAT_RAW2) return launch_gp_sweep<1, FEAT_RAW2, false>(st, a, P, runs, K, first);
-        if (FM == FEAT_DGRU6) return launch_gp_sweep<1, FEAT_DGRU6, true>(st, a, P, runs, K, first);
-        if (FM == FEAT_Q4) return launch_gp_sweep<1, FEAT_Q4, false>(st, a, P, runs, K, first);
-        return launch_gp_sweep<1, FEAT_A4, false>(st, a, P, runs, K, first);
-    }
-    if (FM == FEAT_RAW2) return launch_gp_sweep<2, FEAT_RAW2, false>(st, a, P, runs, K, first);
-    if (FM == FEAT_DGRU6) return launch_gp_sweep<2, FEAT_DGRU6, true>(st, a, P, runs, K, first);
-    if (FM == FEAT_Q4) return launch_gp_sweep<2, FEAT_Q4, false>(st, a, P, runs, K, first);
-    return launch_gp_sweep<2, FEAT_A4, false>(st, a, P, runs, K, first);
+    return gru_nb_dispatch(R, FM, [&](auto nb, auto fm, auto dg) { return launch_gp_sweep<nb(), fm(), dg()>(st, a, P, runs, K, first); });
 }
 bool gru_sweep_eval_ok(const odpd_model_t* m, int B, int T) { return m->bits_w == 0 && gru_uses_eval_kernel(m, B, T, false); }
 template <int NB, int FM, bool DG>
 static int launch_eval_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepRun* runs, int K) {
     const size_t lds = ((size_t)pad4(P) + GruTabs<NB, DG>::kFloats + GruEvalLds<NB>::kFloats) * sizeof(float);
     const int G = a.B;
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)G * K), dim3(64), lds, st, a, runs, G);
-        return (int)hipGetLastError();
-    };
     if constexpr (NB == 2)
-        if (a.H <= 24) return launch(gru_eval_sweep_kernel<NB, FM, DG, true>);
-    return launch(gru_eval_sweep_kernel<NB, FM, DG, false>);
+        if (a.H <= 24) return launch_seq(st, gru_eval_sweep_kernel<NB, FM, DG, true>, G * K, lds, a, runs, G);
+    return launch_seq(st, gru_eval_sweep_kernel<NB, FM, DG, false>, G * K, lds, a, runs, G);
 }
 int gru_sweep_eval(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, const SweepRun* runs, int K) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || !gru_sweep_eval_ok(m, a.B, a.T) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
-    if (R == 1) {
-        if (FM == FEAT_RAW2) return launch_eval_sweep<1, FEAT_RAW2, false>(st, a, P, runs, K);
-        if (FM == FEAT_DGRU6) return launch_eval_sweep<1, FEAT_DGRU6, true>(st, a, P, runs, K);
-        if (FM == FEAT_Q4) return launch_eval_sweep<1, FEAT_Q4, false>(st, a, P, runs, K);
-        return launch_eval_sweep<1, FEAT_A4, false>(st, a, P, runs, K);
-    }
-    if (FM == FEAT_RAW2) return launch_eval_sweep<2, FEAT_RAW2, false>(st, a, P, runs, K);
-    if (FM == FEAT_DGRU6) return launch_eval_sweep<2, FEAT_DGRU6, true>(st, a, P, runs, K);
-    if (FM == FEAT_Q4) return launch_eval_sweep<2, FEAT_Q4, false>(st, a, P, runs, K);
-    return launch_eval_sweep<2, FEAT_A4, false>(st, a, P, runs, K);
+    return gru_nb_dispatch(R, FM, [&](auto nb, auto fm, auto dg) { return launch_eval_sweep<nb(), fm(), dg()>(st, a, P, runs, K); });
 }
 // the frozen-model variant (forward + loss + dL/dx): taken while every sequence of the batch is resident at once
 static size_t gp_fz_lds_bytes(int P, int R, bool DG, int T) {
@@ -1585,21 +1530,16 @@ static bool gru_lossdx_uses_gp(const odpd_model_t* m, int B, int T) {
 template <int R, int FM, bool DG>
 static int launch_gp_lossdx(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = gp_fz_lds_bytes(P, R, DG, a.T);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(gp_fz_grid(P, R, DG, a.B, a.T)), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    const int grid = gp_fz_grid(P, R, DG, a.B, a.T);
     if constexpr (R == 2)
-        if (a.H <= 24) return launch(gru_gp_train_kernel<R, FM, DG, false, true, true>);
-    return launch(gru_gp_train_kernel<R, FM, DG, false, true>);
+        if (a.H <= 24) return launch_seq(st, gru_gp_train_kernel<R, FM, DG, false, true, true>, grid, lds, a);
+    return launch_seq(st, gru_gp_train_kernel<R, FM, DG, false, true>, grid, lds, a);
 }
 int gru_family_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_train_uses_gp(m, a.B, a.T)) { ODPD_GRU_DISPATCH_ALL(launch_gp_train, st, a, P) }
-    ODPD_GRU_DISPATCH_ALL(launch_train, st, a, P)
-    return ODPD_EUNSUPPORTED;
+    if (gru_train_uses_gp(m, a.B, a.T)) return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_gp_train<r(), fm(), dg()>(st, a, P); });
+    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_train<r(), fm(), dg()>(st, a, P); });
 }
 // frozen PA of a cascade: forward + loss + dL/du in one launch; loss rows = (rows, kLossCols)
 int gru_family_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
@@ -1607,9 +1547,8 @@ int gru_family_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
     if (gru_uses_s16n(m, a.B)) return gru_s16x_ok(m) ? gru_s16x_lossdx(st, m, a, gru_s16n_rows(m, a.B)) : gru_s16n_launch(st, m, a, 3);
     if (gru_split_uses_s16(m, a.B)) return gru_s16_lossdx(st, m, a);
-    if (gru_lossdx_uses_gp(m, a.B, a.T)) { ODPD_GRU_DISPATCH_ALL(launch_gp_lossdx, st, a, P) }
-    ODPD_GRU_DISPATCH_ALL(launch_lossdx, st, a, P)
-    return ODPD_EUNSUPPORTED;
+    if (gru_lossdx_uses_gp(m, a.B, a.T)) return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_gp_lossdx<r(), fm(), dg()>(st, a, P); });
+    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_lossdx<r(), fm(), dg()>(st, a, P); });
 }
 int gru_family_lossdx_rows(const odpd_model_t* m, int B, int T) {
     int FM, R, P; bool DG;
@@ -1646,9 +1585,7 @@ int gru_family_rows(const odpd_model_t* m, int B, int which, int T) {
 bool gru_train_uses_s16(const odpd_model_t* m, int B, int T) {
     int FM, R, P; bool DG;
     if (!gru_setup(m, FM, DG, R, P) || R != 1) return false;
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = 16L * 4 * device_cus();   // one 16-sequence wave per SIMD
-    if (B >= min_batch) return true;
+    if (B >= s16_min_batch_or(16L * 4 * device_cus())) return true;   // one 16-sequence wave per SIMD
     return train_shape(P, R, DG, num_groups(B, R), T, nullptr).grid <= 0;   // frame too long for LDS checkpoints
 }
 

@@ -500,7 +500,7 @@ int gru2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!gru2_ok(m) || !gru2_cfg(m, FM)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)gru2_fwd_floats(gru2_P(m, FM), FM == FEAT_DGRU6) * sizeof(float);
 #define ODPD_GRU2_FWD(FM_, DG_) \
-    if (FM == FM_) return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, gru2_fwd_kernel<FM_, DG_, decltype(sv)::value>, lds, a); });
+    if (FM == FM_) return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, gru2_fwd_kernel<FM_, DG_, decltype(sv)::value>, lds, a); });
     ODPD_GRU2_FWD(FEAT_RAW2, false) ODPD_GRU2_FWD(FEAT_DGRU6, true) ODPD_GRU2_FWD(FEAT_Q4, false) ODPD_GRU2_FWD(FEAT_A4, false)
 #undef ODPD_GRU2_FWD
     return ODPD_EUNSUPPORTED;

@@ -876,40 +876,40 @@ int gru_s16_rows(const odpd_model_t* m, int B) {
     return s16_shape(gru_s16_groups(B)).grid;
 }
 
-template <int FM, bool DG, int OCC, bool PACK>
-static int launch_s16(hipStream_t st, const SeqArgs& a, int P) {
-    const LaunchShape ls = s16_shape(a.ngroups);
-    const size_t lds = s16_lds_bytes(P, ls.waves);
-    auto k = gru16_train_kernel<FM, DG, OCC, PACK>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+// OCC / PACK of the fused kernels: f(OCC, PACK) with one wave per SIMD, else two — K-packed where the feature map has two input chunks and
+// hidden <= 13 (three padded K positions free for the r / z chunk-1 slots)
+template <int FM, typename F>
+static int s16_occ_dispatch(const SeqArgs& a, F f) {
+    if (s16_occupancy(a.ngroups) == 1) return f(int_c<1>{}, std::false_type{});
+    if constexpr (S16Cfg<FM>::NCH == 2) { if (a.H <= 13) return f(int_c<2>{}, std::true_type{}); }
+    return f(int_c<2>{}, std::false_type{});
 }
-// frozen PA of a cascade: forward + loss + dL/du in one launch (a.x = u, a.target, a.dx = du, a.partials = loss rows)
-template <int FM, bool DG, int OCC, bool PACK>
-static int launch_s16_lossdx(hipStream_t st, const SeqArgs& a, int P) {
-    const LaunchShape ls = s16_shape(a.ngroups);
-    const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16GroupsDx) + (size_t)ls.waves * (3 * 2 * 16 * kChunkPad + kStageRowFloats)) * sizeof(float);
-    auto k = gru16_train_kernel<FM, DG, OCC, PACK, false, true>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
-}
-template <int FM, bool DG>
-static int launch_s16_lossdx_occ(hipStream_t st, const SeqArgs& a, int P) {
-    constexpr bool kCanPack = S16Cfg<FM>::NCH == 2;
-    if (s16_occupancy(a.ngroups) == 1) return launch_s16_lossdx<FM, DG, 1, false>(st, a, P);
-    if constexpr (kCanPack) { if (a.H <= 13) return launch_s16_lossdx<FM, DG, 2, true>(st, a, P); }
-    return launch_s16_lossdx<FM, DG, 2, false>(st, a, P);
+// the feature map (and with it the fc_hid head, DG): f(FM, DG)
+template <typename F>
+static int s16_feat_dispatch(int FM, F f) {
+    switch (FM) {
+    case FEAT_RAW2: return f(int_c<FEAT_RAW2>{}, std::false_type{});
+    case FEAT_DGRU6: return f(int_c<FEAT_DGRU6>{}, std::true_type{});
+    case FEAT_Q4: return f(int_c<FEAT_Q4>{}, std::false_type{});
+    case FEAT_A4: return f(int_c<FEAT_A4>{}, std::false_type{});
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
 template <int FM, bool DG>
 static int launch_s16_occ(hipStream_t st, const SeqArgs& a, int P) {
-    // K-packing: two input chunks and hidden <= 13 (three padded K positions free for the r / z chunk-1 slots)
-    constexpr bool kCanPack = S16Cfg<FM>::NCH == 2;
-    const bool pack = kCanPack && a.H <= 13;
-    if (s16_occupancy(a.ngroups) == 1) return launch_s16<FM, DG, 1, false>(st, a, P);
-    if constexpr (kCanPack) { if (pack) return launch_s16<FM, DG, 2, true>(st, a, P); }
-    return launch_s16<FM, DG, 2, false>(st, a, P);
+    const LaunchShape ls = s16_shape(a.ngroups);
+    return s16_occ_dispatch<FM>(a, [&](auto occ, auto pack) {
+        return launch_lds(st, gru16_train_kernel<FM, DG, occ(), pack()>, ls.grid, 64 * ls.waves, s16_lds_bytes(P, ls.waves), a);
+    });
+}
+// frozen PA of a cascade: forward + loss + dL/du in one launch (a.x = u, a.target, a.dx = du, a.partials = loss rows)
+template <int FM, bool DG>
+static int launch_s16_lossdx_occ(hipStream_t st, const SeqArgs& a, int P) {
+    const LaunchShape ls = s16_shape(a.ngroups);
+    const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16GroupsDx) + (size_t)ls.waves * (3 * 2 * 16 * kChunkPad + kStageRowFloats)) * sizeof(float);
+    return s16_occ_dispatch<FM>(a, [&](auto occ, auto pack) {
+        return launch_lds(st, gru16_train_kernel<FM, DG, occ(), pack(), false, true>, ls.grid, 64 * ls.waves, lds, a);
+    });
 }
 
 // ---- split kernels: launch shapes -----------------------------------------------------------------
@@ -943,11 +943,7 @@ template <int FM, bool DG>
 static int launch_s16_fwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = s16_fwd_shape(a.ngroups);
     const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16Groups) + (size_t)ls.waves * 2 * 2 * 16 * kChunkPad) * sizeof(float);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_lds(st, k, ls.grid, 64 * ls.waves, lds, a); };
     if constexpr (S16Cfg<FM>::NCH == 2) { if (a.H <= 13) return launch(gru16_fwd_kernel<FM, DG, true>); }   // K-packing
     return launch(gru16_fwd_kernel<FM, DG, false>);
 }
@@ -960,28 +956,16 @@ static int launch_s16_bwd(hipStream_t st, const SeqArgs& a, int P) {
     const int wave_floats = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? kS16Tiles * kTileFloats : 0);
     size_t lds = ((size_t)pad4(P) + s16_tab_floats(DX ? kS16GroupsDx : kS16Groups) + (size_t)waves * wave_floats) * sizeof(float);
     if (NW && lds < reduce_scratch_bytes(P, waves)) lds = reduce_scratch_bytes(P, waves);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * waves), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_lds(st, k, ls.grid, 64 * waves, lds, a); };
     // K-packing (as the fused train kernel): the weight-gradient-only backward of a trained DPD with <= 13 units
     if constexpr (S16Cfg<FM>::NCH == 2 && NW && !DX) { if (a.H <= 13) return launch(gru16_bwd_kernel<FM, DG, NW, DX, WAVES, true>); }
     return launch(gru16_bwd_kernel<FM, DG, NW, DX, WAVES>);
 }
 template <int FM, bool DG>
 static int launch_s16_bwd_mode(hipStream_t st, const SeqArgs& a, int P) {
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_s16_bwd<FM, DG, true, true, 4>(st, a, P);
-    if (nw) return launch_s16_bwd<FM, DG, true, false, 8>(st, a, P);
-    if (dx) return launch_s16_bwd<FM, DG, false, true, 8>(st, a, P);
-    return ODPD_EINVAL;
+    // WAVES: both outputs leave LDS for one wave per SIMD, one output for two
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_s16_bwd<FM, DG, nw(), dx(), (nw() && dx()) ? 4 : 8>(st, a, P); });
 }
-#define ODPD_S16_DISPATCH(FN, ...)                                                   \
-    if (FM == FEAT_RAW2) return FN<FEAT_RAW2, false>(__VA_ARGS__);                   \
-    if (FM == FEAT_DGRU6) return FN<FEAT_DGRU6, true>(__VA_ARGS__);                  \
-    if (FM == FEAT_Q4) return FN<FEAT_Q4, false>(__VA_ARGS__);                       \
-    return FN<FEAT_A4, false>(__VA_ARGS__);
 
 int gru_s16_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
@@ -989,7 +973,7 @@ int gru_s16_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
     const int P = s16_param_count(m->hidden, FM, DG);
-    ODPD_S16_DISPATCH(launch_s16_fwd, st, a, P)
+    return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_fwd<fm(), dg()>(st, a, P); });
 }
 int gru_s16_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
@@ -997,7 +981,7 @@ int gru_s16_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
     const int P = s16_param_count(m->hidden, FM, DG);
-    ODPD_S16_DISPATCH(launch_s16_bwd_mode, st, a, P)
+    return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_bwd_mode<fm(), dg()>(st, a, P); });
 }
 
 int gru_s16_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
@@ -1007,25 +991,15 @@ int gru_s16_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
     const int P = s16_param_count(m->hidden, FM, DG);
-    ODPD_S16_DISPATCH(launch_s16_lossdx_occ, st, a, P)
+    return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_lossdx_occ<fm(), dg()>(st, a, P); });
 }
 
-template <int FM, bool DG, int OCC, bool PACK>
-static int launch_s16_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepRun* runs, int K, long long first) {
-    const LaunchShape ls = s16_shape(a.ngroups);
-    const size_t lds = s16_lds_bytes(P, ls.waves);
-    auto k = gru16_train_sweep_kernel<FM, DG, OCC, PACK>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)ls.grid * K), dim3(64 * ls.waves), lds, st, a, runs, ls.grid, first);
-    return (int)hipGetLastError();
-}
 template <int FM, bool DG>
 static int launch_s16_sweep_occ(hipStream_t st, const SeqArgs& a, int P, const SweepRun* runs, int K, long long first) {
-    constexpr bool kCanPack = S16Cfg<FM>::NCH == 2;
-    const bool pack = kCanPack && a.H <= 13;
-    if (s16_occupancy(a.ngroups) == 1) return launch_s16_sweep<FM, DG, 1, false>(st, a, P, runs, K, first);      // (as launch_s16_occ chooses for this batch)
-    if constexpr (kCanPack) { if (pack) return launch_s16_sweep<FM, DG, 2, true>(st, a, P, runs, K, first); }
-    return launch_s16_sweep<FM, DG, 2, false>(st, a, P, runs, K, first);
+    const LaunchShape ls = s16_shape(a.ngroups);
+    return s16_occ_dispatch<FM>(a, [&](auto occ, auto pack) {
+        return launch_lds(st, gru16_train_sweep_kernel<FM, DG, occ(), pack()>, ls.grid * K, 64 * ls.waves, s16_lds_bytes(P, ls.waves), a, runs, ls.grid, first);
+    });
 }
 bool gru_s16_sweep_ok(const odpd_model_t* m) {
     int FM; bool DG;
@@ -1037,10 +1011,7 @@ int gru_s16_sweep_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
     const int P = s16_param_count(m->hidden, FM, DG);
-    if (FM == FEAT_RAW2) return launch_s16_sweep_occ<FEAT_RAW2, false>(st, a, P, runs, K, first);
-    if (FM == FEAT_DGRU6) return launch_s16_sweep_occ<FEAT_DGRU6, true>(st, a, P, runs, K, first);
-    if (FM == FEAT_Q4) return launch_s16_sweep_occ<FEAT_Q4, false>(st, a, P, runs, K, first);
-    return launch_s16_sweep_occ<FEAT_A4, false>(st, a, P, runs, K, first);
+    return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_sweep_occ<fm(), dg()>(st, a, P, runs, K, first); });
 }
 
 int gru_s16_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
@@ -1050,10 +1021,7 @@ int gru_s16_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
     const int P = s16_param_count(m->hidden, FM, DG);
-    if (FM == FEAT_RAW2) return launch_s16_occ<FEAT_RAW2, false>(st, a, P);
-    if (FM == FEAT_DGRU6) return launch_s16_occ<FEAT_DGRU6, true>(st, a, P);
-    if (FM == FEAT_Q4) return launch_s16_occ<FEAT_Q4, false>(st, a, P);
-    return launch_s16_occ<FEAT_A4, false>(st, a, P);
+    return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_occ<fm(), dg()>(st, a, P); });
 }
 
 }  // namespace odpd

@@ -625,21 +625,14 @@ static int launch_s16n(hipStream_t st, const SeqArgs& a, int P) {
     }
     if (lds > kMaxLds) { ls.waves = 2; lds = bytes(2); }      // weight gradients + dL/dx in one launch: two waves per CU
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = gru16n_kernel<FM, DG, NT, MODE, NW, DX, NCK>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru16n_kernel<FM, DG, NT, MODE, NW, DX, NCK>, ls.grid, 64 * ls.waves, lds, a);
 }
 template <int FM, bool DG, int NT, int NCK>
 static int launch_s16n_mode(hipStream_t st, const SeqArgs& a, int P, int mode) {
     if (mode == 0) return launch_s16n<FM, DG, NT, 0, true, false, NCK>(st, a, P);
     if (mode == 3) return launch_s16n<FM, DG, NT, 0, false, true, NCK>(st, a, P);      // forward + loss + dL/dx (frozen PA)
     if (mode == 1) return launch_s16n<FM, DG, NT, 1, false, false, NCK>(st, a, P);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_s16n<FM, DG, NT, 2, true, true, NCK>(st, a, P);
-    if (nw) return launch_s16n<FM, DG, NT, 2, true, false, NCK>(st, a, P);
-    if (dx) return launch_s16n<FM, DG, NT, 2, false, true, NCK>(st, a, P);
-    return ODPD_EINVAL;
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_s16n<FM, DG, NT, 2, nw(), dx(), NCK>(st, a, P); });
 }
 // hidden 17..24: the last unit tile holds <= 8 units = two K-chunks (instantiated: 2 and 4 chunks)
 template <int FM, bool DG, int NT>

@@ -1260,10 +1260,7 @@ static int launch_s16x(hipStream_t st, const SeqArgs& a, int P, int grid) {
     if (body < (size_t)pad4(P)) body = pad4(P);
     const size_t lds = ((size_t)s16_tab_floats(T::NG) + body) * sizeof(float);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = gru16x_lossdx_kernel<FM, DG, 6, kS16xStride>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru16x_lossdx_kernel<FM, DG, 6, kS16xStride>, grid, 512, lds, a);
 }
 bool gru_s16x_train_ok(const odpd_model_t* m) { return gru_s16x_ok(m) && tuning().s16x_train != 0; }
 template <int FM, bool DG>
@@ -1275,10 +1272,7 @@ static int launch_s16x_train(hipStream_t st, const SeqArgs& a, int P, int grid) 
     size_t lds = ((size_t)s16_tab_floats(T::NG) + body) * sizeof(float);
     if (lds < reduce_scratch_bytes(P, kWaves)) lds = reduce_scratch_bytes(P, kWaves);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = gru16x_train_kernel<FM, DG, 6, kS16xStride>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * kWaves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru16x_train_kernel<FM, DG, 6, kS16xStride>, grid, 64 * kWaves, lds, a);
 }
 // fused train step (forward + loss + BPTT with weight gradients); one row of partials per workgroup, grid = gru_s16n_rows(m, B): the same rows
 // (and row layout) as gru16n_kernel's train flavour, so the reduction / optimiser launches behind it are unchanged
@@ -1304,10 +1298,7 @@ static int launch_s16x_fwd(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = ((size_t)s16_tab_floats(T::NG) + body) * sizeof(float);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
     const int need = (a.ngroups + kWaves - 1) / kWaves, cap = device_cus();
-    auto k = gru16x_fwd_kernel<FM, DG, 6, kS16xStride>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(need < cap ? need : cap), dim3(64 * kWaves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru16x_fwd_kernel<FM, DG, 6, kS16xStride>, need < cap ? need : cap, 64 * kWaves, lds, a);
 }
 int gru_s16x_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
@@ -1332,18 +1323,11 @@ static int launch_s16x_bwd(hipStream_t st, const SeqArgs& a, int P, int rows) {
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
     const int need = (a.ngroups + kWaves - 1) / kWaves, cap = device_cus();
     const int grid = NW ? rows : (need < cap ? need : cap);      // (with parameter gradients: one row per workgroup, the host's row count)
-    auto k = gru16x_bwd_kernel<FM, DG, 6, kS16xStride, NW, DX>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * kWaves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, gru16x_bwd_kernel<FM, DG, 6, kS16xStride, NW, DX>, grid, 64 * kWaves, lds, a);
 }
 template <int FM, bool DG>
 static int launch_s16x_bwd_mode(hipStream_t st, const SeqArgs& a, int P, int rows) {
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch_s16x_bwd<FM, DG, true, true>(st, a, P, rows);
-    if (nw) return launch_s16x_bwd<FM, DG, true, false>(st, a, P, rows);
-    if (dx) return launch_s16x_bwd<FM, DG, false, true>(st, a, P, rows);
-    return ODPD_EINVAL;
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_s16x_bwd<FM, DG, nw(), dx()>(st, a, P, rows); });
 }
 // rows = gru_s16n_rows(m, B): the partial rows the host reduces (the exact kernels' count)
 int gru_s16x_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int rows) {

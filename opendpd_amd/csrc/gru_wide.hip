@@ -463,7 +463,7 @@ int wide_gru_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!wide_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)wide_fwd_floats(wide_P(m, FM, DG), DG, m->hidden) * sizeof(float);
 #define ODPD_WIDE_FWD(FM_, DG_) \
-    if (FM == FM_) return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, wide_gru_fwd_kernel<FM_, DG_, decltype(sv)::value, S0>, lds, a); });
+    if (FM == FM_) return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, wide_gru_fwd_kernel<FM_, DG_, decltype(sv)::value, S0>, lds, a); });
     ODPD_WIDE_FWD(FEAT_RAW2, false) ODPD_WIDE_FWD(FEAT_DGRU6, true) ODPD_WIDE_FWD(FEAT_Q4, false) ODPD_WIDE_FWD(FEAT_A4, false)
 #undef ODPD_WIDE_FWD
     return ODPD_EUNSUPPORTED;

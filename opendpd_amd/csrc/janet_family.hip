@@ -593,53 +593,31 @@ bool janet_train_uses_gp(const odpd_model_t* m, int B, int T) {
     return gp_batch_fits(B, janet_gp_blocks_per_cu(janet_layout(m->hidden).P, T), 2);
 }
 int janet_gp_rows(const odpd_model_t* m, int B, int T) {
-    const int P = janet_layout(m->hidden).P;
-    const long cap = (long)device_cus() * (kMaxLds / janet_gp_lds_bytes(P, T));
-    return B < cap ? B : (int)cap;
+    return gp_rows(B, (int)(kMaxLds / janet_gp_lds_bytes(janet_layout(m->hidden).P, T)));
 }
 int janet_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const int P = janet_layout(m->hidden).P;
     const size_t lds = janet_gp_lds_bytes(P, a.T);
-    if (int e = allow_big_lds(janet_gp_train_kernel, lds)) return e;
-    hipLaunchKernelGGL(janet_gp_train_kernel, dim3(janet_gp_rows(m, a.B, a.T)), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_seq(st, janet_gp_train_kernel, janet_gp_rows(m, a.B, a.T), lds, a);
 }
 int janet_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (m->hidden > 16) return ODPD_EUNSUPPORTED;
     if (janet_uses_s16(m, a.B)) return janet_s16_launch(st, m, a, 1);
     const int P = janet_layout(m->hidden).P;
-    if (a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0) {     // sequences that each get a SIMD of their own (inference / checkpoint-writing forward)
+    if (gp_eval_batch_fits(a.B)) {     // sequences that each get a SIMD of their own (inference / checkpoint-writing forward)
         const size_t lds = ((size_t)pad4(P) + kJTabFloats + kEvalChunk * 4 + kEvalChunk * kJEvalHistStride + 32) * sizeof(float);
-        auto launch = [&](auto k) {
-            if (int e = allow_big_lds(k, lds)) return e;
-            hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a);
-            return (int)hipGetLastError();
-        };
-        return a.ckpt ? launch(janet_eval_kernel<true>) : launch(janet_eval_kernel<false>);
+        return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, janet_eval_kernel<sv()>, a.B, lds, a); });
     }
     const LaunchShape ls = persistent_shape(a.ngroups, 16);
     const size_t lds = janet_lds_bytes(P, ls.waves, false);
-    auto k = janet_fwd_kernel<0>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, janet_fwd_kernel<0>, ls.grid, 64 * ls.waves, lds, a);
 }
 int janet_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (m->hidden > 16) return ODPD_EUNSUPPORTED;
     if (janet_uses_s16(m, a.B)) return janet_s16_launch(st, m, a, 2);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (!nw && !dx) return ODPD_EINVAL;
-    const int P = janet_layout(m->hidden).P;
     const LaunchShape ls = janet_bwd_shape(a.ngroups);
-    const size_t lds = janet_lds_bytes(P, ls.waves, nw);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
-    };
-    if (nw && dx) return launch(janet_bwd_kernel<true, true>);
-    if (nw) return launch(janet_bwd_kernel<true, false>);
-    return launch(janet_bwd_kernel<false, true>);
+    const size_t lds = janet_lds_bytes(janet_layout(m->hidden).P, ls.waves, a.partials != nullptr);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_lds(st, janet_bwd_kernel<nw(), dx()>, ls.grid, 64 * ls.waves, lds, a); });
 }
 int janet_family_rows(const odpd_model_t* m, int B) {
     if (m->hidden > 16) return ODPD_EUNSUPPORTED;

@@ -439,9 +439,7 @@ __global__ __launch_bounds__(256, 1) void janet16_bwd_kernel(SeqArgs a) {
 // -------------------------------------------------------------------------------------------------
 bool janet_uses_s16(const odpd_model_t* m, int B) {
     if (m->backbone != ODPD_PGJANET || m->hidden > 16) return false;
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = 16L * 4 * device_cus();
-    return B >= min_batch;
+    return B >= s16_min_batch_or(16L * 4 * device_cus());
 }
 int janet_s16_rows(const odpd_model_t* m, int B) {
     (void)m;

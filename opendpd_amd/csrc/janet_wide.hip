@@ -309,7 +309,7 @@ int pgjanet_wide_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int pgjanet_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_wide_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)jw_fwd_floats(janet_layout(m->hidden).P) * sizeof(float);
-    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, wide_pgjanet_fwd_kernel<decltype(sv)::value>, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, wide_pgjanet_fwd_kernel<decltype(sv)::value>, lds, a); });
 }
 int pgjanet_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_wide_ok(m)) return ODPD_EUNSUPPORTED;

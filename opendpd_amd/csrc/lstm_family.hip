@@ -1153,48 +1153,35 @@ template <int R, bool VD>
 static int lstm_launch_fwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = persistent_shape(a.ngroups, R == 1 ? 16 : 8);
     const size_t lds = lstm_lds_bytes(P, R, ls.waves, 2 * ((4 / R) * kHaloStride + (4 / R) * kChunkPad), false);
-    auto k = lstm_fwd_kernel<R, VD>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, lstm_fwd_kernel<R, VD>, ls.grid, 64 * ls.waves, lds, a);
 }
 template <int NB, bool VD>
 static int lstm_launch_eval(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = ((size_t)pad4(P) + LstmTabs<NB>::kFloats + LstmEvalLds<NB>::kFloats) * sizeof(float);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
-    if (a.bits_w > 0) return a.ckpt ? launch(lstm_eval_kernel<NB, VD, true, true>) : launch(lstm_eval_kernel<NB, VD, false, true>);
-    return a.ckpt ? launch(lstm_eval_kernel<NB, VD, true>) : launch(lstm_eval_kernel<NB, VD, false>);
+    if (a.bits_w > 0) return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, lstm_eval_kernel<NB, VD, sv(), true>, a.B, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, lstm_eval_kernel<NB, VD, sv()>, a.B, lds, a); });
 }
 template <int R, bool VD, bool NW, bool DX>
 static int lstm_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = lstm_bwd_shape(R, VD, a.ngroups);
     const size_t lds = lstm_lds_bytes(P, R, ls.waves, 2 * ((4 / R) * kHaloStride + 2 * (4 / R) * kChunkPad), NW);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-        return (int)hipGetLastError();
-    };
-    if (a.bits_w > 0) return launch(lstm_bwd_kernel<R, VD, NW, DX, true>);
-    return launch(lstm_bwd_kernel<R, VD, NW, DX>);
+    if (a.bits_w > 0) return launch_lds(st, lstm_bwd_kernel<R, VD, NW, DX, true>, ls.grid, 64 * ls.waves, lds, a);
+    return launch_lds(st, lstm_bwd_kernel<R, VD, NW, DX>, ls.grid, 64 * ls.waves, lds, a);
 }
 template <int R, bool VD>
 static int lstm_launch_bwd_mode(hipStream_t st, const SeqArgs& a, int P) {
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
+    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;      // (not s16_bwd_dispatch: its order would lay the three kernels out in another order)
     if (nw && !dx) return lstm_launch_bwd<R, VD, true, false>(st, a, P);
     if (!nw && dx) return lstm_launch_bwd<R, VD, false, true>(st, a, P);
     if (nw && dx) return lstm_launch_bwd<R, VD, true, true>(st, a, P);
     return ODPD_EINVAL;
 }
-
-#define ODPD_LSTM_DISPATCH(FN, ...)                                   \
-    if (R == 1 && !vd) return FN<1, false>(__VA_ARGS__);               \
-    if (R == 2 && !vd) return FN<2, false>(__VA_ARGS__);               \
-    if (R == 1 && vd) return FN<1, true>(__VA_ARGS__);                 \
-    if (R == 2 && vd) return FN<2, true>(__VA_ARGS__);
+// the kernels' template axes from the model: f(R, VD) as integral constants
+template <typename F>
+static int lstm_dispatch(int R, bool vd, F f) {
+    auto rows = [&](auto v) { return R == 1 ? f(int_c<1>{}, v) : R == 2 ? f(int_c<2>{}, v) : ODPD_EUNSUPPORTED; };
+    return !vd ? rows(std::false_type{}) : rows(std::true_type{});      // (the order the kernels are instantiated in)
+}
 
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, BPTT state of the whole frame in LDS
 static size_t lstm_gp_lds_bytes(int P, bool vd, int T, bool pg) {
@@ -1214,8 +1201,7 @@ int lstm_gp_rows(const odpd_model_t* m, int B, int T) {
     const bool vd = m->backbone == ODPD_VDLSTM;
     const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
     const bool pg = lstm_gp_parks_gates(P, vd, B, T);
-    const long cap = (long)device_cus() * (kMaxLds / lstm_gp_lds_bytes(P, vd, T, pg));
-    return B < cap ? B : (int)cap;
+    return gp_rows(B, (int)(kMaxLds / lstm_gp_lds_bytes(P, vd, T, pg)));
 }
 int lstm_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool vd = m->backbone == ODPD_VDLSTM;
@@ -1223,11 +1209,7 @@ int lstm_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const bool pg = lstm_gp_parks_gates(P, vd, a.B, a.T);
     const size_t lds = lstm_gp_lds_bytes(P, vd, a.T, pg);
     const int grid = lstm_gp_rows(m, a.B, a.T);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-        return (int)hipGetLastError();
-    };
+    auto launch = [&](auto k) { return launch_seq(st, k, grid, lds, a); };
     if (vd && m->bits_w > 0) return pg ? launch(lstm_gp_train_kernel<true, true, true>) : launch(lstm_gp_train_kernel<true, false, true>);
     if (vd) return pg ? launch(lstm_gp_train_kernel<true, true>) : launch(lstm_gp_train_kernel<true, false>);
     if (m->bits_w > 0) return pg ? launch(lstm_gp_train_kernel<false, true, true>) : launch(lstm_gp_train_kernel<false, false, true>);
@@ -1240,9 +1222,8 @@ int lstm_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (vd && a.T < kHalo) return ODPD_EINVAL;
     const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
     // sequences that each get a SIMD of their own (inference, and the checkpoint-writing forward of the split train path): the gate-parallel kernel
-    if (m->bits_w > 0 || (a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0)) { ODPD_LSTM_DISPATCH(lstm_launch_eval, st, a, P) }
-    ODPD_LSTM_DISPATCH(lstm_launch_fwd, st, a, P)
-    return ODPD_EUNSUPPORTED;
+    if (m->bits_w > 0 || gp_eval_batch_fits(a.B)) return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_eval<r(), v()>(st, a, P); });
+    return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_fwd<r(), v()>(st, a, P); });
 }
 int lstm_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const int R = rows_per_seq(m->hidden);
@@ -1250,8 +1231,7 @@ int lstm_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!R) return ODPD_EUNSUPPORTED;
     if (vd && a.T < kHalo) return ODPD_EINVAL;
     const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
-    ODPD_LSTM_DISPATCH(lstm_launch_bwd_mode, st, a, P)
-    return ODPD_EUNSUPPORTED;
+    return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_bwd_mode<r(), v()>(st, a, P); });
 }
 int lstm_family_rows(const odpd_model_t* m, int B) {
     const int R = rows_per_seq(m->hidden);

@@ -279,7 +279,7 @@ int lstm2_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int lstm2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm2_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)lstm2_fwd_floats(lstm2_layout(m->hidden).P) * sizeof(float);
-    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, lstm2_fwd_kernel<decltype(sv)::value>, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, lstm2_fwd_kernel<decltype(sv)::value>, lds, a); });
 }
 int lstm2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!lstm2_ok(m)) return ODPD_EUNSUPPORTED;

@@ -615,9 +615,7 @@ static LaunchShape l16_shape(int ngroups, int nt = 2) {
 bool lstm_train_uses_s16(const odpd_model_t* m, int B) {
     if ((m->backbone != ODPD_LSTM && m->backbone != ODPD_VDLSTM) || m->hidden > 32) return false;
     if (m->bits_w > 0) return false;      // quantised heads (`--quant`): lstm_family.hip's kernels at every batch size
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = (m->hidden <= 16 ? 16L : 8L) * 4 * device_cus();
-    return B >= min_batch;
+    return B >= s16_min_batch_or((m->hidden <= 16 ? 16L : 8L) * 4 * device_cus());
 }
 int lstm_s16_rows(const odpd_model_t* m, int B) {
     return l16_shape((B + 15) / 16, (m->hidden + 15) / 16).grid;
@@ -636,10 +634,7 @@ static int launch_l16(hipStream_t st, const SeqArgs& a, int P) {
     size_t lds = ((size_t)s16_tab_floats(T::NG) + body) * sizeof(float);
     if (lds < reduce_scratch_bytes(P, ls.waves)) lds = reduce_scratch_bytes(P, ls.waves);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto k = lstm16_train_kernel<VD, NT, PK>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a);
-    return (int)hipGetLastError();
+    return launch_lds(st, lstm16_train_kernel<VD, NT, PK>, ls.grid, 64 * ls.waves, lds, a);
 }
 int lstm_s16_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     if (!a0.ckpt) return ODPD_EINVAL;

@@ -295,7 +295,7 @@ namespace {
 template <bool S0>
 int wide_lstm_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     const size_t lds = (size_t)lstmw_fwd_floats(lstm_layout(m->hidden, 0, m->bits_w > 0).P) * sizeof(float);
-    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, wide_lstm_fwd_kernel<decltype(sv)::value, S0>, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, wide_lstm_fwd_kernel<decltype(sv)::value, S0>, lds, a); });
 }
 template <bool S0>
 int wide_lstm_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {

@@ -82,10 +82,4 @@ __device__ __forceinline__ void s16_reduce_rows(const float* smem, float* prow, 
 // ---- host side ---------------------------------------------------------------------------------
 // forward: four-wave workgroups until every CU has four of them, eight-wave ones beyond
 static inline LaunchShape s16_fwd_shape(int ngroups) { return s16_group_shape(ngroups, ngroups <= 4 * device_cus() ? 4 : 8); }
-// a forward without checkpoints on few sequences goes to the backbone's evaluation kernel, where each gets a SIMD of its own
-// (either knob at 0 keeps it on the 16-sequences-per-wave kernel)
-static inline bool gp_eval_fits(const SeqArgs& a, int mode) {
-    return mode == 1 && !a.ckpt && a.B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0;
-}
-
 }  // namespace odpd

@@ -85,6 +85,13 @@ inline int gp_rows(int B, int per_cu) {
     const long cap = (long)device_cus() * per_cu;
     return B < cap ? B : (int)cap;
 }
+// the one-sequence-per-wave evaluation kernels: every sequence of the batch gets a SIMD of its own, and neither knob pins another path
+inline bool gp_eval_batch_fits(int B) { return B <= 2 * device_cus() && tuning().s16_min_batch != 0 && tuning().gp_max_batch != 0; }
+// batch size from which the 16-sequences-per-wave kernels take over: the "s16_min_batch" knob where it is set, else the file's measured crossover
+inline long s16_min_batch_or(long builtin) {
+    const long min_batch = tuning().s16_min_batch;
+    return min_batch < 0 ? builtin : min_batch;
+}
 
 // ---- parameter layouts (flattened named_parameters() order of the reference modules) -------------
 struct GruLayout {
@@ -188,6 +195,14 @@ static inline int s16_bwd_dispatch(const SeqArgs& a, F launch) {
     if (nw) return launch(std::true_type{}, std::false_type{});
     return launch(std::false_type{}, std::true_type{});
 }
+// the two instantiations of a sequence forward: launch(SAVE), with or without the records the backward reads
+template <typename F>
+static inline int ckpt_dispatch(const SeqArgs& a, F launch) {
+    return a.ckpt ? launch(std::true_type{}) : launch(std::false_type{});
+}
+// the evaluation kernel (gp_eval_batch_fits) serves a forward (mode 1) that writes no checkpoints
+inline bool gp_eval_fits(const SeqArgs& a, int mode) { return mode == 1 && !a.ckpt && gp_eval_batch_fits(a.B); }
+template <int V> using int_c = std::integral_constant<int, V>;      // a template argument chosen at run time, handed to a generic lambda
 
 // one run of a lockstep sweep (K independent runs of one model shape advancing together: odpd_train_epoch_sweep, odpd_backbone_fwd_sweep);
 // the table lives in device memory, a sweep kernel's workgroup picks its entry by blockIdx.x / G

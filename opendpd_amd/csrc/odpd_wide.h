@@ -72,10 +72,5 @@ static inline int wide_launch(hipStream_t st, K kernel, size_t lds, const SeqArg
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;      // (vdlstm's and the delta backbones' dL/dx grows with the frame)
     return launch_seq(st, kernel, wide_rows(a.B), lds, a);
 }
-// the forward's two instantiations: launch(SAVE) with the per-step records for a backward pass, or without
-template <typename F>
-static inline int wide_fwd_dispatch(const SeqArgs& a, F launch) {
-    return a.ckpt ? launch(std::true_type{}) : launch(std::false_type{});
-}
 
 }  // namespace odpd

@@ -369,24 +369,16 @@ int pgjanet_q_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_q_ok(m)) return ODPD_EUNSUPPORTED;
     const size_t lds = (size_t)pgq_fwd_floats(pgq_layout(m->hidden).P) * sizeof(float);
     const int grid = pgjanet_q_rows(m, a.B);
-    if (m->hidden <= 16) return a.ckpt ? launch_seq(st, pgq_fwd_kernel<16, true>, grid, lds, a) : launch_seq(st, pgq_fwd_kernel<16, false>, grid, lds, a);
-    return a.ckpt ? launch_seq(st, pgq_fwd_kernel<32, true>, grid, lds, a) : launch_seq(st, pgq_fwd_kernel<32, false>, grid, lds, a);
+    if (m->hidden <= 16) return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, pgq_fwd_kernel<16, sv()>, grid, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, pgq_fwd_kernel<32, sv()>, grid, lds, a); });
 }
 int pgjanet_q_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!pgjanet_q_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
     const size_t lds = (size_t)pgq_bwd_floats(pgq_layout(m->hidden).P) * sizeof(float);
     const int grid = pgjanet_q_rows(m, a.B);
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-#define ODPD_PGQ_BWD(HP_)                                                                           \
-    {                                                                                              \
-        if (nw && dx) return launch_seq(st, pgq_bwd_kernel<HP_, true, true>, grid, lds, a);         \
-        if (nw) return launch_seq(st, pgq_bwd_kernel<HP_, true, false>, grid, lds, a);              \
-        return launch_seq(st, pgq_bwd_kernel<HP_, false, true>, grid, lds, a);                      \
-    }
-    if (m->hidden <= 16) ODPD_PGQ_BWD(16)
-    ODPD_PGQ_BWD(32)
-#undef ODPD_PGQ_BWD
+    if (m->hidden <= 16) return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_seq(st, pgq_bwd_kernel<16, nw(), dx()>, grid, lds, a); });
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_seq(st, pgq_bwd_kernel<32, nw(), dx()>, grid, lds, a); });
 }
 
 }  // namespace odpd

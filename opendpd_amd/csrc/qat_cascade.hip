@@ -191,11 +191,6 @@ template <typename D> size_t lds_of(int pv, bool dgp, int T, int Pd, int Pp) {
 #undef ODPD_QAT_PA
     return 0;
 }
-template <typename K> int launch_k(hipStream_t st, K k, int grid, size_t lds, const CascArgs& a) {
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(128), lds, st, a);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
 namespace {
@@ -218,7 +213,7 @@ int qat_casc_launch(hipStream_t st, const odpd_model_t* dpd, int pv, bool dgp, i
     const QSel s = qsel(dpd);
     const size_t lds = qat_casc_lds_bytes(dpd, pv, dgp, a.T, Pp);
     if (lds == 0 || grid <= 0) return ODPD_EUNSUPPORTED;
-#define ODPD_QAT_PA(MK_, LUT_, NBD_, PV_, FMP_, DGP_) if (pv == PV_ && dgp == DGP_) return launch_k(st, qat_cascade_kernel<MK_, LUT_, NBD_, PV_, FMP_, DGP_>, grid, lds, a);
+#define ODPD_QAT_PA(MK_, LUT_, NBD_, PV_, FMP_, DGP_) if (pv == PV_ && dgp == DGP_) return launch_lds(st, qat_cascade_kernel<MK_, LUT_, NBD_, PV_, FMP_, DGP_>, grid, 128, lds, a);
 #define ODPD_QAT_ALLPA(MK_, LUT_, NBD_)                                                                                                   \
     ODPD_QAT_PA(MK_, LUT_, NBD_, 0, FEAT_RAW2, false) ODPD_QAT_PA(MK_, LUT_, NBD_, 1, FEAT_RAW2, false) ODPD_QAT_PA(MK_, LUT_, NBD_, 2, FEAT_RAW2, false) \
     ODPD_QAT_PA(MK_, LUT_, NBD_, 0, FEAT_DGRU6, true) ODPD_QAT_PA(MK_, LUT_, NBD_, 1, FEAT_DGRU6, true) ODPD_QAT_PA(MK_, LUT_, NBD_, 2, FEAT_DGRU6, true)
@@ -232,7 +227,7 @@ int qat_casc_launch(hipStream_t st, const odpd_model_t* dpd, int pv, bool dgp, i
 #undef ODPD_QAT_ALLPA
 #undef ODPD_QAT_PA
     if (s.tres) {
-#define ODPD_QAT_PA(LUT_, PV_, FMP_, DGP_) if (pv == PV_ && dgp == DGP_) return launch_k(st, qat_delta_cascade_kernel<LUT_, PV_, FMP_, DGP_>, grid, lds, a);
+#define ODPD_QAT_PA(LUT_, PV_, FMP_, DGP_) if (pv == PV_ && dgp == DGP_) return launch_lds(st, qat_delta_cascade_kernel<LUT_, PV_, FMP_, DGP_>, grid, 128, lds, a);
 #define ODPD_QAT_ALLPA(LUT_)                                                                                          \
     ODPD_QAT_PA(LUT_, 0, FEAT_RAW2, false) ODPD_QAT_PA(LUT_, 1, FEAT_RAW2, false) ODPD_QAT_PA(LUT_, 2, FEAT_RAW2, false) \
     ODPD_QAT_PA(LUT_, 0, FEAT_DGRU6, true) ODPD_QAT_PA(LUT_, 1, FEAT_DGRU6, true) ODPD_QAT_PA(LUT_, 2, FEAT_DGRU6, true)
@@ -245,19 +240,16 @@ int qat_casc_launch(hipStream_t st, const odpd_model_t* dpd, int pv, bool dgp, i
 
 // evaluation passes of the quantised models on the one-sequence-per-wave engines: no checkpoints asked for, every sequence on a SIMD of its own
 bool qat_uses_gp_eval(const odpd_model_t* m, int B, bool want_ckpt) {
-    if (want_ckpt || m->bits_w <= 0 || m->bits_a <= 0 || m->hidden < 1 || m->hidden > (m->backbone == ODPD_TRES_DELTAGRU ? 16 : 32) || tuning().gp_max_batch == 0 || tuning().s16_min_batch == 0) return false;
+    if (want_ckpt || m->bits_w <= 0 || m->bits_a <= 0 || m->hidden < 1 || m->hidden > (m->backbone == ODPD_TRES_DELTAGRU ? 16 : 32)) return false;
     if (m->backbone != ODPD_GRU && m->backbone != ODPD_QGRU && m->backbone != ODPD_QGRU_AMP1 && m->backbone != ODPD_TRES_DELTAGRU && m->backbone != ODPD_DGRU)
         return false;
-    return B <= 2 * device_cus();
+    return gp_eval_batch_fits(B);
 }
 namespace {
 template <typename E, bool TRES>
 int qat_eval_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, int P) {
     const size_t lds = (size_t)E::region_floats(kCascChunk, P) * sizeof(float);
-    auto k = qat_eval_kernel<E, TRES>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(64), lds, st, a, (int)m->bits_w, (int)m->bits_a, (m->flags & ODPD_FLAG_EVAL) ? 1 : 0);
-    return (int)hipGetLastError();
+    return launch_seq(st, qat_eval_kernel<E, TRES>, a.B, lds, a, (int)m->bits_w, (int)m->bits_a, (m->flags & ODPD_FLAG_EVAL) ? 1 : 0);
 }
 }  // namespace
 int qat_gp_eval(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
@@ -314,10 +306,7 @@ int qat_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     return (int)qat_with_engine(m, [&](auto eng, int P) {
         using Eng = decltype(eng);
         const size_t lds = (size_t)Eng::type::region_floats(a.T, P) * sizeof(float);
-        auto k = qat_gp_train_kernel<typename Eng::type, Eng::tres>;
-        if (int e = allow_big_lds(k, lds)) return (int64_t)e;
-        hipLaunchKernelGGL(k, dim3(qat_gp_train_rows(m, a.B, a.T)), dim3(64), lds, st, a, (int)m->bits_w, (int)m->bits_a);
-        return (int64_t)hipGetLastError();
+        return (int64_t)launch_seq(st, qat_gp_train_kernel<typename Eng::type, Eng::tres>, qat_gp_train_rows(m, a.B, a.T), lds, a, (int)m->bits_w, (int)m->bits_a);
     });
 }
 

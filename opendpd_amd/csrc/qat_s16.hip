@@ -1385,10 +1385,7 @@ static int launch(hipStream_t st, const odpd_model_t* m, SeqArgs a, int mode) {
             const int need = (a.ngroups + 7) / 8, cap = 2 * device_cus();
             ls.grid = need < cap ? need : cap;
         }
-        auto k = fwd_kernel_of<MK, NT, LUT, U>();
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a, m->bits_w, m->bits_a, (m->flags & ODPD_FLAG_EVAL) ? 1 : 0);
-        return (int)hipGetLastError();
+        return launch_lds(st, fwd_kernel_of<MK, NT, LUT, U>(), ls.grid, 64 * ls.waves, lds, a, m->bits_w, m->bits_a, (m->flags & ODPD_FLAG_EVAL) ? 1 : 0);
     }
     if (mode == 0) {       // fused train step: forward (checkpoints only) + backward with the loss formed inside — two launches, no y / dy
         if (!a.partials || !a.target || (!a.ckpt && a.nck > 1)) return ODPD_EINVAL;
@@ -1401,12 +1398,7 @@ static int launch(hipStream_t st, const odpd_model_t* m, SeqArgs a, int mode) {
         if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
         SeqArgs b = a;
         b.dx = nullptr;
-        auto go = [&](auto k) {
-            if (int e = allow_big_lds(k, lds)) return e;
-            hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, b, m->bits_w, m->bits_a);
-            return (int)hipGetLastError();
-        };
-        return go(bwd_kernel_of<MK, NT, LUT, false, true, U>());
+        return launch_lds(st, bwd_kernel_of<MK, NT, LUT, false, true, U>(), ls.grid, 64 * ls.waves, lds, b, m->bits_w, m->bits_a);
     }
     if (a.partials == nullptr && a.dx == nullptr) return ODPD_EINVAL;
     if (!a.ckpt && a.nck > 1) return ODPD_EINVAL;
@@ -1415,11 +1407,7 @@ static int launch(hipStream_t st, const odpd_model_t* m, SeqArgs a, int mode) {
     ls.grid = bwd_grid<MK, NT>(m, a.ngroups);
     const size_t lds = lds_bytes<MK, NT>(P, ls.waves, m->bits_a, LUT, true, dx);
     if (lds > kMaxLds) return ODPD_EUNSUPPORTED;
-    auto go = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a, m->bits_w, m->bits_a);
-        return (int)hipGetLastError();
-    };
+    auto go = [&](auto k) { return launch_lds(st, k, ls.grid, 64 * ls.waves, lds, a, m->bits_w, m->bits_a); };
     if (!dx) return go(bwd_kernel_of<MK, NT, LUT, false, false, U>());
     if (int e = go(bwd_kernel_of<MK, NT, LUT, true, false, U>())) return e;
     if (MK == K_TRES) {

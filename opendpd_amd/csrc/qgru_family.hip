@@ -430,24 +430,15 @@ template <bool AMP1, bool LUT>
 static int qgru_launch_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, int P) {
     const LaunchShape ls = persistent_shape(a.ngroups, 8);
     const size_t lds = qgru_lds_bytes(P, ls.waves, m->bits_a, LUT, false);
-    auto k = qgru_fwd_kernel<AMP1, LUT>;
-    if (int e = allow_big_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a, m->bits_w, m->bits_a, (m->flags & ODPD_FLAG_EVAL) ? 1 : 0);
-    return (int)hipGetLastError();
+    return launch_lds(st, qgru_fwd_kernel<AMP1, LUT>, ls.grid, 64 * ls.waves, lds, a, m->bits_w, m->bits_a, (m->flags & ODPD_FLAG_EVAL) ? 1 : 0);
 }
 template <bool AMP1, bool LUT>
 static int qgru_launch_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, int P) {
     const LaunchShape ls = qgru_bwd_shape(a.ngroups);
     const size_t lds = qgru_lds_bytes(P, ls.waves, m->bits_a, LUT, true);
-    auto launch = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(ls.grid), dim3(64 * ls.waves), lds, st, a, m->bits_w, m->bits_a);
-        return (int)hipGetLastError();
-    };
-    const bool nw = a.partials != nullptr, dx = a.dx != nullptr;
-    if (nw && dx) return launch(qgru_bwd_kernel<AMP1, LUT, true, true>);
-    if (nw) return launch(qgru_bwd_kernel<AMP1, LUT, true, false>);
-    return launch(qgru_bwd_kernel<AMP1, LUT, false, true>);
+    return s16_bwd_dispatch(a, [&](auto nw, auto dx) {
+        return launch_lds(st, qgru_bwd_kernel<AMP1, LUT, nw(), dx()>, ls.grid, 64 * ls.waves, lds, a, m->bits_w, m->bits_a);
+    });
 }
 
 int qgru_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
@@ -459,7 +450,6 @@ int qgru_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
 }
 int qgru_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!qat_ok(m)) return ODPD_EUNSUPPORTED;
-    if (a.partials == nullptr && a.dx == nullptr) return ODPD_EINVAL;
     const int P = qgru_layout(m->hidden).P;
     const bool amp1 = m->backbone == ODPD_QGRU_AMP1, lut = m->bits_a <= 8;
     if (amp1) return lut ? qgru_launch_bwd<true, true>(st, m, a, P) : qgru_launch_bwd<true, false>(st, m, a, P);

@@ -444,11 +444,7 @@ int rv_launch_bwd(hipStream_t st, const SeqArgs& a, bool nw, bool dx) {
     const int P = rv_layout(a.H).P;
     const size_t lds = rv_lds_bytes<HT>(P, nw, dx);
     const int grid = nw ? rvtdcnn_rows_for(a.B, a.T, dx) : rv_grid(g.npass);
-    auto go = [&](auto k) {
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(kRvThreads), lds, st, a, g);
-        return (int)hipGetLastError();
-    };
+    auto go = [&](auto k) { return launch_lds(st, k, grid, kRvThreads, lds, a, g); };
     if (nw && dx) return go(rv_bwd_kernel<HT, FUSED, true, true>);
     if (nw) return go(rv_bwd_kernel<HT, FUSED, true, false>);
     return go(rv_bwd_kernel<HT, FUSED, false, true>);

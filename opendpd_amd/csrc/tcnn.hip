@@ -567,16 +567,12 @@ static int tcnn_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, 
         const TcnnGeom g = tcnn_geom(a.B, a.T, kTHalo + fir);
         const TcnnBwdShape s = tcnn_bwd_shape(g);
         const size_t lds = ((size_t)4 * pad4(P) + (size_t)4 * 2 * R * 64) * sizeof(float);
-        auto k = tcnn_bwd_kernel<R, NTX>;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(s.grid), dim3(256), lds, st, a, g, s.ncw);
+        return launch_lds(st, tcnn_bwd_kernel<R, NTX>, s.grid, 256, lds, a, g, s.ncw);
     } else {
         const TcnnGeom g = tcnn_geom(a.B, a.T, kTHaloDx + 2 * fir);
         const int ncw = tcnn_split(g.ngroups, 4);
         const size_t lds = ncw > 1 ? (size_t)4 * 6 * R * 64 * sizeof(float) : 0;
-        auto k = tcnn_dx_kernel<R, NTX>;
-        if (int e = allow_big_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3((g.ngroups * ncw + 3) / 4), dim3(256), lds, st, a, g, ncw);
+        return launch_lds(st, tcnn_dx_kernel<R, NTX>, (g.ngroups * ncw + 3) / 4, 256, lds, a, g, ncw);
     }
     return (int)hipGetLastError();
 }

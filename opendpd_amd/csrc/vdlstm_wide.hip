@@ -378,7 +378,7 @@ int vdlstm_wide_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!vdlstm_wide_ok(m)) return ODPD_EUNSUPPORTED;
     if (a.T < 3) return ODPD_EINVAL;      // the circular pad takes the frame's own last three samples (vdlstm.py:66-74)
     const size_t lds = (size_t)vdw_fwd_floats(lstm_layout(m->hidden, 1).P) * sizeof(float);
-    return wide_fwd_dispatch(a, [&](auto sv) { return wide_launch(st, wide_vdlstm_fwd_kernel<decltype(sv)::value>, lds, a); });
+    return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, wide_vdlstm_fwd_kernel<decltype(sv)::value>, lds, a); });
 }
 int vdlstm_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!vdlstm_wide_ok(m)) return ODPD_EUNSUPPORTED;
