@@ -17,11 +17,10 @@ inline Family family_of(int bb);
 // a quantisation-aware model: bits_w > 0 on one of the backbones the reference's surgery turns into a quantised cell
 // (quant/quant_envs.py:114-130, 290-306: gru, dgru, qgru, qgru_amp1 through the GRU swap; deltagru_tcnskip through its op modules)
 inline Family family_of(const odpd_model_t* m) {
-    // ODPD_FLAG_QUANT_CELL: a family of its own (bojanet_q.hip, dvrjanet_q.hip: forward / backward) — like FAM_GRU2 below, so that no entry point
-    // written for the float bojanet / dvrjanet kernels reads the quantised parameter buffer, and the flag on any other descriptor finds no kernel anywhere
+    // ODPD_FLAG_QUANT_CELL, ODPD_FLAG_TWO_LAYERS: families of their own, so that whatever is written for a backbone's one-layer float kernels
+    // (`family_of(m) == FAM_...`: f4_of, fused_step, the cascade) finds none for these descriptors instead of misreading their parameter buffer;
+    // their kernels are kRoutes' (route_of)
     if (m->flags & ODPD_FLAG_QUANT_CELL) return FAM_QCELL;
-    // two recurrent layers: a family of its own (gru_layers2.hip: forward / backward) — every entry point written for the one-layer kernels
-    // tests `family_of(m) == FAM_...` and so answers ODPD_EUNSUPPORTED for these descriptors instead of misreading their parameter buffer
     if (m->flags & ODPD_FLAG_TWO_LAYERS) return FAM_GRU2;
     if (m->bits_w > 0 && (m->backbone == ODPD_QGRU || m->backbone == ODPD_QGRU_AMP1 || m->backbone == ODPD_GRU || m->backbone == ODPD_DGRU ||
                           m->backbone == ODPD_TRES_DELTAGRU))
@@ -32,10 +31,7 @@ inline Family family_of(const odpd_model_t* m) {
 // the batch leaves the chip mostly empty, the 16-sequences-per-wave ones (qat_s16.hip) otherwise and for every other kind / hidden size
 inline bool qat_uses_s16(const odpd_model_t* m, int B) {
     const bool rot_ok = (m->backbone == ODPD_QGRU || m->backbone == ODPD_QGRU_AMP1) && m->hidden <= 16;
-    if (!rot_ok) return true;
-    long min_batch = tuning().s16_min_batch;
-    if (min_batch < 0) min_batch = 16L * 3 * device_cus();
-    return B >= min_batch;
+    return !rot_ok || B >= s16_min_batch_or(16L * 3 * device_cus());
 }
 inline Family family_of(int bb) {
     switch (bb) {
@@ -61,27 +57,64 @@ inline int feat_dim(int bb) {
     default: return 0;
     }
 }
-// ODPD_FLAG_INIT_STATE: the descriptor asks for the state route (a caller-given initial state), which the lane-per-unit kernels of
-// gru_wide.hip / lstm_wide.hip serve for the float gru / dgru / qgru / qgru_amp1 / lstm of 1 .. 64 hidden units, one layer; every entry point
-// answers ODPD_EUNSUPPORTED for the flag on any other descriptor
 inline bool init_state(const odpd_model_t* m) { return (m->flags & ODPD_FLAG_INIT_STATE) != 0; }
-// ODPD_FLAG_QUANT_CELL: the quantised bojanet (bojanet_q.hip) and dvrjanet (dvrjanet_q.hip) of 1 .. 16 hidden units; every entry point answers
-// ODPD_EUNSUPPORTED for the flag on any other descriptor (the state route included)
 inline bool quant_cell(const odpd_model_t* m) { return (m->flags & ODPD_FLAG_QUANT_CELL) != 0; }
-inline bool quant_cell_ok(const odpd_model_t* m) { return bojanet_q_ok(m) || dvrjanet_q_ok(m); }
-inline bool init_state_ok(const odpd_model_t* m) { return !quant_cell(m) && (gru_state_ok(m) || lstm_state_ok(m)); }
-// models served by the lane-per-unit kernels (gru_wide.hip, lstm_wide.hip, vdlstm_wide.hip, delta_wide.hip: 33 .. 64 hidden units; janet_wide.hip: pgjanet 17 .. 32;
-// every ODPD_FLAG_INIT_STATE descriptor): forward / backward only — the fused entry points answer ODPD_EUNSUPPORTED for them and the caller chains
-// forward, loss, backward
-inline bool lane_per_unit_model(const odpd_model_t* m) {
-    return init_state(m) || gru_wide_ok(m) || lstm_wide_ok(m) || vdlstm_wide_ok(m) || delta_wide_ok(m) || pgjanet_wide_ok(m) || deltajanet_wide_ok(m) ||
-           pgjanet_q_ok(m) || quant_cell(m);
+
+// ---- table 1: the kernel sets that are forward / backward only.  The fused entry points answer ODPD_EUNSUPPORTED for their descriptors and
+// the caller chains forward, loss, backward ----
+using SeqFn = int (*)(hipStream_t, const odpd_model_t*, const SeqArgs&);
+struct Route {
+    bool (*ok)(const odpd_model_t*);
+    int64_t (*param_count)(const odpd_model_t*);      // NULL: the backbone's formula in odpd_param_count
+    int64_t (*ckpt_floats)(const odpd_model_t*, int B, int T);
+    int (*rows)(const odpd_model_t*, int B);
+    SeqFn fwd, bwd;
+};
+constexpr Route kRoutes[] = {
+    // ODPD_FLAG_INIT_STATE, a caller-given initial state: the lane-per-unit kernels of gru_wide.hip / lstm_wide.hip (their per-step records and
+    // rows) at every hidden size 1 .. 64, one layer, float; launched by odpd_backbone_fwd_state / _bwd_state alone
+    {gru_state_ok, nullptr, gru_wide_ckpt_floats, gru_wide_rows, gru_state_fwd, gru_state_bwd},
+    {lstm_state_ok, nullptr, lstm_wide_ckpt_floats, lstm_wide_rows, lstm_state_fwd, lstm_state_bwd},
+    // ODPD_FLAG_QUANT_CELL, `--quant` inside the cell: eight INT_Linear on bojanet, nine on dvrjanet, 1 .. 16 hidden units
+    {bojanet_q_ok, bojanet_q_param_count, bojanet_q_ckpt_floats, bojanet_q_rows, bojanet_q_fwd, bojanet_q_bwd},
+    {dvrjanet_q_ok, dvrjanet_q_param_count, dvrjanet_q_ckpt_floats, dvrjanet_q_rows, dvrjanet_q_fwd, dvrjanet_q_bwd},
+    // ODPD_FLAG_TWO_LAYERS: two recurrent layers in one wave, 1 .. 32 hidden units
+    {gru2_ok, gru2_param_count, gru2_ckpt_floats, gru2_rows, gru2_fwd, gru2_bwd},
+    {lstm2_ok, lstm2_param_count, lstm2_ckpt_floats, lstm2_rows, lstm2_fwd, lstm2_bwd},
+    // by hidden size: lane per unit at 33 .. 64 (pgjanet: 17 .. 32; deltajanet with quantised heads: every size), and the pgjanet of six INT_Linear
+    {gru_wide_ok, nullptr, gru_wide_ckpt_floats, gru_wide_rows, gru_wide_fwd, gru_wide_bwd},
+    {lstm_wide_ok, nullptr, lstm_wide_ckpt_floats, lstm_wide_rows, lstm_wide_fwd, lstm_wide_bwd},
+    {vdlstm_wide_ok, nullptr, vdlstm_wide_ckpt_floats, vdlstm_wide_rows, vdlstm_wide_fwd, vdlstm_wide_bwd},
+    {delta_wide_ok, nullptr, delta_wide_ckpt_floats, delta_wide_rows, delta_wide_fwd, delta_wide_bwd},
+    {deltajanet_wide_ok, nullptr, deltajanet_wide_ckpt_floats, deltajanet_wide_rows, deltajanet_wide_fwd, deltajanet_wide_bwd},
+    {pgjanet_wide_ok, nullptr, pgjanet_wide_ckpt_floats, pgjanet_wide_rows, pgjanet_wide_fwd, pgjanet_wide_bwd},
+    {pgjanet_q_ok, pgjanet_q_param_count, pgjanet_q_ckpt_floats, pgjanet_q_rows, pgjanet_q_fwd, pgjanet_q_bwd},
+};
+enum { ROUTE_NONE = -1, ROUTE_REFUSED = -2, kStateRoutes = 0, kQuantCellRoutes = 2, kTwoLayerRoutes = 4, kHiddenRoutes = 6, kNumRoutes = 13 };
+static_assert(sizeof(kRoutes) / sizeof(kRoutes[0]) == kNumRoutes, "kRoutes and its group bounds");
+// Which of kRoutes serves a descriptor: its index; ROUTE_NONE — not a descriptor of these routes (the family kernels below answer for it);
+// ROUTE_REFUSED — it asks for such a route and none serves it: every entry point answers ODPD_EUNSUPPORTED.
+// A flag selects its group alone, in this order: ODPD_FLAG_INIT_STATE first (with ODPD_FLAG_QUANT_CELL on top: refused), then
+// ODPD_FLAG_QUANT_CELL, then ODPD_FLAG_TWO_LAYERS, then the routes chosen by hidden size — so no flag is ever answered by a kernel that
+// would misread the flagged model's parameter buffer.  Without a flag only a pgjanet with bits_w > 0 that the table's last row does not take is refused.
+inline int route_of(const odpd_model_t* m) {
+    const auto first = [m](int lo, int hi, int miss) {
+        for (int k = lo; k < hi; ++k)
+            if (kRoutes[k].ok(m)) return k;
+        return miss;
+    };
+    if (init_state(m)) return quant_cell(m) ? (int)ROUTE_REFUSED : first(kStateRoutes, kQuantCellRoutes, ROUTE_REFUSED);
+    if (quant_cell(m)) return first(kQuantCellRoutes, kTwoLayerRoutes, ROUTE_REFUSED);
+    if (m->flags & ODPD_FLAG_TWO_LAYERS) return first(kTwoLayerRoutes, kHiddenRoutes, ROUTE_REFUSED);
+    return first(kHiddenRoutes, kNumRoutes, m->backbone == ODPD_PGJANET && m->bits_w > 0 ? ROUTE_REFUSED : ROUTE_NONE);
 }
+// the float GRU family on its own kernels (gru_family.hip, gru_s16*.hip): what the frozen-PA loss step and the sweeps serve
+inline bool gru_family_model(const odpd_model_t* m) { return family_of(m) == FAM_GRU && route_of(m) == ROUTE_NONE; }
 // bits_w > 0 selects a quantised model only where one exists (include/opendpd_hip.h, odpd_model_t::bits_w); on every other backbone
 // the descriptor is refused outright — no entry point may answer it with the float kernels on a float parameter layout
 inline bool quant_desc_ok(const odpd_model_t* m) {
     if (m->bits_w <= 0 || m->backbone == ODPD_DVRJANET) return true;      // (dvrjanet: bits_w carries num_dvr_units)
-    if (quant_cell(m)) return true;      // (what the flag is valid on is answered with ODPD_EUNSUPPORTED, not here: quant_cell_ok)
+    if (quant_cell(m)) return true;      // (what the flag is valid on is answered with ODPD_EUNSUPPORTED, not here: route_of)
     switch (m->backbone) {
     case ODPD_GRU: case ODPD_DGRU: case ODPD_QGRU: case ODPD_QGRU_AMP1: case ODPD_TRES_DELTAGRU:      // the surgery's quantised cells
     case ODPD_LSTM: case ODPD_VDLSTM: case ODPD_DELTAJANET: case ODPD_NEURALTX:                      // float core, INT_Linear heads
@@ -102,6 +135,87 @@ inline SeqArgs make_args(const odpd_model_t* m, int B, int T) {
     a.thx = m->thx; a.thh = m->thh;
     a.bits_w = m->bits_w; a.bits_a = m->bits_a; a.eval_out = (m->flags & ODPD_FLAG_EVAL) ? 1 : 0;
     return a;
+}
+
+// ---- table 2: dvrjanet, bojanet, apnrru and mcldnn on the 16-sequences-per-wave f4 mapping share one interface ----
+struct F4Backbone {
+    int (*launch)(hipStream_t, const odpd_model_t*, const SeqArgs&, int mode);      // mode 1 forward, 2 backward
+    int (*rows)(const odpd_model_t*, int B);
+    int64_t (*param_count)(const odpd_model_t*);
+    int64_t (*ckpt_floats)(const odpd_model_t*, int B, int T);
+    bool (*train_uses_gp)(const odpd_model_t*, int B, int T);      // the gate-parallel fused train kernel takes the shape (the reference's batch sizes)
+    int (*gp_rows)(const odpd_model_t*, int B, int T);
+    SeqFn gp_train;
+};
+constexpr F4Backbone kF4[] = {      // FAM_DVR .. FAM_MCL, in the enum's order
+    // K + 7H^2 + 7H + 2 parameters, K = bits_w (dvrjanet.py:11-30, 47-52)
+    {dvrjanet_launch, dvrjanet_rows, dvrjanet_param_count, dvrjanet_ckpt_floats, dvrjanet_train_uses_gp, dvrjanet_gp_rows, dvrjanet_gp_train},
+    // 2H^2 + 28H + 194 (bojanet.py:15-26)
+    {bojanet_launch, bojanet_rows, bojanet_param_count, bojanet_ckpt_floats, bojanet_train_uses_gp, bojanet_gp_rows, bojanet_gp_train},
+    // 343 + 70H (apnrru.py:13-19, 45-53)
+    {apnrru_launch, apnrru_rows, apnrru_param_count, apnrru_ckpt_floats, apnrru_train_uses_gp, apnrru_gp_rows, apnrru_gp_train},
+    // 190C + 589 (mcldnn.py:21-27)
+    {mcldnn_launch, mcldnn_rows, mcldnn_param_count, mcldnn_ckpt_floats, mcldnn_train_uses_gp, mcldnn_gp_rows, mcldnn_gp_train},
+};
+static_assert(FAM_BOJ == FAM_DVR + 1 && FAM_APN == FAM_DVR + 2 && FAM_MCL == FAM_DVR + 3, "kF4 is indexed by family");
+inline const F4Backbone* f4_of(const odpd_model_t* m) {      // (family_of: a flagged descriptor is none of them)
+    const Family f = family_of(m);
+    return f >= FAM_DVR && f <= FAM_MCL ? &kF4[f - FAM_DVR] : nullptr;
+}
+
+// ---- the fused train step (forward + loss + backward in one launch), resolved once per (m, B, T) ----
+// what the `workspace` pointer of odpd_train_fwd_bwd / odpd_train_fwd_bwd_framed is to the kernel: nothing; BPTT checkpoints (ws_floats of them);
+// the four sparsity counters of the step's forward pass (double[4], may be NULL — delta backbones and the quantised TRes-DeltaGRU)
+enum WsKind { WS_UNUSED, WS_CKPT, WS_COUNTERS };
+struct FusedStep {
+    SeqFn train;            // NULL: the family has no fused kernel for this shape
+    int64_t rows;           // partial-gradient rows the launch writes (odpd_partial_rows(fused = 1))
+    int64_t ws_floats;      // floats behind `workspace` (odpd_train_workspace_floats)
+    WsKind ws;
+    bool framed;            // the kernel addresses frames inside resident streams (SeqArgs::frame_idx): the framed entry points serve the shape
+};
+// (launchers that take one argument more, as SeqFn)
+int gru_s16x_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return gru_s16x_train(st, m, a, gru_s16n_rows(m, a.B)); }
+int gru_s16n_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return gru_s16n_launch(st, m, a, 0); }
+int qat_s16_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return qat_s16_launch(st, m, a, 0); }
+int qat_gp_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { SeqArgs b = a; b.ckpt = nullptr; return qat_gp_train(st, m, b); }      // (`workspace`: the counters or nothing)
+// checkpoint floats of the 16-sequences-per-wave kernels of hidden 17 .. 32: the larger of gru_s16n.hip's layout and gru_s16x.hip's (a record
+// every two steps) where that file takes the model — the "s16x" / "s16x_train" knobs change between sizing and launch only with a new
+// generation, but both fit.  The split calls, the fused step and odpd_frozen_loss_dx size one buffer by it.
+inline int64_t gru_s16n_floats(const odpd_model_t* m, int B, int T) {
+    const int64_t own = gru_s16n_ckpt_floats(m, B, T), x = gru_s16x_ok(m) ? gru_s16x_ckpt_floats(m, B, T) : 0;
+    return own > x ? own : x;
+}
+inline FusedStep fused_step(const odpd_model_t* m, int B, int T) {
+    const FusedStep none{nullptr, ODPD_EUNSUPPORTED, ODPD_EUNSUPPORTED, WS_UNUSED, false};
+    const int r = route_of(m);
+    // (kept as it was before the table: a pgjanet whose bit widths no kernel takes is ROUTE_REFUSED, yet of the fused entry points only
+    // odpd_partial_rows ever asked; the others serve its hidden <= 16 as the float model)
+    const bool float_pgjanet = r == ROUTE_REFUSED && family_of(m) == FAM_JANET && !init_state(m);
+    if (r != ROUTE_NONE && !float_pgjanet) return none;
+    if (const F4Backbone* f = f4_of(m)) return f->train_uses_gp(m, B, T) ? FusedStep{f->gp_train, f->gp_rows(m, B, T), 0, WS_UNUSED, true} : none;
+    switch (family_of(m)) {
+    case FAM_GRU:      // every shape, from tensors and from frames: the rows are gru_family_rows' whichever kernel runs
+        if (gru_uses_s16n(m, B))
+            return {gru_s16x_train_ok(m) ? gru_s16x_step : gru_s16n_step, gru_family_rows(m, B, 1, T), gru_s16n_floats(m, B, T), WS_CKPT, true};
+        if (gru_train_uses_s16(m, B, T)) return {gru_s16_train, gru_family_rows(m, B, 1, T), gru_s16_workspace_floats(m, B, T), WS_CKPT, true};
+        return {gru_family_train, gru_family_rows(m, B, 1, T), 0, WS_UNUSED, true};
+    case FAM_LSTM:     // (the 16-sequences-per-wave kernel takes tensors only)
+        if (lstm_train_uses_s16(m, B)) return {lstm_s16_train, lstm_s16_rows(m, B), lstm_s16_workspace_floats(m, B, T), WS_CKPT, false};
+        return lstm_train_uses_gp(m, B, T) ? FusedStep{lstm_gp_train, lstm_gp_rows(m, B, T), 0, WS_UNUSED, true} : none;
+    case FAM_JANET: return janet_train_uses_gp(m, B, T) ? FusedStep{janet_gp_train, janet_gp_rows(m, B, T), 0, WS_UNUSED, true} : none;
+    case FAM_DELTA: {  // (the launcher is named at every shape: odpd_train_fwd_bwd calls it without asking and lets it answer; sizes and frames ask)
+        const bool gp = delta_train_uses_gp(m, B, T);
+        return {delta_gp_train, gp ? (int64_t)delta_gp_train_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED, gp ? 0 : (int64_t)ODPD_EUNSUPPORTED, WS_COUNTERS, gp};
+    }
+    // (the launchers answer for a hidden size they do not take; the workspace query refuses it in front of them)
+    case FAM_GMP: return {gmp_train, gmp_rows(m, B, T), odpd_param_count(m) > 0 ? 0 : (int64_t)ODPD_EUNSUPPORTED, WS_UNUSED, true};
+    case FAM_RVTDCNN: return {rvtdcnn_train, rvtdcnn_train_rows(m, B, T), odpd_param_count(m) > 0 ? 0 : (int64_t)ODPD_EUNSUPPORTED, WS_UNUSED, true};
+    case FAM_QAT:      // one frame per wave at the reference's batch sizes, else forward-with-checkpoints + backward-with-loss launches of qat_s16.hip
+        if (qat_train_uses_gp(m, B, T)) return {qat_gp_step, qat_gp_train_rows(m, B, T), 0, m->backbone == ODPD_TRES_DELTAGRU ? WS_COUNTERS : WS_UNUSED, true};
+        return qat_uses_s16(m, B) ? FusedStep{qat_s16_step, qat_s16_rows(m, B), qat_s16_ckpt_floats(m, B, T), WS_CKPT, true} : none;
+    default: return none;
+    }
 }
 }  // namespace
 
@@ -207,10 +321,11 @@ extern "C" const char* odpd_built_arch(void) { return "gfx950"; }
 
 extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
     if (!model_ok(m)) return ODPD_EINVAL;
-    if (init_state(m) && !init_state_ok(m)) return ODPD_EUNSUPPORTED;
-    if (quant_cell(m)) return bojanet_q_ok(m) ? bojanet_q_param_count(m) : dvrjanet_q_ok(m) ? dvrjanet_q_param_count(m) : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_GRU2) return gru2_ok(m) ? gru2_param_count(m) : lstm2_ok(m) ? lstm2_param_count(m) : (int64_t)ODPD_EUNSUPPORTED;
+    const int r = route_of(m);
+    if (r == ROUTE_REFUSED) return ODPD_EUNSUPPORTED;
+    if (r >= 0 && kRoutes[r].param_count) return kRoutes[r].param_count(m);
     if (family_of(m) == FAM_QAT) return qat_s16_param_count(m);
+    if (const F4Backbone* f = f4_of(m)) return f->param_count(m);
     const int64_t H = m->hidden, F = feat_dim(m->backbone);
     switch (m->backbone) {
     case ODPD_GRU: case ODPD_QGRU: case ODPD_QGRU_AMP1: return 3 * H * F + 3 * H * H + 6 * H + 2 * H + 2;
@@ -222,14 +337,9 @@ extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
     case ODPD_TRES_DELTAGRU: return 3 * H * 6 + 3 * H * H + 2 * H + 18 + 6;
     case ODPD_DELTAJANET: return 2 * H * 6 + 2 * H * H + 4 * H + 2 * H + 2 + (m->bits_w > 0 ? 3 : 0);      // two gates (deltajanet.py:96-111) + fc_out (bits_w > 0: INT_Linear, + three scales)
     case ODPD_TCNN: return 6 * H + H + 4 * 5 * H + 2 * H;
-    case ODPD_PGJANET: return m->bits_w > 0 ? (pgjanet_q_ok(m) ? pgjanet_q_param_count(m) : (int64_t)ODPD_EUNSUPPORTED)
-                                            : 3 * (H * (H + 1) + H) + 2 * (H * 2 * H + H) + 2 * H + 2;
+    case ODPD_PGJANET: return 3 * (H * (H + 1) + H) + 2 * (H * 2 * H + H) + 2 * H + 2;      // (bits_w > 0: kRoutes)
     case ODPD_NEURALTX: return H <= 64 ? 27 * H + 14 + (m->bits_w > 0 ? 3 : 0) : (int64_t)ODPD_EUNSUPPORTED;   // two 5-tap FIRs, 4->C (+bias), 4 x depthwise k5, C->2, IQ_match 2x2 (bits_w > 0: INT_Linear, + three scales)
     case ODPD_GMP: return H == 11 ? H * (1 + 4 * H) : (int64_t)ODPD_EUNSUPPORTED;   // memory_length 11, degree 5 (models.py:26-28)
-    case ODPD_DVRJANET: return dvrjanet_param_count(m);   // K + 7H^2 + 7H + 2, K = bits_w (dvrjanet.py:11-30, 47-52)
-    case ODPD_MCLDNN: return mcldnn_param_count(m);       // 190C + 589 (mcldnn.py:21-27)
-    case ODPD_APNRRU: return apnrru_param_count(m);       // 343 + 70H (apnrru.py:13-19, 45-53)
-    case ODPD_BOJANET: return bojanet_param_count(m);     // 2H^2 + 28H + 194 (bojanet.py:15-26)
     case ODPD_RVTDCNN: return H <= 32 ? (m->bits_w > 0 ? rvtdcnn_q_param_count(m) : 39 * H + 32) : (int64_t)ODPD_EUNSUPPORTED;  // conv 27+3, fc_hid 36H+H, fc_out 2H+2 (rvtdcnn.py:19-33)
     default: return ODPD_EUNSUPPORTED;
     }
@@ -237,31 +347,16 @@ extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
 
 extern "C" int64_t odpd_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    if (init_state(m))      // the per-step records of the lane-per-unit kernels, at every hidden size they serve on the state route
-        return !init_state_ok(m) ? (int64_t)ODPD_EUNSUPPORTED : family_of(m) == FAM_LSTM ? lstm_wide_ckpt_floats(m, B, T) : gru_wide_ckpt_floats(m, B, T);
-    if (quant_cell(m)) return bojanet_q_ok(m) ? bojanet_q_ckpt_floats(m, B, T) : dvrjanet_q_ok(m) ? dvrjanet_q_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
+    const int r = route_of(m);
+    if (r != ROUTE_NONE) return r < 0 ? (int64_t)ODPD_EUNSUPPORTED : kRoutes[r].ckpt_floats(m, B, T);
     if (family_of(m) == FAM_TCNN || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN) return 0;   // not recurrent: nothing to checkpoint
-    if (family_of(m) == FAM_DVR) return dvrjanet_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_BOJ) return bojanet_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_APN) return apnrru_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_MCL) return mcldnn_ckpt_floats(m, B, T);
+    if (const F4Backbone* f = f4_of(m)) return f->ckpt_floats(m, B, T);
     if (family_of(m) == FAM_QAT && qat_uses_s16(m, B)) return qat_s16_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_GRU2) return gru2_ok(m) ? gru2_ckpt_floats(m, B, T) : lstm2_ok(m) ? lstm2_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_GRU && gru_wide_ok(m)) return gru_wide_ckpt_floats(m, B, T);      // 33 .. 64 units: the per-step records of gru_wide.hip
-    if (family_of(m) == FAM_LSTM && lstm_wide_ok(m)) return lstm_wide_ckpt_floats(m, B, T);    // ... of lstm_wide.hip
-    if (family_of(m) == FAM_LSTM && vdlstm_wide_ok(m)) return vdlstm_wide_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_DELTA && delta_wide_ok(m)) return delta_wide_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_DELTA && deltajanet_wide_ok(m)) return deltajanet_wide_ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_JANET && m->bits_w > 0) return pgjanet_q_ok(m) ? pgjanet_q_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_JANET && pgjanet_wide_ok(m)) return pgjanet_wide_ckpt_floats(m, B, T);
     const int R = rows_per_seq(m->hidden);
     if (!R) return ODPD_EUNSUPPORTED;
     switch (family_of(m)) {
     case FAM_GRU:   // [4-sequence group][ckpt][64 lanes], or [16-sequence task][ckpt][64 lanes][4] for the S16 kernels
-        if (gru_uses_s16n(m, B)) {      // (this buffer is also the workspace of odpd_frozen_loss_dx: gru_s16x.hip checkpoints every two steps)
-            const int64_t own = gru_s16n_ckpt_floats(m, B, T), x = gru_s16x_ok(m) ? gru_s16x_ckpt_floats(m, B, T) : 0;
-            return own > x ? own : x;
-        }
+        if (gru_uses_s16n(m, B)) return gru_s16n_floats(m, B, T);
         return gru_split_uses_s16(m, B) ? (int64_t)((B + 15) / 16) * num_ckpt(T) * 256 : (int64_t)num_groups(B, R) * num_ckpt(T) * 64;
     case FAM_LSTM: return (int64_t)num_groups(B, R) * num_ckpt(T) * 128;   // h and c
     case FAM_DELTA:
@@ -277,107 +372,54 @@ extern "C" int64_t odpd_ckpt_floats(const odpd_model_t* m, int B, int T) {
 
 extern "C" int64_t odpd_partial_rows(const odpd_model_t* m, int B, int T, int fused) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    if (init_state(m))
-        return (fused || !init_state_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : family_of(m) == FAM_LSTM ? (int64_t)lstm_wide_rows(m, B) : (int64_t)gru_wide_rows(m, B);
+    const int r = route_of(m);
+    if (r != ROUTE_NONE) return (r < 0 || fused) ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)kRoutes[r].rows(m, B);      // (forward / backward only: no fused rows)
+    if (fused) {
+        const FusedStep f = fused_step(m, B, T);
+        return f.train ? f.rows : (int64_t)ODPD_EUNSUPPORTED;
+    }
+    if (const F4Backbone* f = f4_of(m)) return f->rows(m, B);
     switch (family_of(m)) {
-    case FAM_QCELL: return (fused || !quant_cell_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)(bojanet_q_ok(m) ? bojanet_q_rows(m, B) : dvrjanet_q_rows(m, B));
-    case FAM_GRU2: return fused ? (int64_t)ODPD_EUNSUPPORTED : gru2_ok(m) ? (int64_t)gru2_rows(m, B) : lstm2_ok(m) ? (int64_t)lstm2_rows(m, B) : (int64_t)ODPD_EUNSUPPORTED;
-    case FAM_GRU:
-        if (gru_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)gru_wide_rows(m, B);
-        return gru_family_rows(m, B, fused ? 1 : 0, T);
-    case FAM_LSTM:
-        if (lstm_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)lstm_wide_rows(m, B);
-        if (vdlstm_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)vdlstm_wide_rows(m, B);
-        if (fused) return lstm_train_uses_s16(m, B) ? (int64_t)lstm_s16_rows(m, B)
-                                                    : lstm_train_uses_gp(m, B, T) ? (int64_t)lstm_gp_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return lstm_family_rows(m, B);
-    case FAM_DELTA:
-        if (delta_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)delta_wide_rows(m, B);
-        if (deltajanet_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)deltajanet_wide_rows(m, B);
-        if (fused) return delta_train_uses_gp(m, B, T) ? (int64_t)delta_gp_train_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return delta_family_rows(m, B, T);
-    case FAM_JANET:
-        if (m->bits_w > 0) return (fused || !pgjanet_q_ok(m)) ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)pgjanet_q_rows(m, B);
-        if (pgjanet_wide_ok(m)) return fused ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)pgjanet_wide_rows(m, B);
-        if (fused) return janet_train_uses_gp(m, B, T) ? (int64_t)janet_gp_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return janet_family_rows(m, B);
-    case FAM_DVR:
-        if (fused) return dvrjanet_train_uses_gp(m, B, T) ? (int64_t)dvrjanet_gp_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return (int64_t)dvrjanet_rows(m, B);
-    case FAM_BOJ:
-        if (fused) return bojanet_train_uses_gp(m, B, T) ? (int64_t)bojanet_gp_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return (int64_t)bojanet_rows(m, B);
-    case FAM_APN:
-        if (fused) return apnrru_train_uses_gp(m, B, T) ? (int64_t)apnrru_gp_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return (int64_t)apnrru_rows(m, B);
-    case FAM_MCL:
-        if (fused) return mcldnn_train_uses_gp(m, B, T) ? (int64_t)mcldnn_gp_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-        return (int64_t)mcldnn_rows(m, B);
-    case FAM_TCNN: return fused ? (int64_t)ODPD_EUNSUPPORTED : tcnn_rows(m, B, T);
+    case FAM_GRU: return gru_family_rows(m, B, 0, T);
+    case FAM_LSTM: return lstm_family_rows(m, B);
+    case FAM_DELTA: return delta_family_rows(m, B, T);
+    case FAM_JANET: return janet_family_rows(m, B);
+    case FAM_TCNN: return tcnn_rows(m, B, T);
     case FAM_GMP: return gmp_rows(m, B, T);
-    case FAM_RVTDCNN: return fused ? rvtdcnn_train_rows(m, B, T) : rvtdcnn_rows(m, B, T);
-    case FAM_QAT:      // fused: forward-with-checkpoints + backward-with-loss launches of the 16-sequences-per-wave kernels (same rows as their backward)
-        if (fused && qat_train_uses_gp(m, B, T)) return (int64_t)qat_gp_train_rows(m, B, T);      // (one frame per wave: the reference's batch sizes)
-        if (fused) return qat_uses_s16(m, B) ? (int64_t)qat_s16_rows(m, B) : (int64_t)ODPD_EUNSUPPORTED;
-        return qat_uses_s16(m, B) ? (int64_t)qat_s16_rows(m, B) : (int64_t)qgru_family_rows(m, B);
+    case FAM_RVTDCNN: return rvtdcnn_rows(m, B, T);
+    case FAM_QAT: return qat_uses_s16(m, B) ? (int64_t)qat_s16_rows(m, B) : (int64_t)qgru_family_rows(m, B);
     default: return ODPD_EUNSUPPORTED;
     }
 }
 
 extern "C" int64_t odpd_train_workspace_floats(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    if (lane_per_unit_model(m)) return ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_LSTM)
-        return lstm_train_uses_s16(m, B) ? lstm_s16_workspace_floats(m, B, T) : lstm_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_JANET) return janet_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_DELTA) return delta_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;   // (`workspace` then carries the counters)
-    if (family_of(m) == FAM_BOJ) return bojanet_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_APN) return apnrru_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_DVR) return dvrjanet_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_MCL) return mcldnn_train_uses_gp(m, B, T) ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN) return odpd_param_count(m) > 0 ? 0 : (int64_t)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_QAT) {      // (one frame per wave: no scratch — `workspace` then carries the quantised TRes-DeltaGRU's counters)
-        if (qat_train_uses_gp(m, B, T)) return 0;
-        return qat_uses_s16(m, B) ? qat_s16_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
-    }
-    if (family_of(m) != FAM_GRU) return ODPD_EUNSUPPORTED;
-    if (gru_uses_s16n(m, B)) {      // (the larger of the two layouts: the "s16x_train" knob may change between sizing and launch only with a new generation, but both fit)
-        const int64_t own = gru_s16n_ckpt_floats(m, B, T), x = gru_s16x_ok(m) ? gru_s16x_ckpt_floats(m, B, T) : 0;
-        return own > x ? own : x;
-    }
-    return gru_train_uses_s16(m, B, T) ? gru_s16_workspace_floats(m, B, T) : 0;
+    const FusedStep f = fused_step(m, B, T);
+    return f.train ? f.ws_floats : (int64_t)ODPD_EUNSUPPORTED;
 }
 
 extern "C" int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                                  const float* x, float* y, float* ckpt, double* stats) {
     if (!model_ok(m) || !params || !x || !y || B <= 0 || T <= 0) return ODPD_EINVAL;
-    if (init_state(m)) return init_state_ok(m) ? ODPD_EINVAL : ODPD_EUNSUPPORTED;      // (the flag's forward is odpd_backbone_fwd_state)
+    const int r = route_of(m);
+    if (r == ROUTE_REFUSED) return ODPD_EUNSUPPORTED;
+    if (init_state(m)) return ODPD_EINVAL;      // (served, but by odpd_backbone_fwd_state: this call has no h0)
+    hipStream_t st = (hipStream_t)stream;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.stats = stats;
+    if (r >= 0) return kRoutes[r].fwd(st, m, a);
+    if (const F4Backbone* f = f4_of(m)) return f->launch(st, m, a, 1);
     switch (family_of(m)) {
-    case FAM_QCELL:      // `--quant` on bojanet: eight INT_Linear (bojanet_q.hip); on dvrjanet: nine (dvrjanet_q.hip)
-        return m->backbone == ODPD_DVRJANET ? dvrjanet_q_fwd((hipStream_t)stream, m, a) : bojanet_q_fwd((hipStream_t)stream, m, a);
-    case FAM_GRU2: return lstm2_ok(m) ? lstm2_fwd((hipStream_t)stream, m, a) : gru2_fwd((hipStream_t)stream, m, a);
-    case FAM_GRU: return gru_wide_ok(m) ? gru_wide_fwd((hipStream_t)stream, m, a) : gru_family_fwd((hipStream_t)stream, m, a);
-    case FAM_LSTM:
-        if (vdlstm_wide_ok(m)) return vdlstm_wide_fwd((hipStream_t)stream, m, a);
-        return lstm_wide_ok(m) ? lstm_wide_fwd((hipStream_t)stream, m, a) : lstm_family_fwd((hipStream_t)stream, m, a);
-    case FAM_DELTA:
-        if (deltajanet_wide_ok(m)) return deltajanet_wide_fwd((hipStream_t)stream, m, a);
-        return delta_wide_ok(m) ? delta_wide_fwd((hipStream_t)stream, m, a) : delta_family_fwd((hipStream_t)stream, m, a);
-    case FAM_JANET:
-        if (m->bits_w > 0) return pgjanet_q_fwd((hipStream_t)stream, m, a);      // `--quant`: six INT_Linear (pgjanet_q.hip)
-        return pgjanet_wide_ok(m) ? pgjanet_wide_fwd((hipStream_t)stream, m, a) : janet_family_fwd((hipStream_t)stream, m, a);
-    case FAM_DVR: return dvrjanet_launch((hipStream_t)stream, m, a, 1);
-    case FAM_BOJ: return bojanet_launch((hipStream_t)stream, m, a, 1);
-    case FAM_APN: return apnrru_launch((hipStream_t)stream, m, a, 1);
-    case FAM_MCL: return mcldnn_launch((hipStream_t)stream, m, a, 1);
-    case FAM_TCNN: return tcnn_fwd((hipStream_t)stream, m, a);
-    case FAM_GMP: return gmp_fwd((hipStream_t)stream, m, a);
-    case FAM_RVTDCNN: return rvtdcnn_fwd((hipStream_t)stream, m, a);
+    case FAM_GRU: return gru_family_fwd(st, m, a);
+    case FAM_LSTM: return lstm_family_fwd(st, m, a);
+    case FAM_DELTA: return delta_family_fwd(st, m, a);
+    case FAM_JANET: return janet_family_fwd(st, m, a);
+    case FAM_TCNN: return tcnn_fwd(st, m, a);
+    case FAM_GMP: return gmp_fwd(st, m, a);
+    case FAM_RVTDCNN: return rvtdcnn_fwd(st, m, a);
     case FAM_QAT:
-        if (qat_uses_gp_eval(m, B, ckpt != nullptr)) return qat_gp_eval((hipStream_t)stream, m, a);
-        return qat_uses_s16(m, B) ? qat_s16_launch((hipStream_t)stream, m, a, 1) : qgru_family_fwd((hipStream_t)stream, m, a);
+        if (qat_uses_gp_eval(m, B, ckpt != nullptr)) return qat_gp_eval(st, m, a);
+        return qat_uses_s16(m, B) ? qat_s16_launch(st, m, a, 1) : qgru_family_fwd(st, m, a);
     default: return ODPD_EUNSUPPORTED;
     }
 }
@@ -385,100 +427,67 @@ extern "C" int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int
 extern "C" int odpd_backbone_bwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                                  const float* x, const float* dy, const float* ckpt, float* partials, float* dx) {
     if (!model_ok(m) || !params || !x || !dy || B <= 0 || T <= 0 || (!partials && !dx)) return ODPD_EINVAL;
-    if (init_state(m)) return init_state_ok(m) ? ODPD_EINVAL : ODPD_EUNSUPPORTED;      // (the flag's backward is odpd_backbone_bwd_state)
+    const int r = route_of(m);
+    if (r == ROUTE_REFUSED) return ODPD_EUNSUPPORTED;
+    if (init_state(m)) return ODPD_EINVAL;      // (served, but by odpd_backbone_bwd_state)
+    hipStream_t st = (hipStream_t)stream;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx;
+    if (r >= 0) return kRoutes[r].bwd(st, m, a);
+    if (const F4Backbone* f = f4_of(m)) return f->launch(st, m, a, 2);
+    const bool no_ckpt = !ckpt && a.nck > 1;      // the row-rotated kernels restart every block but the first from a checkpoint
     switch (family_of(m)) {
-    case FAM_QCELL: return m->backbone == ODPD_DVRJANET ? dvrjanet_q_bwd((hipStream_t)stream, m, a) : bojanet_q_bwd((hipStream_t)stream, m, a);
-    case FAM_GRU2: return lstm2_ok(m) ? lstm2_bwd((hipStream_t)stream, m, a) : gru2_bwd((hipStream_t)stream, m, a);
-    case FAM_GRU:
-        if (gru_wide_ok(m)) return gru_wide_bwd((hipStream_t)stream, m, a);
-        if (!ckpt && a.nck > 1) return ODPD_EINVAL;
-        return gru_family_bwd((hipStream_t)stream, m, a);
-    case FAM_LSTM:
-        if (lstm_wide_ok(m)) return lstm_wide_bwd((hipStream_t)stream, m, a);
-        if (vdlstm_wide_ok(m)) return vdlstm_wide_bwd((hipStream_t)stream, m, a);
-        if (!ckpt && a.nck > 1) return ODPD_EINVAL;
-        return lstm_family_bwd((hipStream_t)stream, m, a);
-    case FAM_DELTA:
-        if (delta_wide_ok(m)) return delta_wide_bwd((hipStream_t)stream, m, a);
-        if (deltajanet_wide_ok(m)) return deltajanet_wide_bwd((hipStream_t)stream, m, a);
-        if (!ckpt && a.nck > 1) return ODPD_EINVAL;
-        return delta_family_bwd((hipStream_t)stream, m, a);
-    case FAM_JANET:
-        if (m->bits_w > 0) return pgjanet_q_bwd((hipStream_t)stream, m, a);
-        if (pgjanet_wide_ok(m)) return pgjanet_wide_bwd((hipStream_t)stream, m, a);
-        if (!ckpt && a.nck > 1) return ODPD_EINVAL;
-        return janet_family_bwd((hipStream_t)stream, m, a);
-    case FAM_DVR: return dvrjanet_launch((hipStream_t)stream, m, a, 2);
-    case FAM_BOJ: return bojanet_launch((hipStream_t)stream, m, a, 2);
-    case FAM_APN: return apnrru_launch((hipStream_t)stream, m, a, 2);
-    case FAM_MCL: return mcldnn_launch((hipStream_t)stream, m, a, 2);
-    case FAM_TCNN: return tcnn_bwd((hipStream_t)stream, m, a);
-    case FAM_GMP: return gmp_bwd((hipStream_t)stream, m, a);
-    case FAM_RVTDCNN: return rvtdcnn_bwd((hipStream_t)stream, m, a);
+    case FAM_GRU: return no_ckpt ? (int)ODPD_EINVAL : gru_family_bwd(st, m, a);
+    case FAM_LSTM: return no_ckpt ? (int)ODPD_EINVAL : lstm_family_bwd(st, m, a);
+    case FAM_DELTA: return no_ckpt ? (int)ODPD_EINVAL : delta_family_bwd(st, m, a);
+    case FAM_JANET: return no_ckpt ? (int)ODPD_EINVAL : janet_family_bwd(st, m, a);
+    case FAM_TCNN: return tcnn_bwd(st, m, a);
+    case FAM_GMP: return gmp_bwd(st, m, a);
+    case FAM_RVTDCNN: return rvtdcnn_bwd(st, m, a);
     case FAM_QAT:
-        if (qat_uses_s16(m, B)) return qat_s16_launch((hipStream_t)stream, m, a, 2);      // (checks its own checkpoint count)
-        if (!ckpt && a.nck > 1) return ODPD_EINVAL;
-        return qgru_family_bwd((hipStream_t)stream, m, a);
+        if (qat_uses_s16(m, B)) return qat_s16_launch(st, m, a, 2);      // (checks its own checkpoint count)
+        return no_ckpt ? (int)ODPD_EINVAL : qgru_family_bwd(st, m, a);
     default: return ODPD_EUNSUPPORTED;
     }
 }
 
-// the state route (ODPD_FLAG_INIT_STATE): the lane-per-unit kernels of gru_wide.hip / lstm_wide.hip at every hidden size 1 .. 64
+// the state route (ODPD_FLAG_INIT_STATE: route_of answers nothing but one of its two kernel sets, or ROUTE_REFUSED)
 extern "C" int odpd_backbone_fwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
                                        float* y, float* ckpt) {
     if (!model_ok(m) || !params || !x || !h0 || !y || B <= 0 || T <= 0 || !init_state(m)) return ODPD_EINVAL;
-    if (!init_state_ok(m)) return ODPD_EUNSUPPORTED;
+    const int r = route_of(m);
+    if (r < 0) return ODPD_EUNSUPPORTED;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.h0 = h0;
-    return family_of(m) == FAM_LSTM ? lstm_state_fwd((hipStream_t)stream, m, a) : gru_state_fwd((hipStream_t)stream, m, a);
+    return kRoutes[r].fwd((hipStream_t)stream, m, a);
 }
 extern "C" int odpd_backbone_bwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
                                        const float* dy, const float* ckpt, float* partials, float* dx, float* dh0) {
     if (!model_ok(m) || !params || !x || !h0 || !dy || !ckpt || B <= 0 || T <= 0 || (!partials && !dx && !dh0) || !init_state(m))
         return ODPD_EINVAL;
-    if (!init_state_ok(m)) return ODPD_EUNSUPPORTED;
+    const int r = route_of(m);
+    if (r < 0) return ODPD_EUNSUPPORTED;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx; a.h0 = h0; a.dh0 = dh0;
-    return family_of(m) == FAM_LSTM ? lstm_state_bwd((hipStream_t)stream, m, a) : gru_state_bwd((hipStream_t)stream, m, a);
+    return kRoutes[r].bwd((hipStream_t)stream, m, a);
 }
 
+// `workspace` of the two fused entry points into the launch arguments, as the step's kernel takes it (WsKind)
+static void set_workspace(SeqArgs& a, const FusedStep& f, float* workspace) {
+    a.ckpt = workspace;      // (WS_UNUSED: handed on all the same, as it always was)
+    if (f.ws == WS_COUNTERS) { a.stats = reinterpret_cast<double*>(workspace); a.ckpt = nullptr; }
+}
 extern "C" int odpd_train_fwd_bwd(void* stream, const odpd_model_t* m, int loss_kind, int B, int T, int64_t count,
                                   const float* params, const float* x, const float* target, float* partials,
                                   float* workspace) {
     if (!model_ok(m) || !params || !x || !target || !partials || B <= 0 || T <= 0 || count <= 0) return ODPD_EINVAL;
-    if (lane_per_unit_model(m)) return ODPD_EUNSUPPORTED;
+    const FusedStep f = fused_step(m, B, T);
+    if (!f.train) return ODPD_EUNSUPPORTED;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.target = target; a.partials = partials;
-    a.inv_count = (float)(1.0 / (double)count); a.loss_kind = loss_kind; a.ckpt = workspace;
-    switch (family_of(m)) {
-    case FAM_GRU:
-        if (gru_uses_s16n(m, B))
-            return gru_s16x_train_ok(m) ? gru_s16x_train((hipStream_t)stream, m, a, gru_s16n_rows(m, B)) : gru_s16n_launch((hipStream_t)stream, m, a, 0);
-        return gru_train_uses_s16(m, B, T) ? gru_s16_train((hipStream_t)stream, m, a)
-                                           : gru_family_train((hipStream_t)stream, m, a);
-    case FAM_LSTM:
-        return lstm_train_uses_s16(m, B) ? lstm_s16_train((hipStream_t)stream, m, a)
-                                         : lstm_train_uses_gp(m, B, T) ? lstm_gp_train((hipStream_t)stream, m, a) : (int)ODPD_EUNSUPPORTED;
-    case FAM_JANET: return janet_train_uses_gp(m, B, T) ? janet_gp_train((hipStream_t)stream, m, a) : (int)ODPD_EUNSUPPORTED;
-    case FAM_DELTA:      // delta backbones: `workspace` = the four sparsity counters of the step's forward pass (double[4], may be NULL)
-        a.stats = reinterpret_cast<double*>(workspace); a.ckpt = nullptr;
-        return delta_gp_train((hipStream_t)stream, m, a);
-    case FAM_BOJ: return bojanet_train_uses_gp(m, B, T) ? bojanet_gp_train((hipStream_t)stream, m, a) : (int)ODPD_EUNSUPPORTED;
-    case FAM_APN: return apnrru_train_uses_gp(m, B, T) ? apnrru_gp_train((hipStream_t)stream, m, a) : (int)ODPD_EUNSUPPORTED;
-    case FAM_DVR: return dvrjanet_train_uses_gp(m, B, T) ? dvrjanet_gp_train((hipStream_t)stream, m, a) : (int)ODPD_EUNSUPPORTED;
-    case FAM_MCL: return mcldnn_train_uses_gp(m, B, T) ? mcldnn_gp_train((hipStream_t)stream, m, a) : (int)ODPD_EUNSUPPORTED;
-    case FAM_GMP: return gmp_train((hipStream_t)stream, m, a);
-    case FAM_RVTDCNN: return rvtdcnn_train((hipStream_t)stream, m, a);
-    case FAM_QAT:
-        if (qat_train_uses_gp(m, B, T)) {
-            a.stats = m->backbone == ODPD_TRES_DELTAGRU ? reinterpret_cast<double*>(workspace) : nullptr; a.ckpt = nullptr;
-            return qat_gp_train((hipStream_t)stream, m, a);
-        }
-        return qat_uses_s16(m, B) ? qat_s16_launch((hipStream_t)stream, m, a, 0) : (int)ODPD_EUNSUPPORTED;
-    default: return ODPD_EUNSUPPORTED;
-    }
+    a.inv_count = (float)(1.0 / (double)count); a.loss_kind = loss_kind;
+    set_workspace(a, f, workspace);
+    return f.train((hipStream_t)stream, m, a);      // (whatever f.rows says: a launcher named for a shape it does not take answers for itself)
 }
 
 // Frozen model in front of the loss (the PA of train_dpd): forward + loss + dL/du in ONE launch.  Available for the GRU family
@@ -486,14 +495,14 @@ extern "C" int odpd_train_fwd_bwd(void* stream, const odpd_model_t* m, int loss_
 // ODPD_EUNSUPPORTED (rows < 0) and the caller chains odpd_backbone_fwd, odpd_loss_fwd_bwd, odpd_backbone_bwd.
 extern "C" int64_t odpd_frozen_loss_rows(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    if (family_of(m) != FAM_GRU || lane_per_unit_model(m)) return ODPD_EUNSUPPORTED;
+    if (!gru_family_model(m)) return ODPD_EUNSUPPORTED;
     return gru_family_lossdx_rows(m, B, T);
 }
 extern "C" int odpd_frozen_loss_dx(void* stream, const odpd_model_t* m, int loss_kind, int B, int T, int64_t count,
                                    const float* params, const float* u, const float* target, float* du, float* loss_rows,
                                    float* workspace) {
     if (!model_ok(m) || !params || !u || !target || !du || !loss_rows || !workspace || B <= 0 || T <= 0 || count <= 0) return ODPD_EINVAL;
-    if (family_of(m) != FAM_GRU || lane_per_unit_model(m)) return ODPD_EUNSUPPORTED;
+    if (!gru_family_model(m)) return ODPD_EUNSUPPORTED;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = u; a.target = target; a.dx = du; a.partials = loss_rows;
     a.inv_count = (float)(1.0 / (double)count); a.loss_kind = loss_kind; a.ckpt = workspace;
@@ -531,51 +540,14 @@ extern "C" int odpd_cascade_fwd_bwd(void* stream, const odpd_model_t* dpd, const
 }
 
 namespace {
-// backbones whose fused train kernel addresses frames inside resident streams (SeqArgs::frame_idx)
+// backbones whose fused train kernel addresses frames inside resident streams (SeqArgs::frame_idx) at every batch shape
 inline bool framed_train_ok(const odpd_model_t* m) {
-    if (init_state(m)) return false;      // (ODPD_FLAG_INIT_STATE: forward / backward only, whatever the backbone)
-    return (!lane_per_unit_model(m) && family_of(m) == FAM_GRU) || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN;
+    return route_of(m) == ROUTE_NONE && (family_of(m) == FAM_GRU || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN);
 }
-// ... for this batch shape: also the one-sequence-per-wave fused kernels of lstm / vdlstm / pgjanet (their large-batch kernels take tensors)
+// ... for this batch shape: also the one-sequence-per-wave fused kernels of the other families (the large-batch kernel of lstm / vdlstm takes tensors)
 inline bool framed_train_ok_shape(const odpd_model_t* m, int B, int T) {
-    if (lane_per_unit_model(m)) return false;
-    if (framed_train_ok(m)) return true;
-    if (family_of(m) == FAM_QAT) return qat_train_uses_gp(m, B, T) || qat_uses_s16(m, B);
-    if (family_of(m) == FAM_LSTM) return !lstm_train_uses_s16(m, B) && lstm_train_uses_gp(m, B, T);
-    if (family_of(m) == FAM_JANET) return janet_train_uses_gp(m, B, T);
-    if (family_of(m) == FAM_DELTA) return delta_train_uses_gp(m, B, T);
-    if (family_of(m) == FAM_BOJ) return bojanet_train_uses_gp(m, B, T);
-    if (family_of(m) == FAM_APN) return apnrru_train_uses_gp(m, B, T);
-    if (family_of(m) == FAM_DVR) return dvrjanet_train_uses_gp(m, B, T);
-    if (family_of(m) == FAM_MCL) return mcldnn_train_uses_gp(m, B, T);
-    return false;
-}
-inline int framed_train_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (family_of(m) == FAM_QAT) {
-        if (qat_train_uses_gp(m, a.B, a.T)) {      // (the `workspace` pointer of the framed entry points: the counters, as for the delta backbones)
-            SeqArgs b = a;
-            b.stats = m->backbone == ODPD_TRES_DELTAGRU ? reinterpret_cast<double*>(a.ckpt) : nullptr; b.ckpt = nullptr;
-            return qat_gp_train(st, m, b);
-        }
-        return framed_train_ok_shape(m, a.B, a.T) ? qat_s16_launch(st, m, a, 0) : (int)ODPD_EUNSUPPORTED;
-    }
-    if (family_of(m) == FAM_GMP) return gmp_train(st, m, a);
-    if (family_of(m) == FAM_RVTDCNN) return rvtdcnn_train(st, m, a);
-    if (family_of(m) == FAM_LSTM) return framed_train_ok_shape(m, a.B, a.T) ? lstm_gp_train(st, m, a) : (int)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_JANET) return framed_train_ok_shape(m, a.B, a.T) ? janet_gp_train(st, m, a) : (int)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_DELTA) {     // the `workspace` pointer of the framed entry points carries the sparsity counters here
-        SeqArgs b = a;
-        b.stats = reinterpret_cast<double*>(a.ckpt); b.ckpt = nullptr;
-        return delta_gp_train(st, m, b);
-    }
-    if (family_of(m) == FAM_BOJ) return framed_train_ok_shape(m, a.B, a.T) ? bojanet_gp_train(st, m, a) : (int)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_APN) return framed_train_ok_shape(m, a.B, a.T) ? apnrru_gp_train(st, m, a) : (int)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_DVR) return framed_train_ok_shape(m, a.B, a.T) ? dvrjanet_gp_train(st, m, a) : (int)ODPD_EUNSUPPORTED;
-    if (family_of(m) == FAM_MCL) return framed_train_ok_shape(m, a.B, a.T) ? mcldnn_gp_train(st, m, a) : (int)ODPD_EUNSUPPORTED;
-    const bool s16n = gru_uses_s16n(m, a.B), s16 = !s16n && gru_train_uses_s16(m, a.B, a.T);
-    if ((s16 || s16n) && !a.ckpt) return ODPD_EINVAL;
-    if (s16n) return gru_s16x_train_ok(m) ? gru_s16x_train(st, m, a, gru_s16n_rows(m, a.B)) : gru_s16n_launch(st, m, a, 0);
-    return s16 ? gru_s16_train(st, m, a) : gru_family_train(st, m, a);
+    const FusedStep f = fused_step(m, B, T);
+    return f.train && f.framed;
 }
 // bf16 sample storage is read by the float GRU family's fused train kernels (stage_in / ld_iq); every other path wants fp32 streams
 inline bool frames_format_ok(const odpd_model_t* m, const odpd_frames_t* fr) {
@@ -597,12 +569,17 @@ extern "C" int odpd_train_fwd_bwd_framed(void* stream, const odpd_model_t* m, in
         first < 0 || B <= 0 || first + B > fr->n_frames || count <= 0 || !params || !partials)
         return ODPD_EINVAL;
     const int T = fr->frame_length;
-    if (!framed_train_ok_shape(m, B, T) || !frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;
+    const FusedStep f = fused_step(m, B, T);
+    if (!f.train || !f.framed || !frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;
+    // (only here, and only for the float GRU family's checkpoints: a NULL workspace is refused in front of the launcher — odpd_train_fwd_bwd
+    // leaves it to the launcher, and the quantised step takes NULL where one checkpoint does: qat_s16.hip)
+    if (f.ws == WS_CKPT && !workspace && family_of(m) == FAM_GRU) return ODPD_EINVAL;
     SeqArgs a = make_args(m, B, T);
-    a.params = params; a.x = fr->x_stream; a.target = fr->y_stream; a.partials = partials; a.ckpt = workspace;
+    a.params = params; a.x = fr->x_stream; a.target = fr->y_stream; a.partials = partials;
     a.frame_idx = (const long long*)(fr->order + first); a.frame_stride = fr->stride; a.frames_bf16 = fr->sample_format == ODPD_SAMPLES_BF16;
     a.inv_count = (float)(1.0 / (double)count); a.loss_kind = loss_kind;
-    return framed_train_launch((hipStream_t)stream, m, a);
+    set_workspace(a, f, workspace);
+    return f.train((hipStream_t)stream, m, a);
 }
 
 // rank `rank` of `world` takes items [lo, hi) of n: contiguous shares, the first n % world ranks one item more
@@ -878,16 +855,16 @@ inline int run_sweep_epoch(hipStream_t st, int K, const odpd_sweep_run_t* runs, 
 }  // namespace
 extern "C" int64_t odpd_sweep_scratch_bytes(int K, int64_t n_steps) { return sweep_scratch_bytes(K, n_steps, false); }
 extern "C" int odpd_sweep_train_supported(const odpd_model_t* m, int B, int T) {
-    return model_ok(m) && family_of(m) == FAM_GRU && !lane_per_unit_model(m) && gru_sweep_train_ok(m, B, T) ? 1 : 0;
+    return model_ok(m) && gru_family_model(m) && gru_sweep_train_ok(m, B, T) ? 1 : 0;
 }
 extern "C" int odpd_sweep_fwd_supported(const odpd_model_t* m, int B, int T) {
-    return model_ok(m) && family_of(m) == FAM_GRU && !lane_per_unit_model(m) && gru_sweep_eval_ok(m, B, T) ? 1 : 0;
+    return model_ok(m) && gru_family_model(m) && gru_sweep_eval_ok(m, B, T) ? 1 : 0;
 }
 extern "C" int odpd_sweep_s16_supported(const odpd_model_t* m) {
-    return model_ok(m) && family_of(m) == FAM_GRU && !lane_per_unit_model(m) && gru_s16_sweep_ok(m) ? 1 : 0;
+    return model_ok(m) && gru_family_model(m) && gru_s16_sweep_ok(m) ? 1 : 0;
 }
 extern "C" int64_t odpd_sweep_partial_rows(const odpd_model_t* m, int B, int T, int flags) {
-    if (!model_ok(m) || B <= 0 || T <= 0 || family_of(m) != FAM_GRU || lane_per_unit_model(m)) return ODPD_EUNSUPPORTED;
+    if (!model_ok(m) || B <= 0 || T <= 0 || !gru_family_model(m)) return ODPD_EUNSUPPORTED;
     if (flags & ODPD_SWEEP_S16) return gru_s16_sweep_ok(m) ? gru_s16_rows(m, B) : (int64_t)ODPD_EUNSUPPORTED;
     return gru_sweep_train_ok(m, B, T) ? gru_sweep_train_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
 }
@@ -904,7 +881,7 @@ extern "C" int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K
     if (!sweep_runs_ok(K, runs, [](int) { return true; })) return ODPD_EINVAL;
     const int T = fr->frame_length;
     const bool s16 = (flags & ODPD_SWEEP_S16) != 0;
-    if (family_of(m) != FAM_GRU || lane_per_unit_model(m) || !frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;      // (bf16 frames: served)
+    if (!gru_family_model(m) || !frames_format_ok(m, fr)) return ODPD_EUNSUPPORTED;      // (bf16 frames: served)
     if (s16) {      // the 16-sequences-per-wave kernel: any batch shape, checkpoints in every run's workspace
         if (!gru_s16_sweep_ok(m)) return ODPD_EUNSUPPORTED;
         for (int k = 0; k < K; ++k)
@@ -960,7 +937,7 @@ extern "C" int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int 
     if (!model_ok(m) || K <= 0 || !runs || !x || B <= 0 || T <= 0 || !scratch) return ODPD_EINVAL;
     for (int k = 0; k < K; ++k)
         if (!runs[k].params || !runs[k].y) return ODPD_EINVAL;
-    if (family_of(m) != FAM_GRU || lane_per_unit_model(m) || !gru_sweep_eval_ok(m, B, T)) return ODPD_EUNSUPPORTED;
+    if (!gru_family_model(m) || !gru_sweep_eval_ok(m, B, T)) return ODPD_EUNSUPPORTED;
     SweepRun* dev = nullptr;
     if (int rc = upload_sweep((hipStream_t)stream, K, runs, 0.0, scratch, &dev)) return rc;
     SeqArgs a = make_args(m, B, T);
