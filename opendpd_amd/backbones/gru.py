@@ -38,9 +38,7 @@ class GRU(NativeBackbone):
         self.hidden_size, self.input_size, self.output_size, self.num_layers = hidden_size, input_size, output_size, num_layers
         self.rnn = RnnParams(input_size, hidden_size, gates=3, num_layers=num_layers)
         self.fc_out = nn.Linear(hidden_size, output_size, bias=True)
-        self._finalize(hidden_size)
-        if num_layers == 2:
-            self.desc.flags |= _lib.FLAG_TWO_LAYERS
+        self._finalize(hidden_size, flags=_lib.FLAG_TWO_LAYERS if num_layers == 2 else 0)
 
     def reset_parameters(self):
         init_gatewise(self.rnn, self.hidden_size)
@@ -58,9 +56,7 @@ class DGRU(NativeBackbone):
         self.rnn = RnnParams(6, hidden_size, gates=3, num_layers=num_layers)
         self.fc_out = nn.Linear(hidden_size + 6, output_size, bias=True)
         self.fc_hid = nn.Linear(hidden_size, hidden_size, bias=True)
-        self._finalize(hidden_size)
-        if num_layers == 2:
-            self.desc.flags |= _lib.FLAG_TWO_LAYERS
+        self._finalize(hidden_size, flags=_lib.FLAG_TWO_LAYERS if num_layers == 2 else 0)
 
     def reset_parameters(self):
         init_gatewise(self.rnn, self.hidden_size)
@@ -79,9 +75,7 @@ class QGRU(NativeBackbone):
         self.hidden_size, self.input_size, self.output_size, self.num_layers = hidden_size, 4, output_size, num_layers
         self.rnn = RnnParams(4, hidden_size, gates=3, num_layers=num_layers)
         self.fc_out = nn.Linear(hidden_size, output_size, bias=True)
-        self._finalize(hidden_size)
-        if num_layers == 2:
-            self.desc.flags |= _lib.FLAG_TWO_LAYERS
+        self._finalize(hidden_size, flags=_lib.FLAG_TWO_LAYERS if num_layers == 2 else 0)
 
     def reset_parameters(self):
         # qgru.py:37-57: rnn + fc_out are re-initialised, then the reference touches a non-existent

@@ -27,9 +27,7 @@ class LSTM(NativeBackbone):
         self.hidden_size, self.input_size, self.output_size, self.num_layers = hidden_size, input_size, output_size, num_layers
         self.rnn = RnnParams(input_size, hidden_size, gates=4, num_layers=num_layers)
         self.fc_out = nn.Linear(hidden_size, output_size, bias=True)
-        self._finalize(hidden_size)
-        if num_layers == 2:
-            self.desc.flags |= _lib.FLAG_TWO_LAYERS
+        self._finalize(hidden_size, flags=_lib.FLAG_TWO_LAYERS if num_layers == 2 else 0)
 
     def reset_parameters(self):
         init_gatewise(self.rnn, self.hidden_size)

@@ -68,128 +68,56 @@ def init_linear(lin, weight="xavier"):
 
 
 class _BackboneFn(torch.autograd.Function):
-    """y = backbone(x) through odpd_backbone_fwd / odpd_backbone_bwd.
+    """y = backbone(x) through odpd_backbone_fwd / odpd_backbone_bwd — or, given an initial state h_0 (1, B, H), through
+    odpd_backbone_fwd_state / odpd_backbone_bwd_state (ODPD_FLAG_INIT_STATE: the lane-per-unit kernels of gru_wide.hip / lstm_wide.hip),
+    whose backward also returns dL/dh_0 in h_0's dtype and shape.
 
-    The kernel-selection knobs (odpd_set_tuning) choose the kernel, and with it the checkpoint layout, at each of the two calls, and the
-    checkpoint carries no record of the layout it was written in.  So the backward refuses to run when odpd_tuning_generation moved since
+    The forward states its kernel selection as ONE descriptor (NativeBackbone.call_desc) and the backward sizes and launches with that same
+    object.  The kernel-selection knobs (odpd_set_tuning) choose the kernel, and with it the checkpoint layout, at each of the two calls, and
+    the checkpoint carries no record of the layout it was written in.  So the backward refuses to run when odpd_tuning_generation moved since
     its forward wrote the checkpoints.  The rule is deliberately conservative: any movement refuses, also a knob set and then set back."""
 
     @staticmethod
-    def forward(ctx, x, mod, grad_mode, *params):
+    def forward(ctx, x, h_0, mod, grad_mode, *params):
+        from ..train_funcs import ckpt_buffer
         lib = _lib.load()
         if not x.is_cuda:
             raise RuntimeError("opendpd_amd backbones run on a HIP device only (no CPU fallback)")
         x = x.contiguous().float()
         B, T = x.shape[0], x.shape[1]
+        h0 = None if h_0 is None else h_0.detach().reshape(B, mod.hidden_size).float().contiguous()      # the kernels run in fp32
         flat = mod.flat_params()
         # (needs_input_grad looks at requires_grad only: under torch.no_grad() — net_eval, run_dpd — nothing will call backward, so no
         # checkpoints are asked for and the kernels may take their inference path)
         need_grad = grad_mode and any(ctx.needs_input_grad)      # (autograd switches grad mode off inside forward: the caller passes it)
-        if mod.dx_needs_flag:
-            # delta backbones: dL/dx lives in the 16-sequences-per-wave kernels only; the flag routes forward, checkpoint sizing
-            # and backward of THIS call to them (include/opendpd_hip.h: ODPD_FLAG_NEED_DX)
-            mod.desc.flags = (mod.desc.flags & ~_lib.FLAG_NEED_DX) | (_lib.FLAG_NEED_DX if ctx.needs_input_grad[0] else 0)
-        ctx.flags = mod.desc.flags
+        # delta backbones: dL/dx lives in the 16-sequences-per-wave kernels only; the flag routes forward, checkpoint sizing and backward of
+        # THIS call to them (include/opendpd_hip.h: ODPD_FLAG_NEED_DX)
+        d = ctx.desc = mod.call_desc(need_dx=ctx.needs_input_grad[0], init_state=h0 is not None)
         ctx.generation = None
         y = torch.empty_like(x)
         ckpt = None
         if need_grad:
             ctx.generation = int(lib.odpd_tuning_generation())      # (before the size query: the layout is the one of this generation)
-            n = lib.odpd_ckpt_floats(C.byref(mod.desc), B, T)
-            _lib.check(0 if n >= 0 else int(n), "odpd_ckpt_floats")
-            ckpt = torch.empty(max(int(n), 1), dtype=torch.float32, device=x.device)
-        stats = mod._stats_buffer(x.device)
-        rc = lib.odpd_backbone_fwd(_lib.stream_ptr(), C.byref(mod.desc), B, T, _lib.ptr(flat), _lib.ptr(x),
-                                   _lib.ptr(y), _lib.ptr(ckpt), _lib.ptr(stats))
-        _lib.check(rc, f"odpd_backbone_fwd[{mod.backbone_name}]")
+            ckpt = ckpt_buffer(d, B, T, x.device)
+        if h0 is None:
+            rc = lib.odpd_backbone_fwd(_lib.stream_ptr(), C.byref(d), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(y), _lib.ptr(ckpt),
+                                       _lib.ptr(mod._stats_buffer(x.device)))
+            _lib.check(rc, f"odpd_backbone_fwd[{mod.backbone_name}]")
+        else:
+            rc = lib.odpd_backbone_fwd_state(_lib.stream_ptr(), C.byref(d), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(h0), _lib.ptr(y),
+                                             _lib.ptr(ckpt))
+            _lib.check(rc, f"odpd_backbone_fwd_state[{mod.backbone_name}]")
+            ctx.h0_dtype, ctx.h0_shape = h_0.dtype, h_0.shape
         ctx.mod = mod
-        ctx.save_for_backward(x, ckpt if ckpt is not None else x.new_empty(0), flat)
+        ctx.save_for_backward(x, ckpt if ckpt is not None else x.new_empty(0), flat, *(() if h0 is None else (h0,)))
         return y
 
     @staticmethod
     def backward(ctx, dy):
+        from ..train_funcs import partials_buffer
         lib = _lib.load()
-        mod = ctx.mod
-        x, ckpt, flat = ctx.saved_tensors
-        B, T = x.shape[0], x.shape[1]
-        if ctx.generation is not None and int(lib.odpd_tuning_generation()) != ctx.generation:
-            if mod.dx_needs_flag:
-                mod.desc.flags &= ~_lib.FLAG_NEED_DX       # (as after a backward that ran: nothing stale for the next user of the descriptor)
-            raise RuntimeError(f"{mod.backbone_name}: the kernel-selection knobs (odpd_set_tuning) changed between forward and backward; "
-                               "the checkpoints of the forward may be laid out for another kernel, so no gradients were written. "
-                               "Run the forward again under the current knobs.")
-        dy = dy.contiguous().float()
-        need_dx = ctx.needs_input_grad[0]
-        need_w = any(ctx.needs_input_grad[3:])
-        P = mod.n_flat
-        partials = grad = dx = None
-        mod.desc.flags = ctx.flags
-        if need_w or (need_dx and mod.dx_needs_flag):      # the delta kernels compute the weight gradients in every backward launch
-            rows = int(lib.odpd_partial_rows(C.byref(mod.desc), B, T, 0))
-            _lib.check(0 if rows > 0 else rows, "odpd_partial_rows")
-            partials = torch.empty(rows, P + _lib.LOSS_COLS, dtype=torch.float32, device=x.device)
-        if need_dx:
-            dx = torch.empty_like(x)
-        if not (need_w or need_dx):
-            return (None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-        rc = lib.odpd_backbone_bwd(_lib.stream_ptr(), C.byref(mod.desc), B, T, _lib.ptr(flat), _lib.ptr(x),
-                                   _lib.ptr(dy), _lib.ptr(ckpt) if ckpt.numel() else None, _lib.ptr(partials),
-                                   _lib.ptr(dx))
-        _lib.check(rc, f"odpd_backbone_bwd[{mod.backbone_name}]")
-        if mod.dx_needs_flag:
-            mod.desc.flags &= ~_lib.FLAG_NEED_DX       # per-call selection: nothing stale for the next user of the descriptor
-        gparams = (None,) * (len(ctx.needs_input_grad) - 3)
-        if need_w:
-            grad = torch.empty(P + _lib.LOSS_COLS, dtype=torch.float32, device=x.device)
-            rc = lib.odpd_reduce_partials(_lib.stream_ptr(), partials.shape[0], P, _lib.ptr(partials), _lib.ptr(grad), 0)
-            _lib.check(rc, "odpd_reduce_partials")
-            gparams = tuple(grad[o:o + n].view(shape) if need else None
-                            for (o, n, shape), need in zip(mod._slices, ctx.needs_input_grad[3:]))
-        return (dx, None, None) + gparams
-
-
-class _BackboneStateFn(torch.autograd.Function):
-    """y = backbone(x) from the initial state h_0 (1, B, H) through odpd_backbone_fwd_state / odpd_backbone_bwd_state (ODPD_FLAG_INIT_STATE:
-    the lane-per-unit kernels of gru_wide.hip / lstm_wide.hip); the backward also returns dL/dh_0, in h_0's dtype and shape.
-
-    The flag is set on the descriptor for each call and cleared after it.  The backward refuses to run when odpd_tuning_generation moved
-    since its forward, as _BackboneFn's does."""
-
-    @staticmethod
-    def forward(ctx, x, h_0, mod, grad_mode, *params):
-        lib = _lib.load()
-        if not x.is_cuda:
-            raise RuntimeError("opendpd_amd backbones run on a HIP device only (no CPU fallback)")
-        x = x.contiguous().float()
-        B, T = x.shape[0], x.shape[1]
-        h0 = h_0.detach().reshape(B, mod.hidden_size).float().contiguous()      # the kernels run in fp32
-        flat = mod.flat_params()
-        need_grad = grad_mode and any(ctx.needs_input_grad)
-        ctx.generation = None
-        y = torch.empty_like(x)
-        ckpt = None
-        mod.desc.flags |= _lib.FLAG_INIT_STATE
-        try:
-            if need_grad:
-                ctx.generation = int(lib.odpd_tuning_generation())
-                n = lib.odpd_ckpt_floats(C.byref(mod.desc), B, T)
-                _lib.check(0 if n >= 0 else int(n), "odpd_ckpt_floats")
-                ckpt = torch.empty(max(int(n), 1), dtype=torch.float32, device=x.device)
-            rc = lib.odpd_backbone_fwd_state(_lib.stream_ptr(), C.byref(mod.desc), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(h0),
-                                             _lib.ptr(y), _lib.ptr(ckpt))
-        finally:
-            mod.desc.flags &= ~_lib.FLAG_INIT_STATE
-        _lib.check(rc, f"odpd_backbone_fwd_state[{mod.backbone_name}]")
-        ctx.mod = mod
-        ctx.h0_dtype, ctx.h0_shape = h_0.dtype, h_0.shape
-        ctx.save_for_backward(x, h0, ckpt if ckpt is not None else x.new_empty(0), flat)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        mod = ctx.mod
-        x, h0, ckpt, flat = ctx.saved_tensors
+        mod, d = ctx.mod, ctx.desc
+        x, ckpt, flat, *h0 = ctx.saved_tensors
         B, T = x.shape[0], x.shape[1]
         if ctx.generation is not None and int(lib.odpd_tuning_generation()) != ctx.generation:
             raise RuntimeError(f"{mod.backbone_name}: the kernel-selection knobs (odpd_set_tuning) changed between forward and backward; "
@@ -202,22 +130,23 @@ class _BackboneStateFn(torch.autograd.Function):
         dy = dy.contiguous().float()
         P = mod.n_flat
         partials = dx = dh0 = None
+        if need_w or (need_dx and mod.dx_needs_flag):      # the delta kernels compute the weight gradients in every backward launch
+            partials = partials_buffer(d, (B,), T, 0, P, x.device)
         if need_dx:
             dx = torch.empty_like(x)
-        if need_dh0:
-            dh0 = torch.empty_like(h0)
-        mod.desc.flags |= _lib.FLAG_INIT_STATE
-        try:
-            if need_w:
-                rows = int(lib.odpd_partial_rows(C.byref(mod.desc), B, T, 0))
-                _lib.check(0 if rows > 0 else rows, "odpd_partial_rows")
-                partials = torch.empty(rows, P + _lib.LOSS_COLS, dtype=torch.float32, device=x.device)
-            rc = lib.odpd_backbone_bwd_state(_lib.stream_ptr(), C.byref(mod.desc), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(h0),
-                                             _lib.ptr(dy), _lib.ptr(ckpt) if ckpt.numel() else None, _lib.ptr(partials), _lib.ptr(dx),
-                                             _lib.ptr(dh0))
-        finally:
-            mod.desc.flags &= ~_lib.FLAG_INIT_STATE
-        _lib.check(rc, f"odpd_backbone_bwd_state[{mod.backbone_name}]")
+        ck = _lib.ptr(ckpt) if ckpt.numel() else None
+        if not h0:
+            rc = lib.odpd_backbone_bwd(_lib.stream_ptr(), C.byref(d), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(dy), ck, _lib.ptr(partials),
+                                       _lib.ptr(dx))
+            _lib.check(rc, f"odpd_backbone_bwd[{mod.backbone_name}]")
+        else:
+            if need_dh0:
+                dh0 = torch.empty_like(h0[0])
+            rc = lib.odpd_backbone_bwd_state(_lib.stream_ptr(), C.byref(d), B, T, _lib.ptr(flat), _lib.ptr(x), _lib.ptr(h0[0]), _lib.ptr(dy), ck,
+                                             _lib.ptr(partials), _lib.ptr(dx), _lib.ptr(dh0))
+            _lib.check(rc, f"odpd_backbone_bwd_state[{mod.backbone_name}]")
+            if dh0 is not None:
+                dh0 = dh0.view(ctx.h0_shape).to(ctx.h0_dtype)
         gparams = (None,) * (len(ctx.needs_input_grad) - 4)
         if need_w:
             grad = torch.empty(P + _lib.LOSS_COLS, dtype=torch.float32, device=x.device)
@@ -225,8 +154,6 @@ class _BackboneStateFn(torch.autograd.Function):
             _lib.check(rc, "odpd_reduce_partials")
             gparams = tuple(grad[o:o + n].view(shape) if need else None
                             for (o, n, shape), need in zip(mod._slices, ctx.needs_input_grad[4:]))
-        if dh0 is not None:
-            dh0 = dh0.view(ctx.h0_shape).to(ctx.h0_dtype)
         return (dx, dh0, None, None) + gparams
 
 
@@ -245,10 +172,14 @@ class NativeBackbone(nn.Module):
     dx_needs_flag = False      # True for the delta backbones (ODPD_FLAG_NEED_DX)
     initial_state = H0_REFUSED
 
-    def _finalize(self, hidden_size, thx=0.0, thh=0.0, bits_w=0, bits_a=0):
-        """Call at the end of __init__ once every parameter holder is registered."""
-        self.desc = _lib.ModelDesc(_lib.BACKBONE_IDS[self.backbone_name], int(hidden_size), float(thx), float(thh), int(bits_w),
-                                   int(bits_a), 0)
+    mode_selects_kernel = False      # True where train() / eval() of the module selects a kernel (ODPD_FLAG_EVAL: the quantised models)
+
+    def _finalize(self, hidden_size, thx=0.0, thh=0.0, bits_w=0, bits_a=0, flags=0):
+        """Call at the end of __init__ once every parameter holder is registered.  The arguments are the structural fields of the
+        model's odpd_model_t (`flags`: ODPD_FLAG_TWO_LAYERS, ODPD_FLAG_QUANT_CELL), fixed from here on."""
+        self._desc_fields = (_lib.BACKBONE_IDS[self.backbone_name], int(hidden_size), float(thx), float(thh), int(bits_w), int(bits_a))
+        self._desc_flags = int(flags)
+        self._call_descs = {}
         self._slices = []
         off = 0
         for p in self.parameters():
@@ -297,22 +228,46 @@ class NativeBackbone(nn.Module):
         self._flat = None
         return out
 
+    # -- descriptors -------------------------------------------------------------------------
+    def _mode_flag(self):
+        return _lib.FLAG_EVAL if self.mode_selects_kernel and not self.training else 0
+
+    def _make_desc(self, call_flags):
+        """The one place that builds this model's odpd_model_t: the structural fields plus the flags of one call."""
+        return _lib.ModelDesc(*self._desc_fields, self._desc_flags | call_flags)
+
+    @property
+    def desc(self):
+        """A fresh odpd_model_t of the module as it stands (structural flags; ODPD_FLAG_EVAL where the mode selects a kernel and the module is
+        in eval()): the caller's own copy, for a raw call into the library — editing it never reaches the module."""
+        return self._make_desc(self._mode_flag())
+
+    def call_desc(self, need_dx=False, init_state=False):
+        """The odpd_model_t of ONE call: the per-call kernel selections ODPD_FLAG_NEED_DX (honoured where dx_needs_flag) and
+        ODPD_FLAG_INIT_STATE on top of `desc`.  Cached per selection and shared between callers: read-only."""
+        flags = (self._mode_flag() | (_lib.FLAG_NEED_DX if need_dx and self.dx_needs_flag else 0)
+                 | (_lib.FLAG_INIT_STATE if init_state else 0))
+        d = self._call_descs.get(flags)
+        if d is None:
+            d = self._call_descs[flags] = self._make_desc(flags)
+        return d
+
     def _stats_buffer(self, device):
         return None
 
     def forward(self, x, h_0=None):
-        return _BackboneFn.apply(x, self, torch.is_grad_enabled(), *self.parameters())
+        return _BackboneFn.apply(x, None, self, torch.is_grad_enabled(), *self.parameters())
 
     def state_refusal(self):
         """None when this model can start from a given state on the kernels (forward_state), else the reason it cannot."""
-        if self.desc.bits_w > 0 and self.backbone_name != "dvrjanet":      # (dvrjanet: bits_w carries num_dvr_units)
+        if self._desc_fields[4] > 0 and self.backbone_name != "dvrjanet":      # (bits_w; dvrjanet: it carries num_dvr_units)
             return f"quantised '{self.backbone_name}'"
         if self.initial_state != H0_STATE:
             return f"'{self.backbone_name}'"
-        if self.desc.flags & _lib.FLAG_TWO_LAYERS:
+        if self._desc_flags & _lib.FLAG_TWO_LAYERS:
             return f"two-layer '{self.backbone_name}'"
         return None
 
     def forward_state(self, x, h_0):
         """y = backbone(x) from the initial state h_0 (1, B, H); h_0 may require grad (the state route, ODPD_FLAG_INIT_STATE)."""
-        return _BackboneStateFn.apply(x, h_0, self, torch.is_grad_enabled(), *self.parameters())
+        return _BackboneFn.apply(x, h_0, self, torch.is_grad_enabled(), *self.parameters())

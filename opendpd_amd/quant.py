@@ -126,9 +126,11 @@ class _QRnn(nn.Module):
 class _QuantBase(NativeBackbone):
     """What the quantised backbones share: the optimiser's skip mask, the mode flag, the checkpoint buffers."""
 
-    def _finish(self, hidden_size, bits_w, bits_a, thx=0.0, thh=0.0):
+    mode_selects_kernel = True      # ODPD_FLAG_EVAL: fc_out's 16-bit output quantiser is active in eval only (quant_layers.py:77-80)
+
+    def _finish(self, hidden_size, bits_w, bits_a, thx=0.0, thh=0.0, flags=0):
         self.n_bits_w, self.n_bits_a = bits_w, bits_a
-        self._finalize(hidden_size, thx, thh, bits_w=bits_w, bits_a=bits_a)
+        self._finalize(hidden_size, thx, thh, bits_w=bits_w, bits_a=bits_a, flags=flags)
         # AdamW skips parameters whose grad is None: the out_quantizer scales never enter the train-mode graph
         self.frozen_mask = torch.tensor(np.concatenate([np.full(p.numel(), "out_quantizer" in n) for n, p in self.named_parameters()]))
         self._names = [n for n, _ in self.named_parameters()]
@@ -138,10 +140,9 @@ class _QuantBase(NativeBackbone):
         return super().forward(x, h_0)
 
     def sync_mode(self):
-        """Before every kernel call on this model (autograd path and the direct-ABI train steps alike): the descriptor's
-        ODPD_FLAG_EVAL follows the module's mode — fc_out's 16-bit output quantiser is active in eval only
-        (quant_layers.py:77-80) — and the quantisers this call exercises are remembered for the checkpoint buffers."""
-        self.desc.flags = (self.desc.flags & ~_lib.FLAG_EVAL) | (0 if self.training else _lib.FLAG_EVAL)
+        """Before every kernel call on this model (autograd path and the direct-ABI train steps alike): the quantisers this call
+        exercises are remembered for the checkpoint buffers.  (The call's ODPD_FLAG_EVAL follows the module's mode by itself:
+        NativeBackbone.call_desc.)"""
         for name, m in self.named_modules():
             if isinstance(m, _QScale):
                 # only fc_out has out_quant set (quant_envs.py:278-287), and its output quantiser runs in eval mode only
@@ -315,8 +316,7 @@ class _QuantCell(_QuantBase):
     LAYERS = ()
 
     def _finish_cell(self, hidden_size, bits_w, bits_a, thx=0.0):
-        self._finish(hidden_size, bits_w, bits_a, thx=thx)
-        self.desc.flags |= _lib.FLAG_QUANT_CELL          # (sync_mode keeps every flag bit but ODPD_FLAG_EVAL)
+        self._finish(hidden_size, bits_w, bits_a, thx=thx, flags=_lib.FLAG_QUANT_CELL)
 
     def forward(self, x, h_0=None):
         """the out_quantizer scales are outside the graph (no module is named fc_out): they reach the kernel call detached, so their `grad`
@@ -324,7 +324,7 @@ class _QuantCell(_QuantBase):
         from .backbones.native import _BackboneFn
         self.sync_mode()
         params = [p.detach() if "out_quantizer" in n else p for n, p in self.named_parameters()]
-        return _BackboneFn.apply(x, self, torch.is_grad_enabled(), *params)
+        return _BackboneFn.apply(x, None, self, torch.is_grad_enabled(), *params)
 
     @classmethod
     def serves(cls, model, bits_w, bits_a, dev):

@@ -22,7 +22,13 @@ import torch
 from . import _lib
 from .models import CascadedModel, CoreModel
 from .project import Project, count_net_params
-from .train_funcs import FusedAdamW, _epoch_shape, _loss_kind, _sample_format
+from .train_funcs import FusedAdamW, _epoch_shape, _loss_kind, _sample_format, cascade_rows, rows_buffer
+
+
+def _call_desc(bb):
+    """the descriptor of a call on this backbone, asked for where it is used (NativeBackbone.call_desc: the module's mode as it stands
+    then); None for a backbone that runs through ATen"""
+    return bb.call_desc() if getattr(bb, "native", False) else None
 
 
 class _Rng:
@@ -121,8 +127,6 @@ class _Group:
         train = r0.loaders[0]
         self.T, self.n = train.frame_length, train.n
         self.B, self.n_steps, self.last = _epoch_shape(train)
-        bb = r0.net.backbone
-        self.desc = getattr(bb, "desc", None)
         fused = all(isinstance(r.opt, FusedAdamW) and r.opt.kind == "adamw" and r.opt.pa is None and r.opt.world_size() == 1
                     and getattr(r.net.backbone, "frozen_mask", None) is None for r in runs)
         kind = _loss_kind(r0.criterion)
@@ -138,6 +142,11 @@ class _Group:
         self._tuning_gen = None
         self._size_buffers()
 
+    @property
+    def desc(self):
+        """run 0's descriptor (the group key makes it the group's), asked for at each use"""
+        return _call_desc(self.runs[0].net.backbone)
+
     def _size_buffers(self):
         """partial rows / workspace / scratch of every run, sized for the CURRENT kernel-selection knobs (odpd_set_tuning: gp_max_batch,
         s16_occupancy, s16_min_batch .. change the grids the kernels write); re-done by train_epoch when odpd_tuning_generation has moved
@@ -151,7 +160,7 @@ class _Group:
             P = bb.n_flat
             for r in runs:
                 r.opt._ensure(self.dev)
-                r.partials = torch.empty(rows, P + _lib.LOSS_COLS, dtype=torch.float32, device=self.dev)
+                r.partials = rows_buffer(rows, P, self.dev)
                 r.workspace = torch.empty(ws, dtype=torch.float32, device=self.dev) if ws > 0 else None
             self.scratch = torch.empty(int(lib.odpd_sweep_scratch_bytes(len(runs), self.n_steps)), dtype=torch.uint8, device=self.dev)
 
@@ -413,25 +422,33 @@ class _DpdGroup:
                     and getattr(r.opt.backbone, "frozen_mask", None) is None for r in runs)
         self.eligible = bool(fused and self.kind is not None and len(runs) > 1 and hasattr(train, "epoch_order") and train.x.is_cuda
                              and train.x.dtype == torch.float32)
-        self.dpd_desc = getattr(getattr(r0.net.dpd_model, "backbone", None), "desc", None)
-        self.pa_desc = getattr(r0.net.pa_model.backbone, "desc", None)
         self.train_sweep = False
         self.scratch = None
         self._tuning_gen = None
         self._size_buffers()
+
+    # run 0's descriptors (the group key makes them the group's), asked for at each use
+    @property
+    def dpd_desc(self):
+        return _call_desc(getattr(self.runs[0].net.dpd_model, "backbone", None))
+
+    @property
+    def pa_desc(self):
+        """the frozen PA's, as run 0's optimiser launches with it (asked for in `eligible` groups only: those have a fused optimiser)"""
+        return self.runs[0].opt._pa_desc()
 
     def _size_buffers(self):
         """whether the cascade sweep launch serves the group, and the partial rows / scratch of every run, under the CURRENT kernel-selection
         knobs (odpd_set_tuning: cascade_one_launch, gp_max_batch ..); re-done by train_epoch when odpd_tuning_generation has moved"""
         lib = _lib.load()
         self._tuning_gen = int(lib.odpd_tuning_generation())
-        self.train_sweep = bool(self.eligible and self.dpd_desc is not None and self.pa_desc is not None and all(
+        self.train_sweep = bool(self.eligible and all(
             lib.odpd_sweep_cascade_supported(C.byref(self.dpd_desc), C.byref(self.pa_desc), b, self.T) == 1 for b in {self.B, self.last}))
         if self.train_sweep:
-            rows = max(int(lib.odpd_cascade_rows(C.byref(self.dpd_desc), C.byref(self.pa_desc), b, self.T)) for b in {self.B, self.last})
+            rows = max(cascade_rows(self.dpd_desc, self.pa_desc, b, self.T) for b in {self.B, self.last})
             for r in self.runs:
                 r.opt._ensure(self.dev)
-                r.partials = torch.empty(rows, r.opt.backbone.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=self.dev)
+                r.partials = rows_buffer(rows, r.opt.backbone.n_flat, self.dev)
             self.scratch = torch.empty(int(lib.odpd_sweep_cascade_scratch_bytes(len(self.runs), self.n_steps)), dtype=torch.uint8, device=self.dev)
 
     # ---- one training epoch of every run of the group ----

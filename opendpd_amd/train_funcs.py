@@ -65,6 +65,67 @@ def _skip_mask(bb):
     return frozen
 
 
+# ---- buffers sized by the library's queries.  `desc` is the descriptor of the call that will use the buffer (NativeBackbone.call_desc): the
+# query and the launch then resolve the same kernel route.  `sizes`: the batch sizes the ONE buffer serves (an epoch's full batches and tail).
+def partial_rows(desc, B, T, fused):
+    """odpd_partial_rows as the library answers it (<= 0: no such kernel for this shape, or an error code)"""
+    return int(_lib.load().odpd_partial_rows(C.byref(desc), B, T, fused))
+
+
+def cascade_rows(dpd_desc, pa_desc, B, T):
+    """odpd_cascade_rows as the library answers it (<= 0: the one-launch cascade step does not serve the pair / the shape)"""
+    return int(_lib.load().odpd_cascade_rows(C.byref(dpd_desc), C.byref(pa_desc), B, T))
+
+
+def rows_buffer(rows, P, device):
+    """partial-gradient rows of a model of P parameters (the loss partial sums ride in the extra columns)"""
+    return torch.empty(rows, P + _lib.LOSS_COLS, dtype=torch.float32, device=device)
+
+
+def partials_buffer(desc, sizes, T, fused, P, device):
+    """the rows buffer of the fused (1) or the split backward (0) kernel, large enough for every batch size of `sizes`"""
+    rows = [partial_rows(desc, b, T, fused) for b in sizes] or [1]      # (no size: a rank all of whose shards are empty)
+    _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
+    return rows_buffer(max(rows), P, device)
+
+
+def ckpt_buffer(desc, B, T, device):
+    """BPTT checkpoints of the split forward / backward pair (one float where the kernels keep none: the pointer stays valid)"""
+    n = int(_lib.load().odpd_ckpt_floats(C.byref(desc), B, T))
+    _lib.check(0 if n >= 0 else n, "odpd_ckpt_floats")
+    return torch.empty(max(n, 1), dtype=torch.float32, device=device)
+
+
+def workspace_floats(desc, B, T):
+    """odpd_train_workspace_floats as the library answers it (< 0: no fused kernel for this shape)"""
+    return int(_lib.load().odpd_train_workspace_floats(C.byref(desc), B, T))
+
+
+def workspace_buffer(desc, sizes, T, device):
+    """scratch of the fused kernel (HBM BPTT checkpoints of the large-batch path); None where none is needed"""
+    n = [workspace_floats(desc, b, T) for b in sizes] or [0]
+    _lib.check(0 if min(n) >= 0 else min(n), "odpd_train_workspace_floats")
+    return torch.empty(max(n), dtype=torch.float32, device=device) if max(n) > 0 else None
+
+
+def counts_in_workspace(bb):
+    """backbones with sparsity counters: the fused step's `workspace` argument carries the four counters of its forward pass (double[4]) where
+    the kernel needs no scratch — include/opendpd_hip.h, odpd_train_fwd_bwd"""
+    return bb.dx_needs_flag or getattr(bb, "fused_stats", False)
+
+
+def workspace_or_counters(bb, scratch, device):
+    """what goes into `workspace`: the scratch, or the counters (None while the module's statistics are switched off)"""
+    return bb._stats_buffer(device) if scratch is None and counts_in_workspace(bb) else scratch
+
+
+def mark_exercised(*backbones):
+    """quantised models: remember the quantisers the coming call exercises (quant.py: sync_mode), once per entry point"""
+    for bb in backbones:
+        if hasattr(bb, "sync_mode"):
+            bb.sync_mode()
+
+
 # project.py:274-297's other optimisers, with the hyper-parameters the reference builds them with: constants of the fused kernels
 _FIXED_HYPER = {"adam": dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0), "sgd": dict(momentum=0.9, weight_decay=0.0),
                 "rmsprop": dict(alpha=0.99, eps=1e-8, weight_decay=0.0)}
@@ -87,8 +148,6 @@ class FusedAdamW:
             trained, self.pa = net.dpd_model, net.pa_model.backbone
             if not isinstance(self.pa, NativeBackbone):
                 raise TypeError("FusedAdamW needs a HIP-backed PA model (this one runs through ATen)")
-            if self.pa.dx_needs_flag:       # a frozen delta PA is asked for dL/du in every step
-                self.pa.desc.flags |= _lib.FLAG_NEED_DX
         if not (isinstance(trained, CoreModel) and isinstance(trained.backbone, NativeBackbone)):
             raise TypeError("FusedAdamW needs a HIP-backed CoreModel (or a CascadedModel of two)")
         self.net = net
@@ -99,7 +158,7 @@ class FusedAdamW:
         self.step_count = 0
         self._state_dev = None
         self._tuning_gen = -1
-        self._fused_ok, self._partials, self._cascade_bufs = {}, {}, {}
+        self._cache = {}
 
     # -- state -------------------------------------------------------------------------------
     def _ensure(self, device):
@@ -113,108 +172,84 @@ class FusedAdamW:
         self.exp_avg = torch.zeros(P, dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(P, dtype=torch.float32, device=device)
         self.norm = torch.zeros(1, dtype=torch.float32, device=device)
-        self._partials = {}
-        self._cascade_bufs = {}
+        self._cache = {}
         self._state_dev = device
 
     def _check_tuning(self):
         gen = int(_lib.load().odpd_tuning_generation())
         if gen != self._tuning_gen:
-            self._partials, self._cascade_bufs, self._fused_ok = {}, {}, {}
+            self._cache = {}
             self._tuning_gen = gen
 
-    def _mode(self):
-        """Descriptor flags that take part in the kernel selection (quantised models: ODPD_FLAG_EVAL follows the module's mode)."""
-        if hasattr(self.backbone, "sync_mode"):
-            self.backbone.sync_mode()
-        return int(self.backbone.desc.flags) & _lib.FLAG_EVAL
+    def _desc(self):
+        """the trained model's descriptor for every query and launch here: this optimiser never asks it for dL/dx"""
+        return self.backbone.call_desc()
+
+    def _pa_desc(self):
+        """the frozen PA's: it is asked for dL/du in every step (ODPD_FLAG_NEED_DX on a delta PA)"""
+        return self.pa.call_desc(need_dx=True)
+
+    def _cached(self, key, make):
+        """The ONE cache of what the library's queries answered (dropped with the knobs' generation and the device, _ensure): every key
+        begins with the flags of the descriptor(s) the entry is made from, so no entry outlives the kernel selection it was sized for."""
+        if key not in self._cache:
+            self._cache[key] = make()
+        return self._cache[key]
 
     def partials(self, B, T, device):
         self._ensure(device)
-        key = (B, T, "fused", self._mode())
-        if key not in self._partials:
-            lib = _lib.load()
-            rows = int(lib.odpd_partial_rows(C.byref(self.backbone.desc), B, T, 1))
-            _lib.check(0 if rows > 0 else rows, "odpd_partial_rows")
-            self._partials[key] = torch.empty(rows, self.backbone.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=device)
-        return self._partials[key]
+        d = self._desc()
+        return self._cached((d.flags, B, T, "fused"), lambda: partials_buffer(d, (B,), T, 1, self.backbone.n_flat, device))
 
     def train_workspace(self, B, T, device):
-        """Scratch of the fused kernel (HBM BPTT checkpoints of the large-batch path; None when not needed)."""
+        """Scratch of the fused kernel (HBM BPTT checkpoints of the large-batch path; None when not needed), or the sparsity counters."""
         self._ensure(device)
-        key = (B, T, "ws", self._mode())
-        if key not in self._partials:
-            lib = _lib.load()
-            n = int(lib.odpd_train_workspace_floats(C.byref(self.backbone.desc), B, T))
-            _lib.check(0 if n >= 0 else n, "odpd_train_workspace_floats")
-            self._partials[key] = torch.empty(n, dtype=torch.float32, device=device) if n > 0 else None
-        if self._partials[key] is None and (self.backbone.dx_needs_flag or getattr(self.backbone, "fused_stats", False)):
-            # delta backbones: the fused step's `workspace` argument carries the four sparsity counters of its forward pass (double[4];
-            # None while the module's statistics are switched off) — include/opendpd_hip.h, odpd_train_fwd_bwd
-            return self.backbone._stats_buffer(device)
-        return self._partials[key]
+        d = self._desc()
+        return workspace_or_counters(self.backbone, self._cached((d.flags, B, T, "ws"), lambda: workspace_buffer(d, (B,), T, device)), device)
 
     def has_fused(self, B, T):
         """True when the backbone has a single-launch fwd+loss+bwd kernel for this batch shape."""
-        key = (B, T, "has_fused")
         self._check_tuning()
-        if self.backbone.dx_needs_flag:      # delta backbones: the trained model is never asked for dL/dx by this optimiser — a flag left behind by an
-            self.backbone.desc.flags &= ~_lib.FLAG_NEED_DX      # autograd call on the same module would route it to the dL/dx kernels
-        key = key + (self._mode(),)      # quantised models: the module's train / eval mode selects the kernel too (ODPD_FLAG_EVAL)
-        if key not in self._fused_ok:
-            lib = _lib.load()
-            self._fused_ok[key] = int(lib.odpd_partial_rows(C.byref(self.backbone.desc), B, T, 1)) > 0
-        return self._fused_ok[key]
+        d = self._desc()
+        return self._cached((d.flags, B, T, "has_fused"), lambda: partial_rows(d, B, T, 1) > 0)
 
     def bwd_partials(self, B, T, device):
         """Partial-gradient rows of the split backward kernel (cascade path)."""
         self._ensure(device)
-        key = (B, T, "bwd")
-        if key not in self._partials:
-            lib = _lib.load()
-            rows = int(lib.odpd_partial_rows(C.byref(self.backbone.desc), B, T, 0))
-            _lib.check(0 if rows > 0 else rows, "odpd_partial_rows")
-            self._partials[key] = torch.empty(rows, self.backbone.n_flat + _lib.LOSS_COLS, dtype=torch.float32,
-                                              device=device)
-        return self._partials[key]
+        d = self._desc()
+        return self._cached((d.flags, B, T, "bwd"), lambda: partials_buffer(d, (B,), T, 0, self.backbone.n_flat, device))
 
     def cascade_one_launch(self, B, T, device):
         """Partial-gradient rows of the one-launch cascade step (odpd_cascade_fwd_bwd: DPD wave + frozen-PA wave per frame), or None
-        where the pair of models / the batch shape is not served by it."""
+        where the pair of models / the batch shape is not served by it (e.g. a quantised DPD in eval())."""
         self._ensure(device)
-        key = (B, T, "casc", int(self.backbone.desc.flags))     # (a quantised DPD in eval() is not served by the one-launch step)
-        if key not in self._partials:
-            rows = -1
-            if self.pa is not None and self.pa.native and self.backbone.native:
-                rows = int(_lib.load().odpd_cascade_rows(C.byref(self.backbone.desc), C.byref(self.pa.desc), B, T))
-            self._partials[key] = (torch.empty(rows, self.backbone.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=device)
-                                   if rows > 0 else None)
-        return self._partials[key]
+        if self.pa is None:
+            return None
+        d, p = self._desc(), self._pa_desc()
+
+        def make():
+            rows = cascade_rows(d, p, B, T)
+            return rows_buffer(rows, self.backbone.n_flat, device) if rows > 0 else None
+        return self._cached((d.flags, p.flags, B, T, "casc"), make)
 
     def cascade_buffers(self, B, T, device):
-        """u = DPD(x), y = PA(u), dy, du, checkpoints, loss scratch — allocated once per batch shape."""
+        """u = DPD(x), y = PA(u), dy, du, checkpoints, loss scratch — allocated once per batch shape and kernel selection."""
         self._ensure(device)
-        if (B, T) not in self._cascade_bufs:
-            lib = _lib.load()
-            def ck(bb):
-                n = int(lib.odpd_ckpt_floats(C.byref(bb.desc), B, T))
-                _lib.check(0 if n >= 0 else n, "odpd_ckpt_floats")
-                return torch.empty(max(n, 1), dtype=torch.float32, device=device)
+        d, p = self._desc(), (self._pa_desc() if self.pa is not None else None)
+
+        def make():
             mk = lambda: torch.empty(B, T, 2, dtype=torch.float32, device=device)
-            d = dict(u=mk(), dy=mk(), ck_d=ck(self.backbone),
-                     loss=torch.zeros(_lib.LOSS_WS, dtype=torch.float32, device=device))
-            if self.pa is not None:
-                d.update(y=mk(), du=mk(), ck_p=ck(self.pa), pa_part=None, loss_rows=None)
-                rows = int(lib.odpd_frozen_loss_rows(C.byref(self.pa.desc), B, T))     # > 0: forward + loss + dL/du in one launch
+            buf = dict(u=mk(), dy=mk(), ck_d=ckpt_buffer(d, B, T, device), loss=torch.zeros(_lib.LOSS_WS, dtype=torch.float32, device=device))
+            if p is not None:
+                buf.update(y=mk(), du=mk(), ck_p=ckpt_buffer(p, B, T, device), pa_part=None, loss_rows=None)
+                rows = int(_lib.load().odpd_frozen_loss_rows(C.byref(p), B, T))     # > 0: forward + loss + dL/du in one launch
                 if rows > 0:
-                    d["loss_rows"] = torch.empty(rows, _lib.LOSS_COLS, dtype=torch.float32, device=device)
-                    d["loss4"] = torch.zeros(_lib.LOSS_COLS, dtype=torch.float32, device=device)
+                    buf["loss_rows"] = torch.empty(rows, _lib.LOSS_COLS, dtype=torch.float32, device=device)
+                    buf["loss4"] = torch.zeros(_lib.LOSS_COLS, dtype=torch.float32, device=device)
                 if self.pa.dx_needs_flag:   # the delta backward kernels write their weight gradients in every launch: scratch
-                    rows = int(lib.odpd_partial_rows(C.byref(self.pa.desc), B, T, 0))
-                    _lib.check(0 if rows > 0 else rows, "odpd_partial_rows")
-                    d["pa_part"] = torch.empty(rows, self.pa.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=device)
-            self._cascade_bufs[(B, T)] = d
-        return self._cascade_bufs[(B, T)]
+                    buf["pa_part"] = partials_buffer(p, (B,), T, 0, self.pa.n_flat, device)
+            return buf
+        return self._cached((d.flags, p and p.flags, B, T, "cascade"), make)
 
     def zero_grad(self, set_to_none=True):
         for p in self.net.parameters():
@@ -325,9 +360,11 @@ class FusedAdamW:
         counters it carries the counters when a batch runs on a one-frame-per-wave kernel (workspace floats = 0) and checkpoint scratch when
         it runs on a 16-sequences-per-wave kernel (> 0): an epoch whose full and tail batches fall on different sides cannot be served by one
         pointer — the tail's counters would land in the scratch — and goes through the per-step path instead."""
-        if not (self.backbone.dx_needs_flag or getattr(self.backbone, "fused_stats", False)):
+        if not counts_in_workspace(self.backbone):
             return True
-        ws = [int(_lib.load().odpd_train_workspace_floats(C.byref(self.backbone.desc), b, T)) for b in sizes]
+        self._check_tuning()
+        d = self._desc()
+        ws = self._cached((d.flags, tuple(sorted(sizes)), T, "ws-floats"), lambda: [workspace_floats(d, b, T) for b in sizes])
         return not (any(w > 0 for w in ws) and any(w == 0 for w in ws))
 
     @staticmethod
@@ -339,18 +376,18 @@ class FusedAdamW:
     def reads_frames(self, B, T):
         """True when the backbone's fused kernel for this batch shape addresses frames inside resident streams
         (odpd_framed_train_supported_shape)."""
-        return bool(_lib.load().odpd_framed_train_supported_shape(C.byref(self.backbone.desc), B, T))
+        return bool(_lib.load().odpd_framed_train_supported_shape(C.byref(self._desc()), B, T))
 
     def reads_bf16_frames(self):
         """bf16 sample storage is read in place by the float GRU family's fused train kernels only"""
-        return self.pa is None and self.backbone.backbone_name in ("gru", "dgru", "qgru", "qgru_amp1") and self.backbone.desc.bits_w == 0
+        return self.pa is None and self.backbone.backbone_name in ("gru", "dgru", "qgru", "qgru_amp1") and self._desc().bits_w == 0
 
     def can_run_split_epoch(self, loader):
         """True when odpd_train_epoch_split can drive a whole epoch: a single backbone WITHOUT a frame-reading fused kernel for the
         epoch's batch shapes, one process, resident streams (the forward / loss / backward / reduce / optimiser chain per step then
         runs from C++ instead of from Python)."""
         return (self.pa is None and self.world_size() == 1 and not self.can_run_epoch(loader) and _resident(loader)
-                and loader.x.dtype == torch.float32 and hasattr(self.backbone, "desc"))
+                and loader.x.dtype == torch.float32)
 
     @contextlib.contextmanager
     def _epoch(self, loader):
@@ -374,20 +411,14 @@ class FusedAdamW:
         bb = self.backbone
         with self._epoch(loader) as e:
             B, T, dev = e.B, e.T, e.dev
-            if bb.dx_needs_flag:               # as _cascade_train_step: the trained model is never asked for dL/dx here
-                bb.desc.flags &= ~_lib.FLAG_NEED_DX
-            if hasattr(bb, "sync_mode"):
-                bb.sync_mode()
-            key = (B, T, e.last, "split-epoch")
-            if key not in self._partials:
-                rows = [int(lib.odpd_partial_rows(C.byref(bb.desc), b, T, 0)) for b in {B, e.last}]
-                _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
-                mk = lambda: torch.empty(B, T, 2, dtype=torch.float32, device=dev)
-                self._partials[key] = (torch.empty(max(rows), bb.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev), mk(), mk())
-            part, xbuf, tbuf = self._partials[key]
+            mark_exercised(bb)
+            d = self._desc()
+            mk = lambda: torch.empty(B, T, 2, dtype=torch.float32, device=dev)
+            part, xbuf, tbuf = self._cached((d.flags, B, T, e.last, "split-epoch"),
+                                            lambda: (partials_buffer(d, {B, e.last}, T, 0, bb.n_flat, dev), mk(), mk()))
             buf = self.cascade_buffers(B, T, dev)
             flat = bb.flat_params(full_check=True)
-            rc = lib.odpd_train_epoch_split(_lib.stream_ptr(), C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], e.fr, B, hyper[0], _lib.ptr(flat),
+            rc = lib.odpd_train_epoch_split(_lib.stream_ptr(), C.byref(d), _lib.LOSS_IDS[loss_kind], e.fr, B, hyper[0], _lib.ptr(flat),
                                             _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), e.first_step, *hyper[1:],
                                             float(max_norm or 0.0), _lib.ptr(_skip_mask(bb)), _lib.ptr(xbuf), _lib.ptr(tbuf), _lib.ptr(buf["u"]),
                                             _lib.ptr(buf["dy"]), _lib.ptr(buf["ck_d"]), _lib.ptr(part), _lib.ptr(buf["loss"]),
@@ -400,9 +431,6 @@ class FusedAdamW:
         served by the one-launch cascade step, one process, resident streams."""
         if not (self.pa is not None and _resident(loader) and loader.x.dtype == torch.float32):
             return False
-        for bb in (self.backbone, self.pa):       # quantised models: the descriptor's ODPD_FLAG_EVAL must say what the module says NOW
-            if hasattr(bb, "sync_mode"):          # (an evaluation pass leaves it set; the one-launch step serves train mode only)
-                bb.sync_mode()
         dev = loader.x.device
         if self.world_size() > 1 or self.native_comm() is not None:
             # sharded epoch from C++: needs the library-owned RCCL communicator and the one-launch step for this rank's shards
@@ -421,13 +449,11 @@ class FusedAdamW:
             if sizes:
                 part = max((self.cascade_one_launch(b, e.T, e.dev) for b in sizes), key=lambda p: p.shape[0])
             else:       # a rank all of whose shards are empty (global batch smaller than the world): it still joins every all-reduce
-                part = torch.empty(1, dpd.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=e.dev)
+                part = rows_buffer(1, dpd.n_flat, e.dev)
             flat, pa_flat = dpd.flat_params(full_check=True), pa.flat_params(full_check=True)
             frozen = _skip_mask(dpd)      # (the QAT models' 16-bit output scales)
-            for bb in (dpd, pa):       # quantised models: train / eval mode of the module -> ODPD_FLAG_EVAL
-                if hasattr(bb, "sync_mode"):
-                    bb.sync_mode()
-            rc = lib.odpd_train_epoch_cascade(_lib.stream_ptr(), comm.handle if comm is not None else None, C.byref(dpd.desc), C.byref(pa.desc),
+            mark_exercised(dpd, pa)
+            rc = lib.odpd_train_epoch_cascade(_lib.stream_ptr(), comm.handle if comm is not None else None, C.byref(self._desc()), C.byref(self._pa_desc()),
                                               _lib.LOSS_IDS[loss_kind], e.fr, e.B, hyper[0], _lib.ptr(flat), _lib.ptr(pa_flat), _lib.ptr(self.grad),
                                               _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), e.first_step, *hyper[1:], float(max_norm or 0.0),
                                               _lib.ptr(frozen), _lib.ptr(part), _lib.ptr(dpd._stats_buffer(e.dev)), _lib.ptr(e.losses))
@@ -443,18 +469,15 @@ class FusedAdamW:
         comm = self.native_comm()
         with self._epoch(loader) as e:
             B, T, dev = e.B, e.T, e.dev
-            key = (B, T, e.last, "epoch", comm is not None, self._mode())
-            if key not in self._partials:
+            mark_exercised(bb)
+            d = self._desc()
+
+            def make():
                 sizes = self._shard_sizes(loader) if comm is not None else {B, e.last}
-                rows = [int(lib.odpd_partial_rows(C.byref(bb.desc), b, T, 1)) for b in sizes] or [1]
-                _lib.check(0 if min(rows) > 0 else min(rows), "odpd_partial_rows")
-                ws = max([int(lib.odpd_train_workspace_floats(C.byref(bb.desc), b, T)) for b in sizes] or [0])
-                self._partials[key] = (torch.empty(max(rows), bb.n_flat + _lib.LOSS_COLS, dtype=torch.float32, device=dev),
-                                       torch.empty(ws, dtype=torch.float32, device=dev) if ws > 0 else None)
-            part, ws = self._partials[key]
-            if ws is None and (bb.dx_needs_flag or getattr(bb, "fused_stats", False)):      # delta backbones: `workspace` = the sparsity counters (see train_workspace)
-                ws = bb._stats_buffer(dev)
-            head = (C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], e.fr, B)
+                return partials_buffer(d, sizes, T, 1, bb.n_flat, dev), workspace_buffer(d, sizes, T, dev)
+            part, ws = self._cached((d.flags, B, T, e.last, "epoch", comm is not None), make)
+            ws = workspace_or_counters(bb, ws, dev)
+            head = (C.byref(d), _lib.LOSS_IDS[loss_kind], e.fr, B)
             state = (_lib.ptr(bb.flat_params(full_check=True)), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), e.first_step)
             tail = (float(max_norm or 0.0), _lib.ptr(part), _lib.ptr(ws), _lib.ptr(e.losses))
             if comm is not None:
@@ -530,19 +553,19 @@ def fused_train_step(opt, x, target, loss_kind="l2", grad_clip_val=0.0, global_c
                            "(GRU family, gmp, rvtdcnn; lstm / vdlstm / pgjanet at the reference's batch sizes)")
     if opt.pa is not None or not opt.has_fused(B, T):
         return _cascade_train_step(opt, x, target, loss_kind, grad_clip_val, count, timing if isinstance(timing, list) else None)
+    mark_exercised(bb)
     part = opt.partials(B, T, x.device)
     ws = opt.train_workspace(B, T, x.device)
     flat = bb.flat_params()
     st = _lib.stream_ptr()
-    if hasattr(bb, "sync_mode"):      # quantised models: train / eval mode of the module -> ODPD_FLAG_EVAL
-        bb.sync_mode()
+    d = opt._desc()
     if timing is not None and not isinstance(timing, list):
         timing[0].record()
     if framed:
-        rc = lib.odpd_train_fwd_bwd_framed(st, C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], C.byref(x.desc), 0, B, count,
+        rc = lib.odpd_train_fwd_bwd_framed(st, C.byref(d), _lib.LOSS_IDS[loss_kind], C.byref(x.desc), 0, B, count,
                                            _lib.ptr(flat), _lib.ptr(part), _lib.ptr(ws))
     else:
-        rc = lib.odpd_train_fwd_bwd(st, C.byref(bb.desc), _lib.LOSS_IDS[loss_kind], B, T, count,
+        rc = lib.odpd_train_fwd_bwd(st, C.byref(d), _lib.LOSS_IDS[loss_kind], B, T, count,
                                     _lib.ptr(flat), _lib.ptr(x), _lib.ptr(target), _lib.ptr(part), _lib.ptr(ws))
     if timing is not None and not isinstance(timing, list):
         timing[1].record()
@@ -563,15 +586,9 @@ def _cascade_train_step(opt, x, target, loss_kind, grad_clip_val, count, timing=
     lib = _lib.load()
     dpd, pa = opt.backbone, opt.pa
     B, T = x.shape[0], x.shape[1]
-    # delta backbones: buffers and kernels are selected through the descriptor — pin the selection against a flag left behind
-    # by an autograd call on the same module (the trained model is never asked for dL/dx here, a frozen delta PA always is)
-    if dpd.dx_needs_flag:
-        dpd.desc.flags &= ~_lib.FLAG_NEED_DX
-    if pa is not None and pa.dx_needs_flag:
-        pa.desc.flags |= _lib.FLAG_NEED_DX
-    for bb in (dpd, pa):       # quantised models: train / eval mode of the module -> ODPD_FLAG_EVAL (an evaluation pass may have left it set)
-        if hasattr(bb, "sync_mode"):
-            bb.sync_mode()
+    mark_exercised(dpd, pa)
+    # the descriptors the optimiser sized its buffers by (the trained model is never asked for dL/dx here, a frozen delta PA always is)
+    dd, pd = C.byref(opt._desc()), (C.byref(opt._pa_desc()) if pa is not None else None)
     st = _lib.stream_ptr()
     fd, fp = dpd.flat_params(), (pa.flat_params() if pa is not None else None)
 
@@ -590,7 +607,7 @@ def _cascade_train_step(opt, x, target, loss_kind, grad_clip_val, count, timing=
     if one is not None:
         # the reference's own batch sizes, GRU-family DPD and PA: the whole step body as one launch (csrc/gru_cascade.hip)
         mark("cascade_fwd_loss_bwd")
-        _lib.check(lib.odpd_cascade_fwd_bwd(st, C.byref(dpd.desc), C.byref(pa.desc), _lib.LOSS_IDS[loss_kind], B, T, count, _lib.ptr(fd),
+        _lib.check(lib.odpd_cascade_fwd_bwd(st, dd, pd, _lib.LOSS_IDS[loss_kind], B, T, count, _lib.ptr(fd),
                                             _lib.ptr(fp), _lib.ptr(x), _lib.ptr(target), None, 0, _lib.ptr(one), _lib.ptr(dpd._stats_buffer(x.device))),
                    "cascade fwd + loss + bwd")
         mark("reduce_clip_optimiser")
@@ -603,13 +620,13 @@ def _cascade_train_step(opt, x, target, loss_kind, grad_clip_val, count, timing=
     buf = opt.cascade_buffers(B, T, x.device)
     part = opt.bwd_partials(B, T, x.device)
     mark("dpd_fwd")
-    _lib.check(lib.odpd_backbone_fwd(st, C.byref(dpd.desc), B, T, _lib.ptr(fd), _lib.ptr(x), _lib.ptr(buf["u"]),
+    _lib.check(lib.odpd_backbone_fwd(st, dd, B, T, _lib.ptr(fd), _lib.ptr(x), _lib.ptr(buf["u"]),
                                      _lib.ptr(buf["ck_d"]), _lib.ptr(dpd._stats_buffer(x.device))), "dpd fwd")
     mark("pa_fwd_loss_dx" if pa is not None else "loss")
     loss_sum = None
     if pa is not None and buf["loss_rows"] is not None:
         # frozen PA in front of the loss: forward, loss and dL/du in one launch (16-sequences-per-wave GRU-family kernels)
-        _lib.check(lib.odpd_frozen_loss_dx(st, C.byref(pa.desc), _lib.LOSS_IDS[loss_kind], B, T, count, _lib.ptr(fp),
+        _lib.check(lib.odpd_frozen_loss_dx(st, pd, _lib.LOSS_IDS[loss_kind], B, T, count, _lib.ptr(fp),
                                            _lib.ptr(buf["u"]), _lib.ptr(target), _lib.ptr(buf["du"]), _lib.ptr(buf["loss_rows"]),
                                            _lib.ptr(buf["ck_p"])), "pa fwd + loss + dL/du")
         _lib.check(lib.odpd_reduce_partials(st, buf["loss_rows"].shape[0], 0, _lib.ptr(buf["loss_rows"]), _lib.ptr(buf["loss4"]), 0),
@@ -617,18 +634,18 @@ def _cascade_train_step(opt, x, target, loss_kind, grad_clip_val, count, timing=
         loss_sum, du = buf["loss4"][0], buf["du"]
     else:
         if pa is not None:
-            _lib.check(lib.odpd_backbone_fwd(st, C.byref(pa.desc), B, T, _lib.ptr(fp), _lib.ptr(buf["u"]), _lib.ptr(buf["y"]),
+            _lib.check(lib.odpd_backbone_fwd(st, pd, B, T, _lib.ptr(fp), _lib.ptr(buf["u"]), _lib.ptr(buf["y"]),
                                              _lib.ptr(buf["ck_p"]), _lib.ptr(pa._stats_buffer(x.device))), "pa fwd")
         y = buf["y"] if pa is not None else buf["u"]
         _lib.check(lib.odpd_loss_fwd_bwd(st, _lib.LOSS_IDS[loss_kind], B * T * 2, count, _lib.ptr(y), _lib.ptr(target),
                                          _lib.ptr(buf["dy"]), _lib.ptr(buf["loss"])), "loss")
         du = buf["dy"]
         if pa is not None:
-            _lib.check(lib.odpd_backbone_bwd(st, C.byref(pa.desc), B, T, _lib.ptr(fp), _lib.ptr(buf["u"]), _lib.ptr(buf["dy"]),
+            _lib.check(lib.odpd_backbone_bwd(st, pd, B, T, _lib.ptr(fp), _lib.ptr(buf["u"]), _lib.ptr(buf["dy"]),
                                              _lib.ptr(buf["ck_p"]), _lib.ptr(buf["pa_part"]), _lib.ptr(buf["du"])), "pa bwd")
             du = buf["du"]
     mark("dpd_bwd")
-    _lib.check(lib.odpd_backbone_bwd(st, C.byref(dpd.desc), B, T, _lib.ptr(fd), _lib.ptr(x), _lib.ptr(du),
+    _lib.check(lib.odpd_backbone_bwd(st, dd, B, T, _lib.ptr(fd), _lib.ptr(x), _lib.ptr(du),
                                      _lib.ptr(buf["ck_d"]), _lib.ptr(part), None), "dpd bwd")
     mark("reduce_clip_optimiser")
     _lib.check(lib.odpd_reduce_partials(st, part.shape[0], dpd.n_flat, _lib.ptr(part), _lib.ptr(opt.grad), 0), "reduce")

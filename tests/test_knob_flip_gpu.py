@@ -182,8 +182,9 @@ def test_qat_u3_flip_between_forward_and_backward(lib, bb, H, B, T):
 
 
 def test_refused_delta_backward_leaves_no_dx_flag_behind(lib):
-    """delta backbones with x.requires_grad route the forward through ODPD_FLAG_NEED_DX (the descriptor carries it until the backward ends):
-    a refused backward clears it as a completed one does, and the next weight-only step takes the kernels a fresh module would"""
+    """delta backbones with x.requires_grad route the forward through ODPD_FLAG_NEED_DX, carried by the descriptor of that one call
+    (NativeBackbone.call_desc) and never by the module's own: it is absent there between forward and backward and after a refused backward,
+    and the next weight-only step takes the kernels a fresh module would"""
     from opendpd_amd import _lib
     bb, H, thx, thh, B, T = "deltagru", 15, 0.01, 0.05, 19, 65
     net, x, dy = _net(bb, H, thx, thh, B, T)
@@ -191,7 +192,7 @@ def test_refused_delta_backward_leaves_no_dx_flag_behind(lib):
     _set(lib, "s16_min_batch", NEVER)
     xt = torch.from_numpy(x).cuda().requires_grad_(True)
     y = net(xt)
-    assert net.backbone.desc.flags & _lib.FLAG_NEED_DX
+    assert not net.backbone.desc.flags & _lib.FLAG_NEED_DX
     _set(lib, "s16_min_batch", 0)
     with pytest.raises(RuntimeError, match=REFUSED):
         y.backward(torch.from_numpy(dy).cuda())
