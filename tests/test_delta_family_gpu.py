@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import Fixture, rel_err
+from tests.golden_util import Fixture, assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 2e-5, 3e-4
@@ -48,15 +48,17 @@ def test_golden_forward_backward_and_counters(name, bb):
     assert abs(sp["SP_T_DH"] - fx["stats_a"][2] / fx["stats_a"][3]) < 1e-12 and "HW_PARAM" in sp
 
 
-@pytest.mark.parametrize("bb,H,thx,thh", [("deltagru", 15, 0.0, 0.0), ("deltagru", 15, 0.01, 0.05), ("deltagru", 8, 0.02, 0.1),
-                                          ("deltagru_tcnskip", 15, 0.01, 0.05), ("deltagru_tcnskip", 16, 0.0, 0.0),
-                                          ("deltagru_tcnskip", 9, 0.05, 0.02)])
-@pytest.mark.parametrize("B,T", [(1, 1), (3, 5), (4, 32), (7, 33), (5, 200), (66, 63)])
-def test_against_oracle_ragged(bb, H, thx, thh, B, T):
+RAGGED_MODELS = [("deltagru", 15, 0.0, 0.0), ("deltagru", 15, 0.01, 0.05), ("deltagru", 8, 0.02, 0.1),
+                 ("deltagru_tcnskip", 15, 0.01, 0.05), ("deltagru_tcnskip", 16, 0.0, 0.0), ("deltagru_tcnskip", 9, 0.05, 0.02)]
+RAGGED_SHAPES = [(1, 1), (3, 5), (4, 32), (7, 33), (5, 200), (66, 63)]
+
+
+def ragged_case(bb, H, thx, thh, B, T, device="cuda"):
+    """model, input and output gradient of test_against_oracle_ragged (tests/test_grad_blocks_cpu.py holds the fp32 oracle to the
+    fp64 one on the same cases, `device` "cpu")"""
     from opendpd_amd import CoreModel
-    from oracle.oracle import Oracle, make_model
     torch.manual_seed(H * 100 + B + T)
-    net = CoreModel(2, H, 1, bb, thx=thx, thh=thh).cuda()
+    net = CoreModel(2, H, 1, bb, thx=thx, thh=thh).to(device)
     with torch.no_grad():
         for k, p in net.named_parameters():
             if "bias" in k:
@@ -66,6 +68,14 @@ def test_against_oracle_ragged(bb, H, thx, thh, B, T):
     ph = 2 * np.pi * rng.rand(B, T, 1)
     x = np.concatenate([amp * np.cos(ph), amp * np.sin(ph)], -1).astype(np.float32)
     dy = rng.randn(B, T, 2).astype(np.float32)
+    return net, x, dy
+
+
+@pytest.mark.parametrize("bb,H,thx,thh", RAGGED_MODELS)
+@pytest.mark.parametrize("B,T", RAGGED_SHAPES)
+def test_against_oracle_ragged(bb, H, thx, thh, B, T):
+    from oracle.oracle import Oracle, make_model
+    net, x, dy = ragged_case(bb, H, thx, thh, B, T)
     net.backbone.set_debug(1)
     y = net(torch.from_numpy(x).cuda())
     y.backward(torch.from_numpy(dy).cuda())
@@ -82,7 +92,7 @@ def test_against_oracle_ragged(bb, H, thx, thh, B, T):
     exact = st["num_dx_zeros"] == so[0] and st["num_dh_zeros"] == so[2]
     tol_f, tol_g = (FWD_TOL, GRAD_TOL) if exact else (5e-3, 5e-2)
     assert rel_err(y.detach().cpu().numpy(), yo) < tol_f
-    assert rel_err(g, go) < tol_g
+    assert_grad_blocks(g, go, net_grad_blocks(net), tol_g)
 
 
 @pytest.mark.parametrize("name,bb", [("deltagru_h15_th", "deltagru"), ("tres_h15_th", "deltagru_tcnskip"),
@@ -139,7 +149,7 @@ def test_dx_against_oracle(bb, H, thx, thh, B, T):
     exact = st["num_dx_zeros"] == so[0] and st["num_dh_zeros"] == so[2]
     tol_f, tol_g = (FWD_TOL, GRAD_TOL) if exact else (5e-3, 5e-2)
     assert rel_err(y.detach().cpu().numpy(), yo) < tol_f
-    assert rel_err(g, go) < tol_g
+    assert_grad_blocks(g, go, net_grad_blocks(net), tol_g)
     assert rel_err(xt.grad.cpu().numpy(), dxo) < tol_g
     # frozen model: dL/dx alone
     for q in net.parameters():

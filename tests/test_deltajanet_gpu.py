@@ -5,18 +5,18 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import Fixture, rel_err
+from tests.golden_util import Fixture, assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 2e-5, 3e-4
 
 
-def _net(H, fx=None, prefix="sd", **kw):
+def _net(H, fx=None, prefix="sd", device="cuda", **kw):
     from opendpd_amd import CoreModel
     net = CoreModel(2, H, 1, "deltajanet", **kw)
     if fx is not None:
         net.load_state_dict({k: torch.from_numpy(fx[f"{prefix}/" + k]) for k in fx.keys(prefix)})
-    return net.cuda()
+    return net.to(device)
 
 
 @pytest.mark.parametrize("name", ["deltajanet_h15", "deltajanet_h22"])
@@ -59,12 +59,15 @@ def test_second_reference_vector():
     assert rel_err(x.grad.cpu().numpy(), fx["gx"]) < GRAD_TOL
 
 
-@pytest.mark.parametrize("H", [1, 7, 15, 16, 17, 22, 32])
-@pytest.mark.parametrize("B,T", [(1, 1), (3, 5), (17, 32), (7, 33), (5, 200), (66, 63)])
-def test_against_oracle_ragged(H, B, T):
-    from oracle.oracle import Oracle, make_model
+RAGGED_HIDDEN = [1, 7, 15, 16, 17, 22, 32]
+RAGGED_SHAPES = [(1, 1), (3, 5), (17, 32), (7, 33), (5, 200), (66, 63)]
+
+
+def ragged_case(H, B, T, device="cuda"):
+    """model, input and output gradient of test_against_oracle_ragged (tests/test_grad_blocks_cpu.py holds the fp32 oracle to the
+    fp64 one on the same cases, `device` "cpu")"""
     torch.manual_seed(H * 100 + B + T)
-    net = _net(H)
+    net = _net(H, device=device)
     with torch.no_grad():
         for k, p in net.named_parameters():
             if "bias" in k:
@@ -74,11 +77,20 @@ def test_against_oracle_ragged(H, B, T):
     ph = 2 * np.pi * rng.rand(B, T, 1)
     x = np.concatenate([amp * np.cos(ph), amp * np.sin(ph)], -1).astype(np.float32)
     dy = rng.randn(B, T, 2).astype(np.float32)
+    return net, x, dy
+
+
+@pytest.mark.parametrize("H", RAGGED_HIDDEN)
+@pytest.mark.parametrize("B,T", RAGGED_SHAPES)
+def test_against_oracle_ragged(H, B, T):
+    from oracle.oracle import Oracle, make_model
+    net, x, dy = ragged_case(H, B, T)
     o = Oracle("f32")
     m = make_model("deltajanet", H)
     p = np.concatenate([q.detach().cpu().numpy().reshape(-1) for q in net.parameters()])
     yo, so = o.forward(m, p, x)
     go, dxo = o.backward(m, p, x, dy)
+    blocks = net_grad_blocks(net)
     # weight gradients alone, then with dL/dx, then dL/dx of the frozen model
     net.backbone.set_debug(1)
     y = net(torch.from_numpy(x).cuda())
@@ -87,13 +99,13 @@ def test_against_oracle_ragged(H, B, T):
     st = net.backbone.statistics
     assert st["num_dx_zeros"] == so[0] and st["num_dh_zeros"] == so[2] and st["num_dx_numel"] == so[1] and st["num_dh_numel"] == so[3]
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(g, go) < GRAD_TOL
+    assert_grad_blocks(g, go, blocks, GRAD_TOL)
     for q in net.parameters():
         q.grad = None
     xt = torch.from_numpy(x).cuda().requires_grad_(True)
     net(xt).backward(torch.from_numpy(dy).cuda())
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(g, go) < GRAD_TOL
+    assert_grad_blocks(g, go, blocks, GRAD_TOL)
     assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
     for q in net.parameters():
         q.requires_grad_(False)

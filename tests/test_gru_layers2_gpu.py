@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import Fixture, rel_err
+from tests.golden_util import Fixture, assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -146,4 +146,4 @@ def test_two_layer_dpd_in_train_dpd_takes_the_chained_launches(dpd_bb, H):
     assert abs(lg.item() - loss_ref.item()) < 2e-5 * max(1.0, loss_ref.item())
     got = opt.grad[:-4].cpu().numpy()
     want = np.concatenate([p.grad.detach().cpu().numpy().reshape(-1) for p in ref_dpd.parameters()])
-    assert rel_err(got, want) < 3e-4
+    assert_grad_blocks(got, want, net_grad_blocks(dpd), 3e-4)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import rel_err
+from tests.golden_util import assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 2e-5, 2e-4
@@ -23,12 +23,12 @@ def _data(B, T, seed):
     return np.concatenate([amp * np.cos(ph), amp * np.sin(ph)], -1).astype(np.float32), rng.randn(B, T, 2).astype(np.float32)
 
 
-def _net(bb, H, seed):
+def _net(bb, H, seed, device="cuda"):
     from opendpd_amd import CoreModel
     torch.manual_seed(seed)
     with warnings.catch_warnings():
         warnings.simplefilter("error")          # no "outside the HIP kernels' envelope" warning: these sizes are kernel-backed now
-        net = CoreModel(2, H, 1, bb).cuda()
+        net = CoreModel(2, H, 1, bb).to(device)
     assert net.backbone.native
     with torch.no_grad():      # biases are zero after init: make them count
         for k, p in net.named_parameters():
@@ -37,15 +37,25 @@ def _net(bb, H, seed):
     return net
 
 
-@pytest.mark.parametrize("bb,H", [("gru", 33), ("gru", 48), ("gru", 64), ("dgru", 40), ("dgru", 64), ("dgru", 33), ("qgru", 36), ("qgru_amp1", 50),
-                                  ("lstm", 33), ("lstm", 47), ("lstm", 64), ("vdlstm", 33), ("vdlstm", 50), ("vdlstm", 64)])
-@pytest.mark.parametrize("B,T", [(1, 1), (3, 5), (4, 64), (5, 70), (2, 200), (70, 33)])
-def test_against_oracle_ragged(bb, H, B, T):
-    from oracle.oracle import Oracle, make_model
+RAGGED_MODELS = [("gru", 33), ("gru", 48), ("gru", 64), ("dgru", 40), ("dgru", 64), ("dgru", 33), ("qgru", 36), ("qgru_amp1", 50),
+                 ("lstm", 33), ("lstm", 47), ("lstm", 64), ("vdlstm", 33), ("vdlstm", 50), ("vdlstm", 64)]
+RAGGED_SHAPES = [(1, 1), (3, 5), (4, 64), (5, 70), (2, 200), (70, 33)]
+
+
+def ragged_case(bb, H, B, T, device="cuda"):
+    """model, input and output gradient of test_against_oracle_ragged (tests/test_grad_blocks_cpu.py holds the fp32 oracle to the
+    fp64 one on the same cases, `device` "cpu")"""
     if bb == "vdlstm":
         T = max(T, 3)      # the circular pad takes the frame's own last three samples (vdlstm.py:66-74)
-    net = _net(bb, H, H * 1000 + B * 10 + T)
-    x, dy = _data(B, T, B * 7 + T)
+    return (_net(bb, H, H * 1000 + B * 10 + T, device), *_data(B, T, B * 7 + T))
+
+
+@pytest.mark.parametrize("bb,H", RAGGED_MODELS)
+@pytest.mark.parametrize("B,T", RAGGED_SHAPES)
+def test_against_oracle_ragged(bb, H, B, T):
+    from oracle.oracle import Oracle, make_model
+    net, x, dy = ragged_case(bb, H, B, T)
+    blocks = net_grad_blocks(net)
     o = Oracle("f32")
     m = make_model(bb, H)
     p = np.concatenate([q.detach().cpu().numpy().reshape(-1) for q in net.parameters()])
@@ -59,18 +69,14 @@ def test_against_oracle_ragged(bb, H, B, T):
     y.backward(torch.from_numpy(dy).cuda())
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
     assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL
-    off = 0
-    for k, q in net.named_parameters():                     # every parameter tensor on its own scale
-        n = q.numel()
-        assert rel_err(g[off:off + n], go[off:off + n]) < GRAD_TOL, k
-        off += n
+    assert_grad_blocks(g, go, blocks, GRAD_TOL, exact_zeros=True)      # every parameter tensor, and every gate of the cell's, on its own scale
     assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
     # weights alone (the trained model of a train_pa step) and dL/dx alone (the frozen PA of a cascade)
     for q in net.parameters():
         q.grad = None
     net(torch.from_numpy(x).cuda()).backward(torch.from_numpy(dy).cuda())
     g2 = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(g2, go) < GRAD_TOL
+    assert_grad_blocks(g2, go, blocks, GRAD_TOL)
     for q in net.parameters():
         q.requires_grad_(False)
     xt2 = torch.from_numpy(x).cuda().requires_grad_(True)
@@ -94,7 +100,8 @@ def test_more_sequences_than_workgroups(bb, H):
     y = net(xt)
     y.backward(torch.from_numpy(dy).cuda())
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL and rel_err(g, go) < GRAD_TOL and rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
+    assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL and rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
+    assert_grad_blocks(g, go, net_grad_blocks(net), GRAD_TOL)
 
 
 @pytest.mark.parametrize("bb,H", [("gru", 40), ("dgru", 64), ("lstm", 50), ("vdlstm", 40)])
@@ -268,7 +275,7 @@ def test_delta_backbones_against_oracle(bb, H, thx, thh, B, T):
     flips = np.abs(got - st).max()
     tol_y, tol_g = (FWD_TOL, GRAD_TOL) if flips == 0 else (5e-2, 5e-1)
     assert rel_err(y.detach().cpu().numpy(), yo) < tol_y
-    assert rel_err(g, go) < tol_g
+    assert_grad_blocks(g, go, net_grad_blocks(net), tol_g)
     assert rel_err(xt.grad.cpu().numpy(), dxo) < tol_g
 
 
@@ -311,17 +318,14 @@ def test_pgjanet_17_to_32_units_against_oracle(H, B, T):
     y = net(xt)
     y.backward(torch.from_numpy(dy).cuda())
     assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL
-    off = 0
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    for k, q in net.named_parameters():
-        n = q.numel()
-        assert rel_err(g[off:off + n], go[off:off + n]) < GRAD_TOL, k
-        off += n
+    blocks = net_grad_blocks(net)
+    assert_grad_blocks(g, go, blocks, GRAD_TOL, exact_zeros=True)
     assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
     for q in net.parameters():
         q.grad = None
     net(torch.from_numpy(x).cuda()).backward(torch.from_numpy(dy).cuda())
-    assert rel_err(np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()]), go) < GRAD_TOL
+    assert_grad_blocks(np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()]), go, blocks, GRAD_TOL)
     for q in net.parameters():
         q.requires_grad_(False)
     xt2 = torch.from_numpy(x).cuda().requires_grad_(True)
@@ -360,7 +364,8 @@ def test_deltajanet_33_to_64_units_against_oracle(H, B, T):
     assert np.array_equal(np.array([s["num_dx_zeros"], s["num_dx_numel"], s["num_dh_zeros"], s["num_dh_numel"]]), st)
     y.backward(torch.from_numpy(dy).cuda())
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL and rel_err(g, go) < GRAD_TOL and rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
+    assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL and rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
+    assert_grad_blocks(g, go, net_grad_blocks(net), GRAD_TOL)
     for q in net.parameters():
         q.requires_grad_(False)
     xt2 = torch.from_numpy(x).cuda().requires_grad_(True)

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import rel_err
+from tests.golden_util import assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -105,7 +105,7 @@ def _against_the_oracle(bb, H, thx, thh, net, x, dy, out):
         if not (st["num_dx_zeros"] == so[0] and st["num_dh_zeros"] == so[2]):
             tol_f, tol_g = 5e-3, 5e-2
     assert rel_err(y, yo) < tol_f
-    assert rel_err(g, go) < tol_g
+    assert_grad_blocks(g, go, net_grad_blocks(net), tol_g)
     if dx is not None:
         assert rel_err(dx, dxo) < tol_g
 

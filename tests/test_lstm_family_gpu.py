@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import Fixture, rel_err
+from tests.golden_util import Fixture, assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 2e-5, 3e-4
@@ -37,13 +37,16 @@ def test_golden_forward_backward(name, bb):
     assert rel_err(ya.cpu().numpy(), fx["ya"]) < FWD_TOL
 
 
-@pytest.mark.parametrize("bb,H", [("lstm", 14), ("lstm", 9), ("lstm", 20), ("vdlstm", 13), ("vdlstm", 8), ("vdlstm", 18)])
-@pytest.mark.parametrize("B,T", [(1, 3), (3, 5), (4, 32), (7, 33), (5, 200), (66, 63)])
-def test_against_oracle_ragged(bb, H, B, T):
+RAGGED_MODELS = [("lstm", 14), ("lstm", 9), ("lstm", 20), ("vdlstm", 13), ("vdlstm", 8), ("vdlstm", 18)]
+RAGGED_SHAPES = [(1, 3), (3, 5), (4, 32), (7, 33), (5, 200), (66, 63)]
+
+
+def ragged_case(bb, H, B, T, device="cuda"):
+    """model, input and output gradient of test_against_oracle_ragged (tests/test_grad_blocks_cpu.py holds the fp32 oracle to the
+    fp64 one on the same cases, `device` "cpu")"""
     from opendpd_amd import CoreModel
-    from oracle.oracle import Oracle, make_model
     torch.manual_seed(H * 100 + B + T)
-    net = CoreModel(2, H, 1, bb).cuda()
+    net = CoreModel(2, H, 1, bb).to(device)
     with torch.no_grad():
         for k, p in net.named_parameters():
             if "bias" in k:
@@ -53,6 +56,14 @@ def test_against_oracle_ragged(bb, H, B, T):
     ph = 2 * np.pi * rng.rand(B, T, 1)
     x = np.concatenate([amp * np.cos(ph), amp * np.sin(ph)], -1).astype(np.float32)
     dy = rng.randn(B, T, 2).astype(np.float32)
+    return net, x, dy
+
+
+@pytest.mark.parametrize("bb,H", RAGGED_MODELS)
+@pytest.mark.parametrize("B,T", RAGGED_SHAPES)
+def test_against_oracle_ragged(bb, H, B, T):
+    from oracle.oracle import Oracle, make_model
+    net, x, dy = ragged_case(bb, H, B, T)
     need_dx = True
     xt = torch.from_numpy(x).cuda().requires_grad_(need_dx)
     y = net(xt)
@@ -64,7 +75,7 @@ def test_against_oracle_ragged(bb, H, B, T):
     go, dxo = o.backward(m, p, x, dy)
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
     assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL
-    assert rel_err(g, go) < GRAD_TOL
+    assert_grad_blocks(g, go, net_grad_blocks(net), GRAD_TOL)
     if need_dx:
         assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
 
@@ -95,7 +106,7 @@ def test_lstm_frames_shorter_than_the_halo(s16, H, B, T):
     go, dxo = Oracle("f32").backward(m, p, x, dy)
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
     assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL
-    assert rel_err(g, go) < GRAD_TOL
+    assert_grad_blocks(g, go, net_grad_blocks(net), GRAD_TOL)
     assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
 
 
@@ -264,7 +275,7 @@ def test_gate_parallel_train_kernel(bb, H, B, T):
             loss = fused_train_step(opt, xt, tt, kind, 0.0)
             got = opt.grad[:-4].cpu().numpy().copy()
             assert abs(float(loss) - lo) < 2e-5 * max(1.0, lo)
-            assert rel_err(got, go) < GRAD_TOL
+            assert_grad_blocks(got, go, net_grad_blocks(net), GRAD_TOL)
             # the split kernels on the same batch
             lib.odpd_set_tuning(b"gp_max_batch", C.c_int64(0))
             opt2 = FusedAdamW(net, lr=0.0, weight_decay=0.0)

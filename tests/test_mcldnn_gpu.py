@@ -8,18 +8,18 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import Fixture, rel_err
+from tests.golden_util import Fixture, assert_grad_blocks, net_grad_blocks, rel_err
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 2e-5, 3e-4
 
 
-def _net(C, fx=None, prefix="sd"):
+def _net(C, fx=None, prefix="sd", device="cuda"):
     from opendpd_amd import CoreModel
     net = CoreModel(2, C, 1, "mcldnn")
     if fx is not None:
         net.load_state_dict({k: torch.from_numpy(fx[f"{prefix}/" + k]) for k in fx.keys(prefix)})
-    return net.cuda()
+    return net.to(device)
 
 
 def _iq(rng, B, T):
@@ -58,19 +58,35 @@ def test_second_reference_vector():
     assert rel_err(x.grad.cpu().numpy(), fx["gx"]) < GRAD_TOL
 
 
-@pytest.mark.parametrize("C", [1, 2, 3, 5, 8, 11, 16])
-@pytest.mark.parametrize("B,T", [(1, 4), (3, 5), (17, 32), (7, 33), (5, 200), (66, 63), (2, 36)])
-def test_against_oracle_ragged(C, B, T):
-    from oracle.oracle import Oracle, make_model
+RAGGED_CHANNELS = [1, 2, 3, 5, 8, 11, 16]
+RAGGED_SHAPES = [(1, 4), (3, 5), (17, 32), (7, 33), (5, 200), (66, 63), (2, 36)]
+# input seeds of the (C, B, T) on which B * 17 + T draws a dL/dy whose convolution gradients (conv2d_*.bias: one sum over every sample of
+# the batch per element) cancel so far that the serial fp32 oracle's own rounding on such a block exceeds GRAD_TOL / 16 of the fp64 oracle
+# (tests/test_grad_blocks_cpu.py; 1.9e-5 .. 8.1e-5 there): the first of B * 17 + T + 1000 k on which it does not
+RAGGED_RESEEDED = {(1, 1, 4): 1021, (3, 5, 200): 1285, (3, 66, 63): 2185, (5, 5, 200): 1285, (5, 66, 63): 2185, (11, 66, 63): 2185,
+                   (16, 5, 200): 3285, (16, 66, 63): 4185}
+
+
+def ragged_case(C, B, T, device="cuda"):
+    """model, input and output gradient of test_against_oracle_ragged (tests/test_grad_blocks_cpu.py holds the fp32 oracle to the
+    fp64 one on the same cases, `device` "cpu")"""
     torch.manual_seed(C * 100 + B + T)
-    net = _net(C)
+    net = _net(C, device=device)
     with torch.no_grad():
         for k, p in net.named_parameters():
             if "bias" in k:
                 p.uniform_(-0.3, 0.3)
-    rng = np.random.RandomState(B * 17 + T)
+    rng = np.random.RandomState(RAGGED_RESEEDED.get((C, B, T), B * 17 + T))
     x = _iq(rng, B, T)
     dy = rng.randn(B, T, 2).astype(np.float32)
+    return net, x, dy
+
+
+@pytest.mark.parametrize("C", RAGGED_CHANNELS)
+@pytest.mark.parametrize("B,T", RAGGED_SHAPES)
+def test_against_oracle_ragged(C, B, T):
+    from oracle.oracle import Oracle, make_model
+    net, x, dy = ragged_case(C, B, T)
     o = Oracle("f32")
     m = make_model("mcldnn", C)
     p = np.concatenate([q.detach().cpu().numpy().reshape(-1) for q in net.parameters()])
@@ -81,17 +97,15 @@ def test_against_oracle_ragged(C, B, T):
     y = net(torch.from_numpy(x).cuda())
     y.backward(torch.from_numpy(dy).cuda())
     assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL
-    sizes = [q.numel() for q in net.parameters()]
-    offs = np.cumsum([0] + sizes)
+    blocks = net_grad_blocks(net)
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    for (k, _), a, b in zip(net.named_parameters(), offs[:-1], offs[1:]):          # every tensor on its own scale
-        assert rel_err(g[a:b], go[a:b]) < GRAD_TOL, k
+    assert_grad_blocks(g, go, blocks, GRAD_TOL, exact_zeros=True)                  # every tensor on its own scale
     for q in net.parameters():
         q.grad = None
     xt = torch.from_numpy(x).cuda().requires_grad_(True)
     net(xt).backward(torch.from_numpy(dy).cuda())
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(g, go) < GRAD_TOL
+    assert_grad_blocks(g, go, blocks, GRAD_TOL)
     assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
     for q in net.parameters():
         q.requires_grad_(False)
@@ -124,7 +138,7 @@ def test_gate_parallel_train_kernel(C, B, T):
     p = np.concatenate([q.detach().cpu().numpy().reshape(-1) for q in net.parameters()])
     o, m = Oracle("f32"), make_model("mcldnn", C)
     yo, _ = o.forward(m, p, x)
-    offs = np.cumsum([0] + [q.numel() for q in net.parameters()])
+    blocks = net_grad_blocks(net)
     opt = FusedAdamW(net, lr=0.0, weight_decay=0.0)
     assert opt.has_fused(B, T)
     try:
@@ -136,8 +150,7 @@ def test_gate_parallel_train_kernel(C, B, T):
             loss = fused_train_step(opt, xt, tt, kind, 0.0)
             got = opt.grad[:-4].cpu().numpy().copy()
             assert abs(float(loss) - lo) < 2e-5 * max(1.0, lo)
-            for (k, _), a, b in zip(net.named_parameters(), offs[:-1], offs[1:]):
-                assert rel_err(got[a:b], go[a:b]) < GRAD_TOL, k
+            assert_grad_blocks(got, go, blocks, GRAD_TOL, exact_zeros=True)
             lib.odpd_set_tuning(b"gp_max_batch", C_.c_int64(0))
             opt2 = FusedAdamW(net, lr=0.0, weight_decay=0.0)
             assert not opt2.has_fused(B, T)
@@ -179,7 +192,8 @@ def test_large_batch_every_wave_slot():
     y.backward(torch.from_numpy(dy).cuda())
     assert rel_err(y.detach().cpu().numpy(), yo) < FWD_TOL
     g = np.concatenate([q.grad.cpu().numpy().reshape(-1) for q in net.parameters()])
-    assert rel_err(g, go) < GRAD_TOL and rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
+    assert_grad_blocks(g, go, net_grad_blocks(net), GRAD_TOL)
+    assert rel_err(xt.grad.cpu().numpy(), dxo) < GRAD_TOL
 
 
 @pytest.mark.parametrize("name", ["mcldnn_c8", "mcldnn_c3"])

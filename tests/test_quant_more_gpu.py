@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_util import Fixture, rel_err
+from tests.golden_util import Fixture, assert_grad_blocks, net_grad_blocks, rel_err
 from tests.test_oracle_golden import QAT_MORE, qat_param_names
 
 pytestmark = pytest.mark.gpu
@@ -229,15 +229,7 @@ def _w8a8_against_the_oracle(bb, H, B, T, q=None):
     y.backward(torch.from_numpy(dy).cuda())
     go, dxo = o.qat_backward(m, p, x, dy, need_dx=True)
     g = np.concatenate([(v.grad if v.grad is not None else torch.zeros_like(v)).cpu().numpy().reshape(-1) for v in q.parameters()])
-    sizes = [v.numel() for v in q.parameters()]
-    off = 0
-    for (k, _), n in zip(q.named_parameters(), sizes):      # per tensor: every parameter tensor on its own scale
-        ref = go[off:off + n]
-        if np.abs(ref).max() > 0:
-            assert rel_err(g[off:off + n], ref) < 3e-5, k
-        else:
-            assert np.abs(g[off:off + n]).max() == 0, k
-        off += n
+    assert_grad_blocks(g, go, net_grad_blocks(q, H), 3e-5, exact_zeros=True)      # every parameter tensor and gate on its own scale
     assert rel_err(xt.grad.cpu().numpy(), dxo) < 3e-5
     for v in q.parameters():
         v.requires_grad_(False)
