@@ -336,6 +336,25 @@ int64_t odpd_sweep_cascade_scratch_bytes(int K, int64_t n_steps);
 int odpd_train_epoch_cascade_sweep(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
                                    const float* const* pa_params, int loss_kind, const odpd_frames_t* fr, int batch, int64_t first_step,
                                    double beta1, double beta2, double eps, double weight_decay, double max_norm, void* scratch);
+/* ---- ... with a pair of delta thresholds PER RUN (the THX / THH knobs of bash_scripts/OpenDPDv2.sh, which project.py::gen_dpd_model_id puts into
+ * the model ID: the same (DPD, PA, seed) at several pairs).  The thresholds are the one value of a delta DPD's launch that is not a parameter, so
+ * the call above takes them from the descriptor, for all K runs; here run k's delta engine runs at (thresholds[2k], thresholds[2k + 1]) and the
+ * descriptor's own thx / thh are ignored.  Run k is bit-identical to odpd_train_epoch_cascade called alone with a descriptor that carries its
+ * pair — parameters, optimiser states, per-step losses and the four sparsity counters; with K equal pairs the call gives what
+ * odpd_train_epoch_cascade_sweep gives with that pair in the descriptor.
+ * odpd_sweep_cascade_th_supported: 1 where odpd_sweep_cascade_supported says 1 and the DPD is ODPD_DELTAGRU or ODPD_TRES_DELTAGRU, else 0
+ * (deltajanet is not on the one-launch cascade step, and its layer runs at thresholds 0).
+ * odpd_sweep_cascade_th_scratch_bytes: device bytes behind `scratch` of THIS call (run table, PA pointer table, K threshold pairs, per-step step
+ * sizes; the pairs are copied there and each workgroup reads its run's once, with the run's pointers); ODPD_EINVAL for K <= 0 or n_steps < 0.
+ * odpd_train_epoch_cascade_sweep_th: `thresholds` is a HOST array of K x 2 floats (thx_0, thh_0, thx_1, ..); everything else as above.
+ * ODPD_EINVAL: what the call above answers it for, thresholds == NULL, or an entry that is NaN, infinite or negative; ODPD_EUNSUPPORTED: a pair
+ * or batch (the tail batch included) odpd_sweep_cascade_th_supported refuses, or samples other than ODPD_SAMPLES_F32. */
+int odpd_sweep_cascade_th_supported(const odpd_model_t* dpd, const odpd_model_t* pa, int B, int T);
+int64_t odpd_sweep_cascade_th_scratch_bytes(int K, int64_t n_steps);
+int odpd_train_epoch_cascade_sweep_th(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
+                                      const float* const* pa_params, const float* thresholds, int loss_kind, const odpd_frames_t* fr, int batch,
+                                      int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                      void* scratch);
 
 /* clip_grad_norm_(max_norm) (0 = no clipping) + AdamW step over P parameters
  * (torch.optim.AdamW defaults project.py:283: betas .9/.999, eps 1e-8, weight_decay 0.01).

@@ -120,6 +120,11 @@ _EXPORTS = {
     "odpd_train_epoch_cascade_sweep": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(SweepRun), C.POINTER(C.c_void_p),
                                                  C.c_int, C.POINTER(Frames), C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                                  C.c_double, C.c_void_p]),
+    "odpd_sweep_cascade_th_supported": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "odpd_sweep_cascade_th_scratch_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "odpd_train_epoch_cascade_sweep_th": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(SweepRun), C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_float), C.c_int, C.POINTER(Frames), C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                                    C.c_double, C.c_double, C.c_void_p]),
     "odpd_clip_optim_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }

@@ -796,14 +796,18 @@ extern "C" int odpd_train_epoch_split(void* stream, const odpd_model_t* m, int l
 }
 // ---- lockstep sweeps: K independent runs of ONE model shape (the seeds of bash_scripts/train_all_pa.sh:26-57) advance together — per step
 // one fused train launch of K x grid workgroups, one row reduction, one clip + AdamW launch; each run bit-identical to its solo epoch.
-// scratch: run table | PA parameter pointers (the cascade sweep only) | K step sizes per step of the epoch ----
+// scratch: run table | PA parameter pointers (the cascade sweeps only) | K threshold pairs (the cascade threshold sweep only) | K step sizes per
+// step of the epoch ----
 namespace {
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline size_t sweep_pa_off(int K) { return align256((size_t)K * sizeof(SweepRun)); }
-inline size_t sweep_ss_off(int K, bool pa_table) { return sweep_pa_off(K) + (pa_table ? align256((size_t)K * sizeof(float*)) : 0); }
-inline int64_t sweep_scratch_bytes(int K, int64_t n_steps, bool pa_table) {
+inline size_t sweep_th_off(int K) { return sweep_pa_off(K) + align256((size_t)K * sizeof(float*)); }      // (behind the PA table)
+inline size_t sweep_ss_off(int K, bool pa_table, bool th_table = false) {
+    return sweep_pa_off(K) + (pa_table ? align256((size_t)K * sizeof(float*)) : 0) + (th_table ? align256((size_t)K * 2 * sizeof(float)) : 0);
+}
+inline int64_t sweep_scratch_bytes(int K, int64_t n_steps, bool pa_table, bool th_table = false) {
     if (K <= 0 || n_steps < 0) return ODPD_EINVAL;
-    return (int64_t)sweep_ss_off(K, pa_table) + (int64_t)K * n_steps * (int64_t)sizeof(float) + 256;
+    return (int64_t)sweep_ss_off(K, pa_table, th_table) + (int64_t)K * n_steps * (int64_t)sizeof(float) + 256;
 }
 // the pointers every run of a training sweep needs, and extra(k) on top of them
 template <class Extra>
@@ -833,21 +837,24 @@ inline int sweep_step_sizes(hipStream_t st, int K, const odpd_sweep_run_t* runs,
     }
     return (int)hipMemcpyAsync(ss_dev, ss.data(), ss.size() * sizeof(float), hipMemcpyHostToDevice, st);      // (pageable source, as above)
 }
-// One lockstep epoch: the run table, every run's PA parameter pointer (pa_params; NULL: no such table) and the step sizes into `scratch`, then
-// per step launch(step, run table, PA table, &rows) — the K runs' forward + loss + backward — one row reduction, one clip + AdamW launch
+// One lockstep epoch: the run table, every run's PA parameter pointer (pa_params; NULL: no such table), every run's threshold pair (thresholds,
+// K x 2 floats behind the PA table; NULL: no such table) and the step sizes into `scratch`, then per step
+// launch(step, run table, PA table, threshold table or NULL, &rows) — the K runs' forward + loss + backward — one row reduction, one clip + AdamW launch
 template <class Launch>
-inline int run_sweep_epoch(hipStream_t st, int K, const odpd_sweep_run_t* runs, const float* const* pa_params, const odpd_frames_t* fr, int batch,
-                           int64_t P, int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,
-                           void* scratch, Launch&& launch) {
+inline int run_sweep_epoch(hipStream_t st, int K, const odpd_sweep_run_t* runs, const float* const* pa_params, const float* thresholds,
+                           const odpd_frames_t* fr, int batch, int64_t P, int64_t first_step, double beta1, double beta2, double eps,
+                           double weight_decay, double max_norm, void* scratch, Launch&& launch) {
     SweepRun* dev = nullptr;
     if (int rc = upload_sweep(st, K, runs, weight_decay, scratch, &dev)) return rc;
     const float** pa_dev = reinterpret_cast<const float**>(reinterpret_cast<char*>(scratch) + sweep_pa_off(K));
     if (pa_params) ODPD_CHECK_HIP(hipMemcpyAsync(pa_dev, pa_params, (size_t)K * sizeof(float*), hipMemcpyHostToDevice, st));      // (pageable source, as above)
-    float* ss_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + sweep_ss_off(K, pa_params != nullptr));
+    float* th_dev = thresholds ? reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + sweep_th_off(K)) : nullptr;
+    if (th_dev) ODPD_CHECK_HIP(hipMemcpyAsync(th_dev, thresholds, (size_t)K * 2 * sizeof(float), hipMemcpyHostToDevice, st));      // (pageable source, as above)
+    float* ss_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + sweep_ss_off(K, pa_params != nullptr, thresholds != nullptr));
     if (int rc = sweep_step_sizes(st, K, runs, (fr->n_frames + batch - 1) / batch, first_step, beta1, ss_dev)) return rc;
     return epoch_steps(fr, batch, 0, 1, [&](const EpochStep& s) -> int {
         int64_t rows = 0;
-        if (int rc = launch(s, dev, pa_dev, &rows)) return rc;
+        if (int rc = launch(s, dev, pa_dev, th_dev, &rows)) return rc;
         if (int rc = launch_reduce_sweep(st, dev, K, rows, P)) return rc;
         return launch_clip_adamw_sweep(st, dev, K, P, ss_dev + s.i * K, first_step + s.i, s.i, beta1, beta2, eps, max_norm, s.inv_count);
     });
@@ -890,8 +897,8 @@ extern "C" int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K
         return ODPD_EUNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    return run_sweep_epoch(st, K, runs, /*pa_params*/ nullptr, fr, batch, odpd_param_count(m), first_step, beta1, beta2, eps, weight_decay, max_norm,
-                           scratch, [&](const EpochStep& s, SweepRun* dev, const float**, int64_t* rows) -> int {
+    return run_sweep_epoch(st, K, runs, /*pa_params*/ nullptr, /*thresholds*/ nullptr, fr, batch, odpd_param_count(m), first_step, beta1, beta2, eps,
+                           weight_decay, max_norm, scratch, [&](const EpochStep& s, SweepRun* dev, const float**, const float*, int64_t* rows) -> int {
                                SeqArgs a = make_args(m, s.B, T);
                                a.x = fr->x_stream; a.target = fr->y_stream; a.frame_stride = fr->stride; a.inv_count = s.inv_count;
                                a.frames_bf16 = fr->sample_format == ODPD_SAMPLES_BF16; a.loss_kind = loss_kind;
@@ -909,28 +916,56 @@ extern "C" int odpd_sweep_cascade_supported(const odpd_model_t* dpd, const odpd_
     return odpd_cascade_rows(dpd, pa, B, T) > 0 ? 1 : 0;
 }
 extern "C" int64_t odpd_sweep_cascade_scratch_bytes(int K, int64_t n_steps) { return sweep_scratch_bytes(K, n_steps, true); }
-extern "C" int odpd_train_epoch_cascade_sweep(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
-                                              const float* const* pa_params, int loss_kind, const odpd_frames_t* fr, int batch, int64_t first_step,
-                                              double beta1, double beta2, double eps, double weight_decay, double max_norm, void* scratch) {
+// both cascade sweep entry points; thresholds (HOST, K x 2; NULL: the descriptor's pair for every run) and th_call tell them apart
+static int cascade_sweep_epoch(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
+                               const float* const* pa_params, const float* thresholds, bool th_call, int loss_kind, const odpd_frames_t* fr,
+                               int batch, int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                               void* scratch) {
     if (!dpd || !pa || !model_ok(dpd) || !model_ok(pa) || K <= 0 || !runs || !pa_params || !epoch_frames_ok(fr, batch, false) || first_step <= 0 ||
-        !scratch)
+        !scratch || (th_call && !thresholds))
         return ODPD_EINVAL;
     // (on top of the common pointers: every run's PA; workspace = a delta DPD's sparsity counters — doubles — or NULL)
     if (!sweep_runs_ok(K, runs, [&](int k) { return pa_params[k] && !(reinterpret_cast<uintptr_t>(runs[k].workspace) & 7); })) return ODPD_EINVAL;
+    if (th_call)      // (|delta| < threshold masks the delta: finite and not negative)
+        for (int i = 0; i < 2 * K; ++i)
+            if (!std::isfinite(thresholds[i]) || thresholds[i] < 0.0f) return ODPD_EINVAL;
     if (fr->sample_format != ODPD_SAMPLES_F32) return ODPD_EUNSUPPORTED;
     const int T = fr->frame_length;
-    if (!epoch_shapes_served(fr, batch, 0, 1, [&](int B) { return odpd_sweep_cascade_supported(dpd, pa, B, T) != 0; })) return ODPD_EUNSUPPORTED;
+    if (!epoch_shapes_served(fr, batch, 0, 1, [&](int B) {
+            return (th_call ? odpd_sweep_cascade_th_supported(dpd, pa, B, T) : odpd_sweep_cascade_supported(dpd, pa, B, T)) != 0;
+        }))
+        return ODPD_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     CascArgs a{};
-    a.thx = dpd->thx; a.thh = dpd->thh; a.bits_w = dpd->bits_w; a.bits_a = dpd->bits_a;
+    a.thx = dpd->thx; a.thh = dpd->thh; a.bits_w = dpd->bits_w; a.bits_a = dpd->bits_a;      // (a threshold sweep: the kernel overwrites the pair per run)
     a.x = fr->x_stream; a.target = fr->y_stream; a.frame_stride = fr->stride;
     a.loss_kind = loss_kind; a.T = T; a.Hd = dpd->hidden; a.Hp = pa->hidden;
-    return run_sweep_epoch(st, K, runs, pa_params, fr, batch, odpd_param_count(dpd), first_step, beta1, beta2, eps, weight_decay, max_norm, scratch,
-                           [&](const EpochStep& s, SweepRun* dev, const float** pa_dev, int64_t* rows) -> int {
+    return run_sweep_epoch(st, K, runs, pa_params, thresholds, fr, batch, odpd_param_count(dpd), first_step, beta1, beta2, eps, weight_decay, max_norm,
+                           scratch, [&](const EpochStep& s, SweepRun* dev, const float** pa_dev, const float* th_dev, int64_t* rows) -> int {
                                a.B = s.B; a.inv_count = s.inv_count;
                                *rows = odpd_cascade_rows(dpd, pa, s.B, T);
-                               return gru_cascade_sweep_train(st, dpd, pa, a, dev, pa_dev, K, (long long)s.f0);
+                               return gru_cascade_sweep_train(st, dpd, pa, a, dev, pa_dev, th_dev, K, (long long)s.f0);
                            });
+}
+extern "C" int odpd_train_epoch_cascade_sweep(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
+                                              const float* const* pa_params, int loss_kind, const odpd_frames_t* fr, int batch, int64_t first_step,
+                                              double beta1, double beta2, double eps, double weight_decay, double max_norm, void* scratch) {
+    return cascade_sweep_epoch(stream, dpd, pa, K, runs, pa_params, /*thresholds*/ nullptr, false, loss_kind, fr, batch, first_step, beta1, beta2, eps,
+                               weight_decay, max_norm, scratch);
+}
+// ---- ... with a pair of delta thresholds per run (the THX / THH knobs of bash_scripts/OpenDPDv2.sh): deltagru / deltagru_tcnskip DPDs only;
+// the pairs travel behind the PA pointer table and are read once per workgroup ----
+extern "C" int odpd_sweep_cascade_th_supported(const odpd_model_t* dpd, const odpd_model_t* pa, int B, int T) {
+    if (!odpd_sweep_cascade_supported(dpd, pa, B, T)) return 0;
+    return dpd->backbone == ODPD_DELTAGRU || dpd->backbone == ODPD_TRES_DELTAGRU ? 1 : 0;
+}
+extern "C" int64_t odpd_sweep_cascade_th_scratch_bytes(int K, int64_t n_steps) { return sweep_scratch_bytes(K, n_steps, true, true); }
+extern "C" int odpd_train_epoch_cascade_sweep_th(void* stream, const odpd_model_t* dpd, const odpd_model_t* pa, int K, const odpd_sweep_run_t* runs,
+                                                 const float* const* pa_params, const float* thresholds, int loss_kind, const odpd_frames_t* fr,
+                                                 int batch, int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
+                                                 double max_norm, void* scratch) {
+    return cascade_sweep_epoch(stream, dpd, pa, K, runs, pa_params, thresholds, true, loss_kind, fr, batch, first_step, beta1, beta2, eps, weight_decay,
+                               max_norm, scratch);
 }
 extern "C" int odpd_backbone_fwd_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int B, int T, const float* x,
                                        void* scratch) {

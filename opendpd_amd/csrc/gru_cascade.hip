@@ -17,6 +17,7 @@
 // (odpd_lstm.h) of <= 16 units as the DPD.
 // *_cascade_sweep_kernel: the same three bodies for K lockstep runs in one launch (odpd_train_epoch_cascade_sweep) — a workgroup fills a CU's
 // LDS, so one run's batch of 64 leaves most of the chip idle, and K runs side by side are what fills it.
+// delta_cascade_sweep_th_kernel: ... with a pair of delta thresholds per run (odpd_train_epoch_cascade_sweep_th: the THX / THH sweep).
 #include "odpd_gpseq.h"
 #include "odpd_deltaseq.h"
 #include "odpd_lstm.h"
@@ -201,11 +202,14 @@ __global__ __launch_bounds__(128) void lstm_cascade_kernel(CascArgs a) {
 // parameters, its frozen PA (pa_tab[k]: the PAs of a seed sweep differ), its epoch order from the step's first frame on, its partial rows
 // and (delta DPDs) its sparsity counters.  Workgroups never wait for one another (workgroup barriers and per-workgroup rows only), so the
 // launch may hold more workgroups than the chip hosts at once.
+// th_tab (delta_cascade_sweep_th_kernel only; elsewhere the constant NULL, which leaves the launch-wide pair of `a` and no trace in the
+// code): the run's own delta thresholds (thx_k, thh_k) — read here, once per workgroup, with the run's other pointers
 __device__ __forceinline__ void casc_sweep_args(CascArgs& a, const SweepRun* __restrict__ runs, const float* const* __restrict__ pa_tab, int k,
-                                                long long first) {
+                                                long long first, const float2* __restrict__ th_tab = nullptr) {
     const SweepRun r = runs[k];
     a.dpd_params = r.params; a.pa_params = pa_tab[k]; a.partials = r.partials; a.frame_idx = r.order + first;
     a.stats = reinterpret_cast<double*>(r.workspace);
+    if (th_tab) { const float2 th = th_tab[k]; a.thx = th.x; a.thh = th.y; }
 }
 template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
 __global__ __launch_bounds__(128) void gru_cascade_sweep_kernel(CascArgs a, const SweepRun* __restrict__ runs,
@@ -217,6 +221,15 @@ template <bool TRES, int PV, int FMP, bool DGP>
 __global__ __launch_bounds__(128) void delta_cascade_sweep_kernel(CascArgs a, const SweepRun* __restrict__ runs,
                                                                   const float* const* __restrict__ pa_tab, int G, long long first) {
     casc_sweep_args(a, runs, pa_tab, blockIdx.x / G, first);
+    delta_cascade_body<TRES, PV, FMP, DGP>(a, blockIdx.x % G, G);
+}
+// ... of a threshold sweep (odpd_train_epoch_cascade_sweep_th): the same launch, run k's delta engine at th_tab[k] instead of the pair of `a`.
+// A kernel of its own, so that the seed sweep above stays the code object it was (its thresholds are kernel arguments, not a load)
+template <bool TRES, int PV, int FMP, bool DGP>
+__global__ __launch_bounds__(128) void delta_cascade_sweep_th_kernel(CascArgs a, const SweepRun* __restrict__ runs,
+                                                                     const float* const* __restrict__ pa_tab,
+                                                                     const float2* __restrict__ th_tab, int G, long long first) {
+    casc_sweep_args(a, runs, pa_tab, blockIdx.x / G, first, th_tab);
     delta_cascade_body<TRES, PV, FMP, DGP>(a, blockIdx.x % G, G);
 }
 template <int PV, int FMP, bool DGP>
@@ -321,12 +334,15 @@ int casc_launch(hipStream_t st, const CascArgs& a, const CascCfg& c) {
 }
 // the sweep form of casc_launch: K x G workgroups, G = the solo grid of this (B, T)
 template <int NBD, int FMD, bool DGD, int PV, int FMP, bool DGP>
-int casc_sweep_launch(hipStream_t st, const CascArgs& a, const CascCfg& c, const SweepRun* runs, const float* const* pa_tab, int K, long long first) {
+int casc_sweep_launch(hipStream_t st, const CascArgs& a, const CascCfg& c, const SweepRun* runs, const float* const* pa_tab, const float2* th_tab,
+                      int K, long long first) {
     const size_t lds = casc_lds<NBD, FMD, DGD, PV, FMP, DGP>(a.T, c.Pd, c.Pp);
     const int G = casc_grid(c, a.B, a.T);
     auto launch = [&](auto k) { return launch_lds(st, k, G * K, 128, lds, a, runs, pa_tab, G, first); };      // (G K < 2^31: checked by the caller)
-    if constexpr (FMD == kDpdDelta || FMD == kDpdTres) return launch(delta_cascade_sweep_kernel<FMD == kDpdTres, PV, FMP, DGP>);
-    else if constexpr (FMD == kDpdLstm) return launch(lstm_cascade_sweep_kernel<PV, FMP, DGP>);
+    if constexpr (FMD == kDpdDelta || FMD == kDpdTres) {
+        if (th_tab) return launch_lds(st, delta_cascade_sweep_th_kernel<FMD == kDpdTres, PV, FMP, DGP>, G * K, 128, lds, a, runs, pa_tab, th_tab, G, first);
+        return launch(delta_cascade_sweep_kernel<FMD == kDpdTres, PV, FMP, DGP>);
+    } else if constexpr (FMD == kDpdLstm) return launch(lstm_cascade_sweep_kernel<PV, FMP, DGP>);
     else return launch(gru_cascade_sweep_kernel<NBD, FMD, DGD, PV, FMP, DGP>);
 }
 }  // namespace
@@ -349,13 +365,15 @@ int gru_cascade_train(hipStream_t st, const odpd_model_t* dpd, const odpd_model_
 }
 
 // K runs of one (DPD, PA) shape pair in one launch (float DPDs only: the quantised ones keep the per-run epoch); a.dpd_params / pa_params /
-// partials / frame_idx / stats come from the two device tables
+// partials / frame_idx / stats come from the two device tables; th_tab != NULL (delta DPDs only): a.thx / a.thh from a third, K (thx, thh) pairs
 int gru_cascade_sweep_train(hipStream_t st, const odpd_model_t* dpd, const odpd_model_t* pa, const CascArgs& a, const SweepRun* runs,
-                            const float* const* pa_tab, int K, long long first) {
+                            const float* const* pa_tab, const float* th_tab, int K, long long first) {
     CascCfg c;
     if (!casc_cfg(dpd, pa, c) || c.fmd == kDpdQat || casc_grid(c, a.B, a.T) <= 0 || K <= 0 || !runs || !pa_tab) return ODPD_EUNSUPPORTED;
     if ((long long)casc_grid(c, a.B, a.T) * K > 0x7fffffffLL) return ODPD_EUNSUPPORTED;
-#define ODPD_CASC_SWEEP(NBD_, FMD_, DGD_, PV_, FMP_, DGP_) casc_sweep_launch<NBD_, FMD_, DGD_, PV_, FMP_, DGP_>(st, a, c, runs, pa_tab, K, first)
+    if (th_tab && c.fmd != kDpdDelta && c.fmd != kDpdTres) return ODPD_EUNSUPPORTED;
+    const float2* th2 = reinterpret_cast<const float2*>(th_tab);
+#define ODPD_CASC_SWEEP(NBD_, FMD_, DGD_, PV_, FMP_, DGP_) casc_sweep_launch<NBD_, FMD_, DGD_, PV_, FMP_, DGP_>(st, a, c, runs, pa_tab, th2, K, first)
     ODPD_CASC_ALL(ODPD_CASC_SWEEP)
 #undef ODPD_CASC_SWEEP
     return ODPD_EUNSUPPORTED;

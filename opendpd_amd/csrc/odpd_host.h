@@ -335,9 +335,10 @@ int qat_gp_train_rows(const odpd_model_t* m, int B, int T);
 int qat_gp_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_cascade_train(hipStream_t s, const odpd_model_t* dpd, const odpd_model_t* pa, const CascArgs& a);
 // K lockstep runs of one float (DPD, PA) pair, one launch of K x rows workgroups: a.dpd_params / partials / frame_idx / stats come from the
-// run table (stats = the run's `workspace`), a.pa_params from pa_tab[k] (device table of K device pointers)
+// run table (stats = the run's `workspace`), a.pa_params from pa_tab[k] (device table of K device pointers); th_tab (NULL: a.thx / a.thh
+// for every run): device table of K (thx, thh) pairs, 8-byte aligned, run k's delta engine at its own — delta DPDs only, else ODPD_EUNSUPPORTED
 int gru_cascade_sweep_train(hipStream_t s, const odpd_model_t* dpd, const odpd_model_t* pa, const CascArgs& a, const SweepRun* runs,
-                            const float* const* pa_tab, int K, long long first);
+                            const float* const* pa_tab, const float* th_tab, int K, long long first);
 // 16-sequences-per-wave fused kernel (gru_s16.hip) and the rule that selects it
 bool gru_train_uses_s16(const odpd_model_t* m, int B, int T);
 int gru_s16_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);

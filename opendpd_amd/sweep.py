@@ -11,7 +11,9 @@ families, batches beyond the one-sequence-per-wave regime) advance through the o
 `train_dpd_sweep` does the same for `train_dpd` (bash_scripts/train_all_dpd.sh: seeds x DPD backbones, each DPD in front of the frozen PA of
 its own seed).  Its step is the one-launch cascade step, which gives every frame a workgroup with a CU's LDS to itself: at batch 64 a solo
 run occupies 64 CUs, and the launch that carries K runs (csrc: odpd_train_epoch_cascade_sweep) fills the rest of the chip while every run
-stays its solo run bit for bit — for train_dpd the chip-filling mode and the exact mode are the same mode."""
+stays its solo run bit for bit — for train_dpd the chip-filling mode and the exact mode are the same mode.  The delta thresholds of a
+deltagru / deltagru_tcnskip DPD are one more axis of such a sweep (`thresholds=`: the THX / THH knobs of bash_scripts/OpenDPDv2.sh): runs that
+differ in their pair share the launch too, each workgroup reading its run's pair from a device table (csrc: odpd_train_epoch_cascade_sweep_th)."""
 import ctypes as C
 import random
 import time
@@ -401,8 +403,10 @@ def _setup_dpd(run):
 
 def _dpd_group_key(run):
     p = run.proj
+    # the thresholds of a float deltagru / deltagru_tcnskip DPD are a per-run value of the launch (_DpdGroup._size_buffers), not part of its shape
+    th = (None, None) if p.DPD_backbone in ("deltagru", "deltagru_tcnskip") and not p.quant else (p.thx, p.thh)
     return (p.DPD_backbone, p.DPD_hidden_size, p.DPD_num_layers, p.PA_backbone, p.PA_hidden_size, p.PA_num_layers, p.batch_size, p.frame_length,
-            p.frame_stride, p.loss_type, p.opt_type, p.dataset_label, p.frame_storage, p.grad_clip_val, p.thx, p.thh, p.quant, p.n_bits_w,
+            p.frame_stride, p.loss_type, p.opt_type, p.dataset_label, p.frame_storage, p.grad_clip_val, *th, p.quant, p.n_bits_w,
             p.n_bits_a, p.pretrained_model, p.quant_dir_label, p.q_pretrain)
 
 
@@ -423,11 +427,13 @@ class _DpdGroup:
         self.eligible = bool(fused and self.kind is not None and len(runs) > 1 and hasattr(train, "epoch_order") and train.x.is_cuda
                              and train.x.dtype == torch.float32)
         self.train_sweep = False
+        self.thresholds = None
         self.scratch = None
         self._tuning_gen = None
         self._size_buffers()
 
-    # run 0's descriptors (the group key makes them the group's), asked for at each use
+    # run 0's descriptors (the group key makes them the group's — but for the thresholds of a delta DPD, which `thresholds` carries per run where
+    # they differ), asked for at each use
     @property
     def dpd_desc(self):
         return _call_desc(getattr(self.runs[0].net.dpd_model, "backbone", None))
@@ -438,18 +444,24 @@ class _DpdGroup:
         return self.runs[0].opt._pa_desc()
 
     def _size_buffers(self):
-        """whether the cascade sweep launch serves the group, and the partial rows / scratch of every run, under the CURRENT kernel-selection
-        knobs (odpd_set_tuning: cascade_one_launch, gp_max_batch ..); re-done by train_epoch when odpd_tuning_generation has moved"""
+        """whether a cascade sweep launch serves the group — runs of one threshold pair: odpd_train_epoch_cascade_sweep with run 0's descriptor;
+        of differing pairs: odpd_train_epoch_cascade_sweep_th with the K pairs in `thresholds` — and the partial rows / scratch of every run, under
+        the CURRENT kernel-selection knobs (odpd_set_tuning: cascade_one_launch, gp_max_batch ..); re-done by train_epoch when
+        odpd_tuning_generation has moved"""
         lib = _lib.load()
         self._tuning_gen = int(lib.odpd_tuning_generation())
+        pairs = [(float(r.proj.thx), float(r.proj.thh)) for r in self.runs]
+        self.thresholds = None if all(p == pairs[0] for p in pairs) else (C.c_float * (2 * len(pairs)))(*(v for p in pairs for v in p))
+        supported = lib.odpd_sweep_cascade_supported if self.thresholds is None else lib.odpd_sweep_cascade_th_supported
         self.train_sweep = bool(self.eligible and all(
-            lib.odpd_sweep_cascade_supported(C.byref(self.dpd_desc), C.byref(self.pa_desc), b, self.T) == 1 for b in {self.B, self.last}))
+            supported(C.byref(self.dpd_desc), C.byref(self.pa_desc), b, self.T) == 1 for b in {self.B, self.last}))
         if self.train_sweep:
             rows = max(cascade_rows(self.dpd_desc, self.pa_desc, b, self.T) for b in {self.B, self.last})
             for r in self.runs:
                 r.opt._ensure(self.dev)
                 r.partials = rows_buffer(rows, r.opt.backbone.n_flat, self.dev)
-            self.scratch = torch.empty(int(lib.odpd_sweep_cascade_scratch_bytes(len(self.runs), self.n_steps)), dtype=torch.uint8, device=self.dev)
+            scratch_bytes = lib.odpd_sweep_cascade_scratch_bytes if self.thresholds is None else lib.odpd_sweep_cascade_th_scratch_bytes
+            self.scratch = torch.empty(int(scratch_bytes(len(self.runs), self.n_steps)), dtype=torch.uint8, device=self.dev)
 
     # ---- one training epoch of every run of the group ----
     def train_epoch(self):
@@ -466,9 +478,15 @@ class _DpdGroup:
         table, fr, adamw = _epoch_tables(self.runs, self.n, self.T, self.n_steps, self.dev, lambda r: r.opt.backbone._stats_buffer(self.dev))
         pa_flat = [r.opt.pa.flat_params(full_check=True) for r in self.runs]
         pa_tab = (C.c_void_p * len(self.runs))(*(f.data_ptr() for f in pa_flat))
-        rc = lib.odpd_train_epoch_cascade_sweep(_lib.stream_ptr(), C.byref(self.dpd_desc), C.byref(self.pa_desc), len(self.runs), table, pa_tab,
-                                                _lib.LOSS_IDS[self.kind], C.byref(fr), self.B, *adamw, C.c_void_p(self.scratch.data_ptr()))
-        _lib.check(rc, "odpd_train_epoch_cascade_sweep")
+        if self.thresholds is None:
+            rc = lib.odpd_train_epoch_cascade_sweep(_lib.stream_ptr(), C.byref(self.dpd_desc), C.byref(self.pa_desc), len(self.runs), table, pa_tab,
+                                                    _lib.LOSS_IDS[self.kind], C.byref(fr), self.B, *adamw, C.c_void_p(self.scratch.data_ptr()))
+            _lib.check(rc, "odpd_train_epoch_cascade_sweep")
+        else:
+            rc = lib.odpd_train_epoch_cascade_sweep_th(_lib.stream_ptr(), C.byref(self.dpd_desc), C.byref(self.pa_desc), len(self.runs), table, pa_tab,
+                                                       self.thresholds, _lib.LOSS_IDS[self.kind], C.byref(fr), self.B, *adamw,
+                                                       C.c_void_p(self.scratch.data_ptr()))
+            _lib.check(rc, "odpd_train_epoch_cascade_sweep_th")
         _epoch_done(self.runs, self.n_steps)
 
     # ---- validation + test of every run of the group: what train_funcs.net_eval_pair computes for each run ----
@@ -518,16 +536,46 @@ class _DpdGroup:
         _metrics_many(self.runs, outs)
 
 
+def _threshold_pairs(thresholds, thx, thh, DPD_backbone):
+    """the (thx, thh) pairs of train_dpd_sweep(thresholds=...) as floats, or ValueError for what cannot be a sweep: the runs' files are named
+    after f"{v:.3f}" of their pair, and only for a delta backbone (project.gen_dpd_model_id)"""
+    import math
+    if thx or thh:
+        raise ValueError("train_dpd_sweep: give either thresholds=[(thx, thh), ..] or thx= / thh=, not both")
+    try:
+        pairs = [(float(a), float(b)) for a, b in thresholds]
+    except (TypeError, ValueError):
+        raise ValueError("train_dpd_sweep: thresholds must be a sequence of (thx, thh) pairs") from None
+    if not pairs:
+        raise ValueError("train_dpd_sweep: thresholds holds no pair")
+    for pair in pairs:
+        if not all(math.isfinite(v) and v >= 0.0 for v in pair):
+            raise ValueError(f"train_dpd_sweep: the thresholds {pair} are not finite numbers >= 0")
+    names = [(f"{a:.3f}", f"{b:.3f}") for a, b in pairs]
+    if len(set(names)) != len(names):
+        raise ValueError(f"train_dpd_sweep: two threshold pairs would write the same files (model IDs carry them as THX_%.3f_THH_%.3f): {names}")
+    if len(pairs) > 1 and "delta" not in DPD_backbone:
+        raise ValueError(f"train_dpd_sweep: the model ID of a {DPD_backbone!r} DPD holds no thresholds, {len(pairs)} pairs would overwrite each other")
+    return pairs
+
+
 def train_dpd_sweep(dataset_name=None, seeds=(0,), hidden_sizes=None, DPD_backbone="deltagru_tcnskip", DPD_hidden_size=15, PA_backbone="gru",
-                    PA_hidden_size=23, n_epochs=100, batch_size=256, lr=5e-4, accelerator="cuda", frame_length=200, thx=0.0, thh=0.0, **kwargs):
+                    PA_hidden_size=23, n_epochs=100, batch_size=256, lr=5e-4, accelerator="cuda", frame_length=200, thx=0.0, thh=0.0,
+                    thresholds=None, **kwargs):
     """`opendpd.api.train_dpd` for every (DPD hidden size, seed) pair, the runs of one (DPD, PA) shape pair advancing in lockstep on one GPU:
     every training step of a group is ONE cascade launch for all its runs (+ one row reduction, one clip + AdamW launch).  Each run trains in
     front of the frozen PA `train_pa` saved for its own seed and is its solo `train_dpd` bit for bit (same files under `save/` and `log/`).
     Returns one result dictionary per run ({'status', 'model_path', 'log_path', 'seed', 'DPD_hidden_size', 'lockstep'}), in
     hidden-size-major order.  Groups the sweep launch does not serve (quantised DPDs, other families or optimisers, a single run) advance
-    through the ordinary per-run epoch inside the same loop ('lockstep': False)."""
+    through the ordinary per-run epoch inside the same loop ('lockstep': False).
+    thresholds: a sequence of (thx, thh) pairs instead of the one pair thx= / thh= — the runs are then every (hidden size, pair, seed), in that
+    nesting order, and each result also carries 'thx' and 'thh'.  Float deltagru / deltagru_tcnskip runs that differ only in their pair form one
+    group and share its launches, each at its own thresholds (evaluation stays per run: every module counts its own sparsity); for any other
+    DPD each pair is a group of its own.  ValueError: thresholds together with a non-zero thx / thh, a negative or non-finite value, two pairs
+    that print alike at three decimals (they would write the same files), several pairs for a backbone that is not a delta one."""
     if not dataset_name:
         raise ValueError("train_dpd_sweep requires dataset_name. Create a dataset first with create_dataset().")
+    pairs = [(thx, thh)] if thresholds is None else _threshold_pairs(thresholds, thx, thh, DPD_backbone)
     from . import data as D
     from . import project as PJ
     runs = []
@@ -535,14 +583,15 @@ def train_dpd_sweep(dataset_name=None, seeds=(0,), hidden_sizes=None, DPD_backbo
     PJ._stream_share = {}      # ... and one upload of its train streams (read-only on the device)
     try:
         for H in (list(hidden_sizes) if hidden_sizes else [DPD_hidden_size]):
-            for seed in seeds:
-                run = _Run(None)
-                with run.rng:      # Project.__init__ seeds the global RNGs (project.py:108-112): from here on this run owns its own copy of them
-                    run.proj = Project(step="train_dpd", dataset_name=dataset_name, DPD_backbone=DPD_backbone, DPD_hidden_size=int(H),
-                                       PA_backbone=PA_backbone, PA_hidden_size=PA_hidden_size, n_epochs=n_epochs, batch_size=batch_size, lr=lr,
-                                       accelerator=accelerator, frame_length=frame_length, seed=int(seed), thx=thx, thh=thh, **kwargs)
-                    _setup_dpd(run)
-                runs.append(run)
+            for pair in pairs:
+                for seed in seeds:
+                    run = _Run(None)
+                    with run.rng:      # Project.__init__ seeds the global RNGs (project.py:108-112): from here on this run owns its own copy of them
+                        run.proj = Project(step="train_dpd", dataset_name=dataset_name, DPD_backbone=DPD_backbone, DPD_hidden_size=int(H),
+                                           PA_backbone=PA_backbone, PA_hidden_size=PA_hidden_size, n_epochs=n_epochs, batch_size=batch_size, lr=lr,
+                                           accelerator=accelerator, frame_length=frame_length, seed=int(seed), thx=pair[0], thh=pair[1], **kwargs)
+                        _setup_dpd(run)
+                    runs.append(run)
     finally:
         D._share = None
         PJ._stream_share = None
@@ -552,4 +601,5 @@ def train_dpd_sweep(dataset_name=None, seeds=(0,), hidden_sizes=None, DPD_backbo
     groups = [_DpdGroup(v) for v in groups.values()]
     _sweep_loop(runs, groups, n_epochs, "ACLR_AVG")
     return [{"status": "completed", "model_path": r.proj.path_save_file_best, "log_path": r.proj.path_log_file_best, "seed": r.proj.seed,
-             "DPD_hidden_size": r.proj.DPD_hidden_size, "lockstep": bool(g_.train_sweep)} for g_ in groups for r in g_.runs]
+             "DPD_hidden_size": r.proj.DPD_hidden_size, "lockstep": bool(g_.train_sweep),
+             **({} if thresholds is None else {"thx": r.proj.thx, "thh": r.proj.thh})} for g_ in groups for r in g_.runs]
