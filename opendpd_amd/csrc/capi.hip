@@ -27,12 +27,6 @@ inline Family family_of(const odpd_model_t* m) {
         return FAM_QAT;
     return family_of((int)m->backbone);
 }
-// which QAT kernels serve a batch: the row-rotated ones (qgru_family.hip: qgru / qgru_amp1, hidden <= 16, 4 sequences per wave) while
-// the batch leaves the chip mostly empty, the 16-sequences-per-wave ones (qat_s16.hip) otherwise and for every other kind / hidden size
-inline bool qat_uses_s16(const odpd_model_t* m, int B) {
-    const bool rot_ok = (m->backbone == ODPD_QGRU || m->backbone == ODPD_QGRU_AMP1) && m->hidden <= 16;
-    return !rot_ok || B >= s16_min_batch_or(16L * 3 * device_cus());
-}
 inline Family family_of(int bb) {
     switch (bb) {
     case ODPD_GRU: case ODPD_DGRU: case ODPD_QGRU: case ODPD_QGRU_AMP1: return FAM_GRU;
@@ -138,8 +132,10 @@ inline SeqArgs make_args(const odpd_model_t* m, int B, int T) {
 }
 
 // ---- table 2: dvrjanet, bojanet, apnrru and mcldnn on the 16-sequences-per-wave f4 mapping share one interface ----
+template <int (*LAUNCH)(hipStream_t, const odpd_model_t*, const SeqArgs&, int), int MODE>      // (mode 1 forward, 2 backward)
+int f4_call(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return LAUNCH(st, m, a, MODE); }
 struct F4Backbone {
-    int (*launch)(hipStream_t, const odpd_model_t*, const SeqArgs&, int mode);      // mode 1 forward, 2 backward
+    SeqFn fwd, bwd;
     int (*rows)(const odpd_model_t*, int B);
     int64_t (*param_count)(const odpd_model_t*);
     int64_t (*ckpt_floats)(const odpd_model_t*, int B, int T);
@@ -149,13 +145,13 @@ struct F4Backbone {
 };
 constexpr F4Backbone kF4[] = {      // FAM_DVR .. FAM_MCL, in the enum's order
     // K + 7H^2 + 7H + 2 parameters, K = bits_w (dvrjanet.py:11-30, 47-52)
-    {dvrjanet_launch, dvrjanet_rows, dvrjanet_param_count, dvrjanet_ckpt_floats, dvrjanet_train_uses_gp, dvrjanet_gp_rows, dvrjanet_gp_train},
+    {f4_call<dvrjanet_launch, 1>, f4_call<dvrjanet_launch, 2>, dvrjanet_rows, dvrjanet_param_count, dvrjanet_ckpt_floats, dvrjanet_train_uses_gp, dvrjanet_gp_rows, dvrjanet_gp_train},
     // 2H^2 + 28H + 194 (bojanet.py:15-26)
-    {bojanet_launch, bojanet_rows, bojanet_param_count, bojanet_ckpt_floats, bojanet_train_uses_gp, bojanet_gp_rows, bojanet_gp_train},
+    {f4_call<bojanet_launch, 1>, f4_call<bojanet_launch, 2>, bojanet_rows, bojanet_param_count, bojanet_ckpt_floats, bojanet_train_uses_gp, bojanet_gp_rows, bojanet_gp_train},
     // 343 + 70H (apnrru.py:13-19, 45-53)
-    {apnrru_launch, apnrru_rows, apnrru_param_count, apnrru_ckpt_floats, apnrru_train_uses_gp, apnrru_gp_rows, apnrru_gp_train},
+    {f4_call<apnrru_launch, 1>, f4_call<apnrru_launch, 2>, apnrru_rows, apnrru_param_count, apnrru_ckpt_floats, apnrru_train_uses_gp, apnrru_gp_rows, apnrru_gp_train},
     // 190C + 589 (mcldnn.py:21-27)
-    {mcldnn_launch, mcldnn_rows, mcldnn_param_count, mcldnn_ckpt_floats, mcldnn_train_uses_gp, mcldnn_gp_rows, mcldnn_gp_train},
+    {f4_call<mcldnn_launch, 1>, f4_call<mcldnn_launch, 2>, mcldnn_rows, mcldnn_param_count, mcldnn_ckpt_floats, mcldnn_train_uses_gp, mcldnn_gp_rows, mcldnn_gp_train},
 };
 static_assert(FAM_BOJ == FAM_DVR + 1 && FAM_APN == FAM_DVR + 2 && FAM_MCL == FAM_DVR + 3, "kF4 is indexed by family");
 inline const F4Backbone* f4_of(const odpd_model_t* m) {      // (family_of: a flagged descriptor is none of them)
@@ -174,18 +170,6 @@ struct FusedStep {
     WsKind ws;
     bool framed;            // the kernel addresses frames inside resident streams (SeqArgs::frame_idx): the framed entry points serve the shape
 };
-// (launchers that take one argument more, as SeqFn)
-int gru_s16x_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return gru_s16x_train(st, m, a, gru_s16n_rows(m, a.B)); }
-int gru_s16n_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return gru_s16n_launch(st, m, a, 0); }
-int qat_s16_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { return qat_s16_launch(st, m, a, 0); }
-int qat_gp_step(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) { SeqArgs b = a; b.ckpt = nullptr; return qat_gp_train(st, m, b); }      // (`workspace`: the counters or nothing)
-// checkpoint floats of the 16-sequences-per-wave kernels of hidden 17 .. 32: the larger of gru_s16n.hip's layout and gru_s16x.hip's (a record
-// every two steps) where that file takes the model — the "s16x" / "s16x_train" knobs change between sizing and launch only with a new
-// generation, but both fit.  The split calls, the fused step and odpd_frozen_loss_dx size one buffer by it.
-inline int64_t gru_s16n_floats(const odpd_model_t* m, int B, int T) {
-    const int64_t own = gru_s16n_ckpt_floats(m, B, T), x = gru_s16x_ok(m) ? gru_s16x_ckpt_floats(m, B, T) : 0;
-    return own > x ? own : x;
-}
 inline FusedStep fused_step(const odpd_model_t* m, int B, int T) {
     const FusedStep none{nullptr, ODPD_EUNSUPPORTED, ODPD_EUNSUPPORTED, WS_UNUSED, false};
     const int r = route_of(m);
@@ -194,26 +178,60 @@ inline FusedStep fused_step(const odpd_model_t* m, int B, int T) {
     const bool float_pgjanet = r == ROUTE_REFUSED && family_of(m) == FAM_JANET && !init_state(m);
     if (r != ROUTE_NONE && !float_pgjanet) return none;
     if (const F4Backbone* f = f4_of(m)) return f->train_uses_gp(m, B, T) ? FusedStep{f->gp_train, f->gp_rows(m, B, T), 0, WS_UNUSED, true} : none;
+    const auto ws_of = [](KernelSet fused) { return fused == KS_S16 || fused == KS_S16N || fused == KS_S16X ? WS_CKPT : WS_UNUSED; };
     switch (family_of(m)) {
-    case FAM_GRU:      // every shape, from tensors and from frames: the rows are gru_family_rows' whichever kernel runs
-        if (gru_uses_s16n(m, B))
-            return {gru_s16x_train_ok(m) ? gru_s16x_step : gru_s16n_step, gru_family_rows(m, B, 1, T), gru_s16n_floats(m, B, T), WS_CKPT, true};
-        if (gru_train_uses_s16(m, B, T)) return {gru_s16_train, gru_family_rows(m, B, 1, T), gru_s16_workspace_floats(m, B, T), WS_CKPT, true};
-        return {gru_family_train, gru_family_rows(m, B, 1, T), 0, WS_UNUSED, true};
-    case FAM_LSTM:     // (the 16-sequences-per-wave kernel takes tensors only)
-        if (lstm_train_uses_s16(m, B)) return {lstm_s16_train, lstm_s16_rows(m, B), lstm_s16_workspace_floats(m, B, T), WS_CKPT, false};
-        return lstm_train_uses_gp(m, B, T) ? FusedStep{lstm_gp_train, lstm_gp_rows(m, B, T), 0, WS_UNUSED, true} : none;
-    case FAM_JANET: return janet_train_uses_gp(m, B, T) ? FusedStep{janet_gp_train, janet_gp_rows(m, B, T), 0, WS_UNUSED, true} : none;
+    case FAM_GRU: {    // every shape, from tensors and from frames (a model the family does not take: the launcher and the rows refuse, each for itself)
+        const GruPlan p = gru_plan(m, B, T, GRU_PLAN_FUSED);
+        return {gru_family_train, p.fused_rows, p.ws_floats, ws_of(p.fused), true};
+    }
+    case FAM_LSTM: {   // (the 16-sequences-per-wave kernel takes tensors only)
+        const SplitPlan p = lstm_plan(m, B, T);
+        if (p.fused == KS_NONE) return none;
+        return {p.fused == KS_S16 ? lstm_s16_train : lstm_gp_train, p.fused_rows, p.ws_floats, ws_of(p.fused), p.fused != KS_S16};
+    }
+    case FAM_JANET: {
+        const SplitPlan p = janet_plan(m, B, T);
+        return p.fused == KS_NONE ? none : FusedStep{janet_gp_train, p.fused_rows, p.ws_floats, WS_UNUSED, true};
+    }
     case FAM_DELTA: {  // (the launcher is named at every shape: odpd_train_fwd_bwd calls it without asking and lets it answer; sizes and frames ask)
-        const bool gp = delta_train_uses_gp(m, B, T);
-        return {delta_gp_train, gp ? (int64_t)delta_gp_train_rows(m, B, T) : (int64_t)ODPD_EUNSUPPORTED, gp ? 0 : (int64_t)ODPD_EUNSUPPORTED, WS_COUNTERS, gp};
+        const SplitPlan p = delta_plan(m, B, T);
+        return {delta_gp_train, p.fused_rows, p.ws_floats, WS_COUNTERS, p.fused != KS_NONE};
     }
     // (the launchers answer for a hidden size they do not take; the workspace query refuses it in front of them)
     case FAM_GMP: return {gmp_train, gmp_rows(m, B, T), odpd_param_count(m) > 0 ? 0 : (int64_t)ODPD_EUNSUPPORTED, WS_UNUSED, true};
     case FAM_RVTDCNN: return {rvtdcnn_train, rvtdcnn_train_rows(m, B, T), odpd_param_count(m) > 0 ? 0 : (int64_t)ODPD_EUNSUPPORTED, WS_UNUSED, true};
-    case FAM_QAT:      // one frame per wave at the reference's batch sizes, else forward-with-checkpoints + backward-with-loss launches of qat_s16.hip
-        if (qat_train_uses_gp(m, B, T)) return {qat_gp_step, qat_gp_train_rows(m, B, T), 0, m->backbone == ODPD_TRES_DELTAGRU ? WS_COUNTERS : WS_UNUSED, true};
-        return qat_uses_s16(m, B) ? FusedStep{qat_s16_step, qat_s16_rows(m, B), qat_s16_ckpt_floats(m, B, T), WS_CKPT, true} : none;
+    case FAM_QAT: {
+        const SplitPlan p = qat_plan(m, B, T);
+        if (p.fused == KS_NONE) return none;
+        return {qat_family_train, p.fused_rows, p.ws_floats, p.fused == KS_S16 ? WS_CKPT : m->backbone == ODPD_TRES_DELTAGRU ? WS_COUNTERS : WS_UNUSED, true};
+    }
+    default: return none;
+    }
+}
+
+// ---- the split calls (forward, backward from dL/dy) and their two buffers, resolved once per (m, B, T) ----
+struct SplitStep {
+    SeqFn fwd, bwd;           // NULL: no kernel serves the descriptor (ODPD_EUNSUPPORTED)
+    int64_t ckpt_floats;      // odpd_ckpt_floats
+    int64_t rows;             // odpd_partial_rows(fused = 0)
+    bool need_ckpt;           // a backward without checkpoints over more than one block is ODPD_EINVAL (the row-rotated kernels restart every block but the first from one)
+};
+inline SplitStep split_step(const odpd_model_t* m, int B, int T) {
+    const SplitStep none{nullptr, nullptr, ODPD_EUNSUPPORTED, ODPD_EUNSUPPORTED, false};
+    const int r = route_of(m);
+    if (r == ROUTE_REFUSED) return none;
+    if (r >= 0) return {kRoutes[r].fwd, kRoutes[r].bwd, kRoutes[r].ckpt_floats(m, B, T), kRoutes[r].rows(m, B), false};
+    if (const F4Backbone* f = f4_of(m)) return {f->fwd, f->bwd, f->ckpt_floats(m, B, T), f->rows(m, B), false};
+    const auto of = [](SeqFn fwd, SeqFn bwd, const SplitPlan& p) { return SplitStep{fwd, bwd, p.ckpt_floats, p.bwd_rows, p.need_ckpt}; };
+    switch (family_of(m)) {
+    case FAM_GRU: return of(gru_family_fwd, gru_family_bwd, gru_plan(m, B, T, GRU_PLAN_SPLIT));
+    case FAM_LSTM: return of(lstm_family_fwd, lstm_family_bwd, lstm_plan(m, B, T));
+    case FAM_DELTA: return of(delta_family_fwd, delta_family_bwd, delta_plan(m, B, T));
+    case FAM_JANET: return of(janet_family_fwd, janet_family_bwd, janet_plan(m, B, T));
+    case FAM_QAT: return of(qat_family_fwd, qat_family_bwd, qat_plan(m, B, T));
+    case FAM_TCNN: return {tcnn_fwd, tcnn_bwd, 0, tcnn_rows(m, B, T), false};      // (these three are not recurrent: nothing to checkpoint)
+    case FAM_GMP: return {gmp_fwd, gmp_bwd, 0, gmp_rows(m, B, T), false};
+    case FAM_RVTDCNN: return {rvtdcnn_fwd, rvtdcnn_bwd, 0, rvtdcnn_rows(m, B, T), false};
     default: return none;
     }
 }
@@ -347,49 +365,15 @@ extern "C" int64_t odpd_param_count(const odpd_model_t* m) {
 
 extern "C" int64_t odpd_ckpt_floats(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    const int r = route_of(m);
-    if (r != ROUTE_NONE) return r < 0 ? (int64_t)ODPD_EUNSUPPORTED : kRoutes[r].ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_TCNN || family_of(m) == FAM_GMP || family_of(m) == FAM_RVTDCNN) return 0;   // not recurrent: nothing to checkpoint
-    if (const F4Backbone* f = f4_of(m)) return f->ckpt_floats(m, B, T);
-    if (family_of(m) == FAM_QAT && qat_uses_s16(m, B)) return qat_s16_ckpt_floats(m, B, T);
-    const int R = rows_per_seq(m->hidden);
-    if (!R) return ODPD_EUNSUPPORTED;
-    switch (family_of(m)) {
-    case FAM_GRU:   // [4-sequence group][ckpt][64 lanes], or [16-sequence task][ckpt][64 lanes][4] for the S16 kernels
-        if (gru_uses_s16n(m, B)) return gru_s16n_floats(m, B, T);
-        return gru_split_uses_s16(m, B) ? (int64_t)((B + 15) / 16) * num_ckpt(T) * 256 : (int64_t)num_groups(B, R) * num_ckpt(T) * 64;
-    case FAM_LSTM: return (int64_t)num_groups(B, R) * num_ckpt(T) * 128;   // h and c
-    case FAM_DELTA:
-        if (delta_uses_s16(m, B)) return delta_s16_ckpt_floats(m, B, T);
-        return R == 1 ? (int64_t)num_groups(B, 1) * num_ckpt(T) * 7 * 64 : (int64_t)ODPD_EUNSUPPORTED;
-    case FAM_JANET:
-        if (janet_uses_s16(m, B)) return janet_s16_ckpt_floats(m, B, T);
-        return R == 1 ? (int64_t)num_groups(B, 1) * num_ckpt(T) * 64 : (int64_t)ODPD_EUNSUPPORTED;
-    case FAM_QAT: return R == 1 ? (int64_t)num_groups(B, 1) * num_ckpt(T) * 64 : (int64_t)ODPD_EUNSUPPORTED;
-    default: return ODPD_EUNSUPPORTED;
-    }
+    return split_step(m, B, T).ckpt_floats;
 }
 
 extern "C" int64_t odpd_partial_rows(const odpd_model_t* m, int B, int T, int fused) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
-    const int r = route_of(m);
-    if (r != ROUTE_NONE) return (r < 0 || fused) ? (int64_t)ODPD_EUNSUPPORTED : (int64_t)kRoutes[r].rows(m, B);      // (forward / backward only: no fused rows)
-    if (fused) {
-        const FusedStep f = fused_step(m, B, T);
-        return f.train ? f.rows : (int64_t)ODPD_EUNSUPPORTED;
-    }
-    if (const F4Backbone* f = f4_of(m)) return f->rows(m, B);
-    switch (family_of(m)) {
-    case FAM_GRU: return gru_family_rows(m, B, 0, T);
-    case FAM_LSTM: return lstm_family_rows(m, B);
-    case FAM_DELTA: return delta_family_rows(m, B, T);
-    case FAM_JANET: return janet_family_rows(m, B);
-    case FAM_TCNN: return tcnn_rows(m, B, T);
-    case FAM_GMP: return gmp_rows(m, B, T);
-    case FAM_RVTDCNN: return rvtdcnn_rows(m, B, T);
-    case FAM_QAT: return qat_uses_s16(m, B) ? (int64_t)qat_s16_rows(m, B) : (int64_t)qgru_family_rows(m, B);
-    default: return ODPD_EUNSUPPORTED;
-    }
+    if (!fused) return split_step(m, B, T).rows;
+    if (route_of(m) != ROUTE_NONE) return ODPD_EUNSUPPORTED;      // (forward / backward only: no fused rows)
+    const FusedStep f = fused_step(m, B, T);
+    return f.train ? f.rows : (int64_t)ODPD_EUNSUPPORTED;
 }
 
 extern "C" int64_t odpd_train_workspace_floats(const odpd_model_t* m, int B, int T) {
@@ -401,75 +385,45 @@ extern "C" int64_t odpd_train_workspace_floats(const odpd_model_t* m, int B, int
 extern "C" int odpd_backbone_fwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                                  const float* x, float* y, float* ckpt, double* stats) {
     if (!model_ok(m) || !params || !x || !y || B <= 0 || T <= 0) return ODPD_EINVAL;
-    const int r = route_of(m);
-    if (r == ROUTE_REFUSED) return ODPD_EUNSUPPORTED;
+    const SplitStep s = split_step(m, B, T);
+    if (!s.fwd) return ODPD_EUNSUPPORTED;
     if (init_state(m)) return ODPD_EINVAL;      // (served, but by odpd_backbone_fwd_state: this call has no h0)
-    hipStream_t st = (hipStream_t)stream;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.stats = stats;
-    if (r >= 0) return kRoutes[r].fwd(st, m, a);
-    if (const F4Backbone* f = f4_of(m)) return f->launch(st, m, a, 1);
-    switch (family_of(m)) {
-    case FAM_GRU: return gru_family_fwd(st, m, a);
-    case FAM_LSTM: return lstm_family_fwd(st, m, a);
-    case FAM_DELTA: return delta_family_fwd(st, m, a);
-    case FAM_JANET: return janet_family_fwd(st, m, a);
-    case FAM_TCNN: return tcnn_fwd(st, m, a);
-    case FAM_GMP: return gmp_fwd(st, m, a);
-    case FAM_RVTDCNN: return rvtdcnn_fwd(st, m, a);
-    case FAM_QAT:
-        if (qat_uses_gp_eval(m, B, ckpt != nullptr)) return qat_gp_eval(st, m, a);
-        return qat_uses_s16(m, B) ? qat_s16_launch(st, m, a, 1) : qgru_family_fwd(st, m, a);
-    default: return ODPD_EUNSUPPORTED;
-    }
+    return s.fwd((hipStream_t)stream, m, a);
 }
 
 extern "C" int odpd_backbone_bwd(void* stream, const odpd_model_t* m, int B, int T, const float* params,
                                  const float* x, const float* dy, const float* ckpt, float* partials, float* dx) {
     if (!model_ok(m) || !params || !x || !dy || B <= 0 || T <= 0 || (!partials && !dx)) return ODPD_EINVAL;
-    const int r = route_of(m);
-    if (r == ROUTE_REFUSED) return ODPD_EUNSUPPORTED;
+    const SplitStep s = split_step(m, B, T);
+    if (!s.bwd) return ODPD_EUNSUPPORTED;
     if (init_state(m)) return ODPD_EINVAL;      // (served, but by odpd_backbone_bwd_state)
-    hipStream_t st = (hipStream_t)stream;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx;
-    if (r >= 0) return kRoutes[r].bwd(st, m, a);
-    if (const F4Backbone* f = f4_of(m)) return f->launch(st, m, a, 2);
-    const bool no_ckpt = !ckpt && a.nck > 1;      // the row-rotated kernels restart every block but the first from a checkpoint
-    switch (family_of(m)) {
-    case FAM_GRU: return no_ckpt ? (int)ODPD_EINVAL : gru_family_bwd(st, m, a);
-    case FAM_LSTM: return no_ckpt ? (int)ODPD_EINVAL : lstm_family_bwd(st, m, a);
-    case FAM_DELTA: return no_ckpt ? (int)ODPD_EINVAL : delta_family_bwd(st, m, a);
-    case FAM_JANET: return no_ckpt ? (int)ODPD_EINVAL : janet_family_bwd(st, m, a);
-    case FAM_TCNN: return tcnn_bwd(st, m, a);
-    case FAM_GMP: return gmp_bwd(st, m, a);
-    case FAM_RVTDCNN: return rvtdcnn_bwd(st, m, a);
-    case FAM_QAT:
-        if (qat_uses_s16(m, B)) return qat_s16_launch(st, m, a, 2);      // (checks its own checkpoint count)
-        return no_ckpt ? (int)ODPD_EINVAL : qgru_family_bwd(st, m, a);
-    default: return ODPD_EUNSUPPORTED;
-    }
+    if (s.need_ckpt && !ckpt && a.nck > 1) return ODPD_EINVAL;
+    return s.bwd((hipStream_t)stream, m, a);
 }
 
 // the state route (ODPD_FLAG_INIT_STATE: route_of answers nothing but one of its two kernel sets, or ROUTE_REFUSED)
 extern "C" int odpd_backbone_fwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
                                        float* y, float* ckpt) {
     if (!model_ok(m) || !params || !x || !h0 || !y || B <= 0 || T <= 0 || !init_state(m)) return ODPD_EINVAL;
-    const int r = route_of(m);
-    if (r < 0) return ODPD_EUNSUPPORTED;
+    const SplitStep s = split_step(m, B, T);
+    if (!s.fwd) return ODPD_EUNSUPPORTED;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.y = y; a.ckpt = ckpt; a.h0 = h0;
-    return kRoutes[r].fwd((hipStream_t)stream, m, a);
+    return s.fwd((hipStream_t)stream, m, a);
 }
 extern "C" int odpd_backbone_bwd_state(void* stream, const odpd_model_t* m, int B, int T, const float* params, const float* x, const float* h0,
                                        const float* dy, const float* ckpt, float* partials, float* dx, float* dh0) {
     if (!model_ok(m) || !params || !x || !h0 || !dy || !ckpt || B <= 0 || T <= 0 || (!partials && !dx && !dh0) || !init_state(m))
         return ODPD_EINVAL;
-    const int r = route_of(m);
-    if (r < 0) return ODPD_EUNSUPPORTED;
+    const SplitStep s = split_step(m, B, T);
+    if (!s.bwd) return ODPD_EUNSUPPORTED;
     SeqArgs a = make_args(m, B, T);
     a.params = params; a.x = x; a.dy = dy; a.ckpt = const_cast<float*>(ckpt); a.partials = partials; a.dx = dx; a.h0 = h0; a.dh0 = dh0;
-    return kRoutes[r].bwd((hipStream_t)stream, m, a);
+    return s.bwd((hipStream_t)stream, m, a);
 }
 
 // `workspace` of the two fused entry points into the launch arguments, as the step's kernel takes it (WsKind)
@@ -496,7 +450,7 @@ extern "C" int odpd_train_fwd_bwd(void* stream, const odpd_model_t* m, int loss_
 extern "C" int64_t odpd_frozen_loss_rows(const odpd_model_t* m, int B, int T) {
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
     if (!gru_family_model(m)) return ODPD_EUNSUPPORTED;
-    return gru_family_lossdx_rows(m, B, T);
+    return gru_plan(m, B, T, GRU_PLAN_LOSSDX).loss_rows;
 }
 extern "C" int odpd_frozen_loss_dx(void* stream, const odpd_model_t* m, int loss_kind, int B, int T, int64_t count,
                                    const float* params, const float* u, const float* target, float* du, float* loss_rows,
@@ -879,7 +833,7 @@ extern "C" int64_t odpd_sweep_workspace_floats(const odpd_model_t* m, int B, int
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
     if (init_state(m) || quant_cell(m)) return ODPD_EUNSUPPORTED;
     if (!(flags & ODPD_SWEEP_S16)) return 0;
-    return odpd_sweep_s16_supported(m) ? gru_s16_workspace_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
+    return odpd_sweep_s16_supported(m) ? gru_s16_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
 }
 extern "C" int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int loss_kind, const odpd_frames_t* fr,
                                       int batch, int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,

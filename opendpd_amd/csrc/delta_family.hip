@@ -932,88 +932,93 @@ static int delta_launch_bwd(hipStream_t st, const SeqArgs& a, int P) {
 // the gate-parallel backward kernel: one sequence per single-wave workgroup, the frame's parked state in LDS
 static size_t delta_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + delta_gp_buffer_floats(T)) * sizeof(float); }
 static int delta_gp_blocks_per_cu(int P, int T) { return gp_blocks_per_cu(delta_gp_lds_bytes(P, T), 4); }
-static bool delta_bwd_uses_gp(const odpd_model_t* m, int B, int T) {
-    if (m->hidden > 16 || delta_uses_s16(m, B) || tuning().s16_min_batch == 0) return false;
-    const int P = delta_layout(m->hidden, m->backbone == ODPD_TRES_DELTAGRU).P;
-    return gp_batch_fits(B, delta_gp_blocks_per_cu(P, T), 1);      // every sequence resident at once
-}
-static int delta_gp_rows(const odpd_model_t* m, int B, int T) {
-    const int P = delta_layout(m->hidden, m->backbone == ODPD_TRES_DELTAGRU).P;
-    return gp_rows(B, (int)(kMaxLds / delta_gp_lds_bytes(P, T)));
-}
 template <bool TRES>
-static int delta_launch_gp_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, int P) {
-    return launch_seq(st, delta_gp_bwd_kernel<TRES>, delta_gp_rows(m, a.B, a.T), delta_gp_lds_bytes(P, a.T), a);
-}
-
-// deltajanet's home is delta_s16.hip (every batch, dL/dx, hidden <= 32); at the reference's own batch sizes — every sequence on a SIMD of its
-// own — hidden <= 16 without dL/dx takes the one-sequence-per-wave kernels: delta_eval_kernel<.., JAN> as the forward (it writes no
-// checkpoints: the backward below runs the forward again) and delta_gp_bwd_kernel<.., JAN>
-static int jan_P(const odpd_model_t* m) { return delta_layout(m->hidden, 0, 2).P; }
-static bool jan_gp_ok(const odpd_model_t* m) {
-    return m->backbone == ODPD_DELTAJANET && m->hidden <= 16 && !(m->flags & ODPD_FLAG_NEED_DX) && tuning().s16_min_batch != 0 &&
-           tuning().gp_max_batch != 0;
-}
-static bool jan_train_uses_gp(const odpd_model_t* m, int B, int T) {
-    if (!jan_gp_ok(m)) return false;
-    // up to three frames per workgroup in turn: still ahead of the 16-sequence waves there (768 x 200: 0.31 vs 0.44 ms, profiles/r03/gp_train_bench.txt)
-    return gp_batch_fits(B, delta_gp_blocks_per_cu(jan_P(m), T), 3);
-}
-static int jan_gp_rows(const odpd_model_t* m, int B, int T) {
-    return gp_rows(B, (int)(kMaxLds / delta_gp_lds_bytes(jan_P(m), T)));
+static int delta_launch_gp_bwd(hipStream_t st, const SeqArgs& a, int P, int rows) {
+    return launch_seq(st, delta_gp_bwd_kernel<TRES>, rows, delta_gp_lds_bytes(P, a.T), a);
 }
 static int jan_launch_eval(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = ((size_t)pad4(P) + kDTabFloats + kEvalChunk * 8 + kEvalChunk * kDEvalHistStride + 32) * sizeof(float);
     return launch_seq(st, delta_eval_kernel<false, false, true>, a.B, lds, a);
 }
 // ---- fused train step at the reference's batch sizes (one frame per single-wave workgroup): delta_gp_bwd_kernel<.., FUSED> ----
-bool delta_train_uses_gp(const odpd_model_t* m, int B, int T) {
-    if (m->flags & ODPD_FLAG_NEED_DX) return false;
-    if (m->backbone == ODPD_DELTAJANET) return jan_train_uses_gp(m, B, T);
-    if (m->backbone != ODPD_DELTAGRU && m->backbone != ODPD_TRES_DELTAGRU) return false;
-    return delta_bwd_uses_gp(m, B, T);
-}
-int delta_gp_train_rows(const odpd_model_t* m, int B, int T) {
-    return m->backbone == ODPD_DELTAJANET ? jan_gp_rows(m, B, T) : delta_gp_rows(m, B, T);
-}
 // a.stats: the four sparsity counters of the step's forward pass (nullable); a.x / a.target: (B,T,2) tensors or frames of resident streams
 int delta_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (!delta_train_uses_gp(m, a.B, a.T)) return ODPD_EUNSUPPORTED;
-    const bool jan = m->backbone == ODPD_DELTAJANET, tres = m->backbone == ODPD_TRES_DELTAGRU;
-    const int P = jan ? jan_P(m) : delta_layout(m->hidden, tres).P;
-    const size_t lds = delta_gp_lds_bytes(P, a.T);
-    auto launch = [&](auto k) { return launch_seq(st, k, delta_gp_train_rows(m, a.B, a.T), lds, a); };
-    if (jan) return launch(delta_gp_bwd_kernel<false, true, true>);
-    return tres ? launch(delta_gp_bwd_kernel<true, false, true>) : launch(delta_gp_bwd_kernel<false, false, true>);
+    const SplitPlan p = delta_plan(m, a.B, a.T);
+    if (p.fused != KS_GP) return ODPD_EUNSUPPORTED;
+    const size_t lds = delta_gp_lds_bytes(p.P, a.T);
+    auto launch = [&](auto k) { return launch_seq(st, k, (int)p.fused_rows, lds, a); };
+    if (m->backbone == ODPD_DELTAJANET) return launch(delta_gp_bwd_kernel<false, true, true>);
+    return m->backbone == ODPD_TRES_DELTAGRU ? launch(delta_gp_bwd_kernel<true, false, true>) : launch(delta_gp_bwd_kernel<false, false, true>);
 }
 int delta_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (jan_gp_ok(m) && ((a.ckpt == nullptr && a.B <= 2 * device_cus()) || (a.ckpt != nullptr && jan_train_uses_gp(m, a.B, a.T))))
-        return jan_launch_eval(st, a, jan_P(m));
-    if (delta_uses_s16(m, a.B)) return delta_s16_launch(st, m, a, 1);
-    if (m->hidden > 16) return ODPD_EUNSUPPORTED;
+    const SplitPlan p = delta_plan(m, a.B, a.T);
     const bool tres = m->backbone == ODPD_TRES_DELTAGRU;
-    const int P = delta_layout(m->hidden, tres).P;
-    if (gp_eval_batch_fits(a.B))          // sequences that each get a SIMD of their own (inference / checkpoint-writing forward)
-        return tres ? delta_launch_eval<true>(st, a, P) : delta_launch_eval<false>(st, a, P);
-    return tres ? delta_launch_fwd<true>(st, a, P) : delta_launch_fwd<false>(st, a, P);
+    switch (p.fwd(a)) {
+    case KS_S16: return delta_s16_launch(st, m, a, 1);
+    case KS_EVAL:      // (deltajanet: it writes no checkpoints — its backward, KS_GP, runs the forward again)
+        if (m->backbone == ODPD_DELTAJANET) return jan_launch_eval(st, a, p.P);
+        return tres ? delta_launch_eval<true>(st, a, p.P) : delta_launch_eval<false>(st, a, p.P);
+    case KS_ROT: return tres ? delta_launch_fwd<true>(st, a, p.P) : delta_launch_fwd<false>(st, a, p.P);
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
 int delta_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (a.dx == nullptr && a.partials != nullptr && jan_train_uses_gp(m, a.B, a.T))
-        return launch_seq(st, delta_gp_bwd_kernel<false, true>, jan_gp_rows(m, a.B, a.T), delta_gp_lds_bytes(jan_P(m), a.T), a);
-    if (delta_uses_s16(m, a.B)) return delta_s16_launch(st, m, a, 2);
-    if (m->hidden > 16) return ODPD_EUNSUPPORTED;
+    const SplitPlan p = delta_plan(m, a.B, a.T);
     const bool tres = m->backbone == ODPD_TRES_DELTAGRU;
-    const int P = delta_layout(m->hidden, tres).P;
-    if (a.dx == nullptr && a.partials != nullptr && delta_bwd_uses_gp(m, a.B, a.T))
-        return tres ? delta_launch_gp_bwd<true>(st, m, a, P) : delta_launch_gp_bwd<false>(st, m, a, P);
-    return tres ? delta_launch_bwd<true>(st, a, P) : delta_launch_bwd<false>(st, a, P);
+    switch (p.bwd(a)) {
+    case KS_GP:
+        if (m->backbone == ODPD_DELTAJANET) return launch_seq(st, delta_gp_bwd_kernel<false, true>, (int)p.bwd_rows, delta_gp_lds_bytes(p.P, a.T), a);
+        return tres ? delta_launch_gp_bwd<true>(st, a, p.P, (int)p.bwd_rows) : delta_launch_gp_bwd<false>(st, a, p.P, (int)p.bwd_rows);
+    case KS_S16: return delta_s16_launch(st, m, a, 2);
+    case KS_ROT: return tres ? delta_launch_bwd<true>(st, a, p.P) : delta_launch_bwd<false>(st, a, p.P);
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
-int delta_family_rows(const odpd_model_t* m, int B, int T) {
-    if (jan_train_uses_gp(m, B, T)) return jan_gp_rows(m, B, T);
-    if (delta_uses_s16(m, B)) return delta_s16_rows(m, B);
-    if (m->hidden > 16) return ODPD_EUNSUPPORTED;
-    if (delta_bwd_uses_gp(m, B, T)) return delta_gp_rows(m, B, T);
-    return delta_bwd_shape(num_groups(B, 1)).grid;
+
+// Every crossover of the delta backbones.  deltagru / deltagru_tcnskip of hidden <= 16: the row-rotated kernels, the evaluation kernel for
+// the forward of batches whose sequences each get a SIMD of their own, the gate-parallel backward (weight gradients alone) while every
+// sequence is resident at once; delta_s16.hip from the batch that fills the chip, at hidden 17 .. 32 and with ODPD_FLAG_NEED_DX (delta_uses_s16).
+// deltajanet's home is delta_s16.hip (every batch, dL/dx, hidden <= 32); at the reference's own batch sizes — every sequence on a SIMD of its
+// own — hidden <= 16 without dL/dx takes the one-sequence-per-wave kernels: delta_eval_kernel<.., JAN> as the forward and
+// delta_gp_bwd_kernel<.., JAN>, up to three frames per workgroup in turn: still ahead of the 16-sequence waves there (768 x 200: 0.31 vs
+// 0.44 ms, profiles/r03/gp_train_bench.txt).  The fused train step is the gate-parallel backward's kernel with FUSED set: same shapes, same rows.
+SplitPlan delta_plan(const odpd_model_t* m, int B, int T) {
+    SplitPlan p{};
+    p.need_ckpt = true;
+    const bool jan = m->backbone == ODPD_DELTAJANET, s16 = delta_uses_s16(m, B), small = m->hidden <= 16;
+    const int R = rows_per_seq(m->hidden);
+    p.P = jan ? delta_layout(m->hidden, 0, 2).P : delta_layout(m->hidden, m->backbone == ODPD_TRES_DELTAGRU).P;
+    const Tuning& tn = tuning();
+    const bool jan_ok = jan && small && !(m->flags & ODPD_FLAG_NEED_DX) && tn.s16_min_batch != 0 && tn.gp_max_batch != 0;
+    const int gp_per_cu = small ? delta_gp_blocks_per_cu(p.P, T) : 0;
+    const bool jan_gp = jan_ok && gp_batch_fits(B, gp_per_cu, 3);
+    const bool bwd_gp = small && !s16 && tn.s16_min_batch != 0 && gp_batch_fits(B, gp_per_cu, 1);      // every sequence resident at once
+    // the kernels below deltajanet's one-sequence-per-wave pair: delta_s16.hip, else (hidden <= 16) this file's, else none
+    const bool rot = !s16 && small;
+    const KernelSet rest = s16 ? KS_S16 : rot ? KS_ROT : KS_NONE;
+    const bool eval_fits = rot && gp_eval_batch_fits(B);      // the evaluation kernel as the forward: sequences that each get a SIMD of their own
+    // (kept: the checkpoint query refuses hidden > 32 itself and does not know deltajanet's evaluation forward; the rows leave hidden > 32 to delta_s16_rows)
+    if (!R) p.ckpt_floats = ODPD_EUNSUPPORTED;
+    else if (s16) p.ckpt_floats = delta_s16_ckpt_floats(m, B, T);
+    else p.ckpt_floats = R == 1 ? (int64_t)num_groups(B, 1) * num_ckpt(T) * 7 * 64 : (int64_t)ODPD_EUNSUPPORTED;
+    // (kept: deltajanet's forward without checkpoints asks for a SIMD per sequence and no frame length; with them, for what its backward asks)
+    const bool jan_eval = jan_ok && B <= 2 * device_cus();
+    p.fwd_eval = jan_eval || eval_fits ? KS_EVAL : rest;
+    p.fwd_ckpt = jan_gp || eval_fits ? KS_EVAL : rest;
+    const bool gp = jan_gp || (rot && bwd_gp);      // weight gradients alone on the gate-parallel kernel; the fused step is that kernel with FUSED set
+    p.bwd_w = gp ? KS_GP : rest;
+    p.bwd_dx = p.bwd_wdx = rest;      // (the row-rotated kernels have no dL/dx: delta_launch_bwd refuses)
+    p.fused = gp ? KS_GP : KS_NONE;
+    p.fused_rows = p.ws_floats = ODPD_EUNSUPPORTED;
+    if (gp) {
+        p.bwd_rows = p.fused_rows = gp_rows(B, (int)(kMaxLds / delta_gp_lds_bytes(p.P, T)));
+        p.ws_floats = 0;
+    } else if (s16) {
+        p.bwd_rows = delta_s16_rows(m, B);
+    } else {
+        p.bwd_rows = rot ? delta_bwd_shape(num_groups(B, 1)).grid : ODPD_EUNSUPPORTED;
+    }
+    return p;
 }
 
 }  // namespace odpd

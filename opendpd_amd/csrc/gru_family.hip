@@ -26,6 +26,8 @@
 // frames, the evaluation segments): the four 16-lane rows of a wave take one gate each, only the recurrence stays in the step loop:
 //   gru_eval_kernel      forward (inference; CK: also the checkpoint-writing forward of the split train path)
 //   gru_gp_train_kernel  fused train step with the frame's BPTT state in LDS and the weight gradients as 4-block MFMAs
+#include <algorithm>
+
 #include "odpd_gru.h"
 
 namespace odpd {
@@ -1269,15 +1271,6 @@ __global__ __launch_bounds__(64) void gru_gp_train_sweep_kernel(SeqArgs a, const
 constexpr int kFwdWavesPerCU = 16;  // 4 waves per SIMD (forward kernels use <= 128 VGPRs for R = 1)
 static int bwd_waves_per_cu(int R) { return R == 1 ? 8 : 4; }
 
-static bool gru_cfg(const odpd_model_t* m, int& FM, bool& DG) {
-    switch (m->backbone) {
-    case ODPD_GRU: FM = FEAT_RAW2; DG = false; return true;
-    case ODPD_DGRU: FM = FEAT_DGRU6; DG = true; return true;
-    case ODPD_QGRU: FM = FEAT_Q4; DG = false; return true;
-    case ODPD_QGRU_AMP1: FM = FEAT_A4; DG = false; return true;
-    default: return false;
-    }
-}
 static int gru_tab_floats(int R, bool DG) { return (DG ? 8 * R : 6 * R) * 4 * 64 * 4; }
 // dynamic LDS of a block: params + tables + per-wave region; never smaller than the reduce scratch
 static size_t gru_lds_bytes(int P, int R, bool DG, int waves, size_t wave_floats, bool reduce) {
@@ -1366,29 +1359,6 @@ static int launch_bwd_mode(hipStream_t st, const SeqArgs& a, int P) {
     return ODPD_EINVAL;
 }
 
-static bool gru_setup(const odpd_model_t* m, int& FM, bool& DG, int& R, int& P) {
-    if (!gru_cfg(m, FM, DG)) return false;
-    R = rows_per_seq(m->hidden);
-    if (!R) return false;
-    P = gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
-    return true;
-}
-
-// hidden 17..32: the generic-tile S16 kernels (gru_s16n.hip) take over from the two-row DPP kernels at the same batch
-bool gru_uses_s16n(const odpd_model_t* m, int B) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || R != 2) return false;
-    return B >= s16_min_batch_or(8L * 4 * device_cus());    // measured crossover (DGRU-23, T = 200): 1.54 vs 1.33 ms at 8192
-}
-
-// The split kernels switch to the 16-sequences-per-wave mapping at the same batch size as the fused one.  Forward
-// and backward of one (B,T) batch must agree (checkpoint layout), so the rule only looks at the model and B.
-bool gru_split_uses_s16(const odpd_model_t* m, int B) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || R != 1) return false;
-    return B >= s16_min_batch_or(16L * 4 * device_cus());
-}
-
 // inference on a few long sequences (no checkpoints asked for): the gate-parallel evaluation kernel, one sequence per wave
 template <int NB, int FM, bool DG>
 static int launch_eval(hipStream_t st, const SeqArgs& a, int P) {
@@ -1397,41 +1367,36 @@ static int launch_eval(hipStream_t st, const SeqArgs& a, int P) {
         if (a.H <= 24) return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, gru_eval_kernel<NB, FM, DG, sv(), true>, a.B, lds, a); });
     return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, gru_eval_kernel<NB, FM, DG, sv()>, a.B, lds, a); });
 }
-bool gru_uses_eval_kernel(const odpd_model_t* m, int B, int T, bool want_ckpt) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || tuning().s16_min_batch == 0 || tuning().gp_max_batch == 0) return false;
-    // a few long sequences (net_eval / run_dpd), or any batch whose sequences each get a SIMD of their own before the S16 kernels take over
-    // (then also as the checkpoint-writing forward of the split train path)
-    return (!want_ckpt && B <= 8 && T >= 256) || (gp_eval_batch_fits(B) && !gru_split_uses_s16(m, B) && !gru_uses_s16n(m, B));
-}
 int gru_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_uses_eval_kernel(m, a.B, a.T, a.ckpt != nullptr)) return gru_nb_dispatch(R, FM, [&](auto nb, auto fm, auto dg) { return launch_eval<nb(), fm(), dg()>(st, a, P); });
-    if (gru_split_uses_s16(m, a.B)) return gru_s16_fwd(st, m, a);
-    if (gru_uses_s16n(m, a.B)) return gru_s16x_train_ok(m) ? gru_s16x_fwd(st, m, a) : gru_s16n_launch(st, m, a, 1);
-    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_fwd<r(), fm(), dg()>(st, a, P); });
+    const GruPlan p = gru_plan(m, a.B, a.T, GRU_PLAN_SPLIT);
+    const int P = p.P;
+    switch (p.fwd(a)) {
+    case KS_EVAL: return gru_nb_dispatch(p.R, p.FM, [&](auto nb, auto fm, auto dg) { return launch_eval<nb(), fm(), dg()>(st, a, P); });
+    case KS_S16: return gru_s16_fwd(st, m, a);
+    case KS_S16X: return gru_s16x_fwd(st, m, a);
+    case KS_S16N: return gru_s16n_launch(st, m, a, 1);
+    case KS_ROT: return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_fwd<r(), fm(), dg()>(st, a, P); });
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
-static bool gru_bwd_uses_gp(const odpd_model_t* m, int B, int T);
-static int gp_grid(int P, int R, bool DG, int B, int T);
 template <int R, int FM, bool DG>
 static int launch_gp_train(hipStream_t st, const SeqArgs& a, int P);
 int gru_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_split_uses_s16(m, a.B)) return gru_s16_bwd(st, m, a);
-    if (gru_uses_s16n(m, a.B)) return gru_s16x_train_ok(m) ? gru_s16x_bwd(st, m, a, gru_s16n_rows(m, a.B)) : gru_s16n_launch(st, m, a, 2);
-    if (gru_bwd_uses_gp(m, a.B, a.T)) {
-        // weight gradients only: the fused one-sequence-per-wave kernel with dL/dy given (it runs its own forward; the checkpoints stay unread)
-        if (a.partials != nullptr && a.dx == nullptr) return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_gp_train<r(), fm(), dg()>(st, a, P); });
-        // dL/dx asked for: the row-rotated kernel writes fewer rows than the caller's buffer holds — the rest are zero
-        if (a.partials != nullptr) {
-            const int have = bwd_shape(R, a.ngroups).grid, rows = gp_grid(P, R, DG, a.B, a.T);
-            if (rows > have)
-                ODPD_CHECK_HIP(hipMemsetAsync(a.partials + (size_t)have * (P + kLossCols), 0, (size_t)(rows - have) * (P + kLossCols) * sizeof(float), st));
-        }
+    const GruPlan p = gru_plan(m, a.B, a.T, GRU_PLAN_SPLIT);
+    const int P = p.P;
+    switch (p.bwd(a)) {
+    case KS_S16: return gru_s16_bwd(st, m, a);
+    case KS_S16X: return gru_s16x_bwd(st, m, a, (int)p.bwd_rows);
+    case KS_S16N: return gru_s16n_launch(st, m, a, 2);
+    // weight gradients only: the fused one-sequence-per-wave kernel with dL/dy given (it runs its own forward; the checkpoints stay unread)
+    case KS_GP: return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_gp_train<r(), fm(), dg()>(st, a, P); });
+    case KS_ROT:
+        // with dL/dx, where weight gradients alone go to KS_GP: the row-rotated kernel writes fewer rows than the caller's buffer holds — the rest are zero
+        if (a.partials != nullptr && a.dx != nullptr && p.bwd_rows > p.rot_rows)
+            ODPD_CHECK_HIP(hipMemsetAsync(a.partials + (size_t)p.rot_rows * (P + kLossCols), 0, (size_t)(p.bwd_rows - p.rot_rows) * (P + kLossCols) * sizeof(float), st));
+        return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_bwd_mode<r(), fm(), dg()>(st, a, P); });
+    default: return ODPD_EUNSUPPORTED;
     }
-    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_bwd_mode<r(), fm(), dg()>(st, a, P); });
 }
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, BPTT state of the whole frame in LDS
 static size_t gp_lds_bytes(int P, int R, bool DG, int T, bool pg) {
@@ -1443,17 +1408,6 @@ static size_t gp_lds_bytes(int P, int R, bool DG, int T, bool pg) {
 static int gp_blocks_per_cu(int P, int R, bool DG, int T, bool pg) { return odpd::gp_blocks_per_cu(gp_lds_bytes(P, R, DG, T, pg), 4); }
 // the variant that parks the gates is taken while every sequence of the batch still gets its own SIMD
 static bool gp_parks_gates(int P, int R, bool DG, int B, int T) { return (long)B <= (long)device_cus() * gp_blocks_per_cu(P, R, DG, T, true); }
-bool gru_train_uses_gp(const odpd_model_t* m, int B, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || gru_uses_s16n(m, B) || gru_train_uses_s16(m, B, T)) return false;
-    return gp_batch_fits(B, gp_blocks_per_cu(P, R, DG, T, false), 1);        // one sequence per SIMD, all resident at once
-}
-// the split backward (dL/dy given) on the same kernel: hidden <= 16, every sequence resident at once
-static bool gru_bwd_uses_gp(const odpd_model_t* m, int B, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || R != 1 || gru_split_uses_s16(m, B) || tuning().gp_max_batch == 0 || tuning().s16_min_batch == 0) return false;
-    return (long)B <= (long)device_cus() * gp_blocks_per_cu(P, R, DG, T, false);
-}
 static int gp_grid(int P, int R, bool DG, int B, int T) {
     const bool pg = gp_parks_gates(P, R, DG, B, T);
     return gp_rows(B, (int)(kMaxLds / gp_lds_bytes(P, R, DG, T, pg)));
@@ -1469,12 +1423,8 @@ static int launch_gp_train(hipStream_t st, const SeqArgs& a, int P) {
     return pg ? launch(gru_gp_train_kernel<R, FM, DG, true>) : launch(gru_gp_train_kernel<R, FM, DG, false>);
 }
 // ---- lockstep sweeps: K runs of one model shape, each exactly the solo launch it replaces (same instantiation, same grid per run) ----
-bool gru_sweep_train_ok(const odpd_model_t* m, int B, int T) { return m->bits_w == 0 && gru_train_uses_gp(m, B, T); }
-int gru_sweep_train_rows(const odpd_model_t* m, int B, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || !gru_sweep_train_ok(m, B, T)) return ODPD_EUNSUPPORTED;
-    return gp_grid(P, R, DG, B, T);
-}
+bool gru_sweep_train_ok(const odpd_model_t* m, int B, int T) { return m->bits_w == 0 && gru_plan(m, B, T, GRU_PLAN_FUSED).fused == KS_GP; }
+int gru_sweep_train_rows(const odpd_model_t* m, int B, int T) { return gru_sweep_train_ok(m, B, T) ? (int)gru_plan(m, B, T, GRU_PLAN_FUSED).fused_rows : ODPD_EUNSUPPORTED; }
 template <int R, int FM, bool DG>
 static int launch_gp_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepRun* runs, int K, long long first) {
     const bool pg = gp_parks_gates(P, R, DG, a.B, a.T);
@@ -1486,11 +1436,12 @@ static int launch_gp_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepR
     return pg ? launch(gru_gp_train_sweep_kernel<R, FM, DG, true, false>) : launch(gru_gp_train_sweep_kernel<R, FM, DG, false, false>);
 }
 int gru_sweep_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, const SweepRun* runs, int K, long long first) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || !gru_sweep_train_ok(m, a.B, a.T) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
-    return gru_nb_dispatch(R, FM, [&](auto nb, auto fm, auto dg) { return launch_gp_sweep<nb(), fm(), dg()>(st, a, P, runs, K, first); });
+    const GruPlan p = gru_plan(m, a.B, a.T, GRU_PLAN_FUSED);
+    const int P = p.P;
+    if (m->bits_w != 0 || p.fused != KS_GP || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
+    return gru_nb_dispatch(p.R, p.FM, [&](auto nb, auto fm, auto dg) { return launch_gp_sweep<nb(), fm(), dg()>(st, a, P, runs, K, first); });
 }
-bool gru_sweep_eval_ok(const odpd_model_t* m, int B, int T) { return m->bits_w == 0 && gru_uses_eval_kernel(m, B, T, false); }
+bool gru_sweep_eval_ok(const odpd_model_t* m, int B, int T) { return m->bits_w == 0 && gru_plan(m, B, T, GRU_PLAN_SPLIT).fwd_eval == KS_EVAL; }
 template <int NB, int FM, bool DG>
 static int launch_eval_sweep(hipStream_t st, const SeqArgs& a, int P, const SweepRun* runs, int K) {
     const size_t lds = ((size_t)pad4(P) + GruTabs<NB, DG>::kFloats + GruEvalLds<NB>::kFloats) * sizeof(float);
@@ -1500,9 +1451,10 @@ static int launch_eval_sweep(hipStream_t st, const SeqArgs& a, int P, const Swee
     return launch_seq(st, gru_eval_sweep_kernel<NB, FM, DG, false>, G * K, lds, a, runs, G);
 }
 int gru_sweep_eval(hipStream_t st, const odpd_model_t* m, const SeqArgs& a, const SweepRun* runs, int K) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || !gru_sweep_eval_ok(m, a.B, a.T) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
-    return gru_nb_dispatch(R, FM, [&](auto nb, auto fm, auto dg) { return launch_eval_sweep<nb(), fm(), dg()>(st, a, P, runs, K); });
+    const GruPlan p = gru_plan(m, a.B, a.T, GRU_PLAN_SPLIT);
+    const int P = p.P;
+    if (m->bits_w != 0 || p.fwd_eval != KS_EVAL || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
+    return gru_nb_dispatch(p.R, p.FM, [&](auto nb, auto fm, auto dg) { return launch_eval_sweep<nb(), fm(), dg()>(st, a, P, runs, K); });
 }
 // the frozen-model variant (forward + loss + dL/dx): taken while every sequence of the batch is resident at once
 static size_t gp_fz_lds_bytes(int P, int R, bool DG, int T) {
@@ -1517,16 +1469,6 @@ static int gp_fz_grid(int P, int R, bool DG, int B, int T) {
     const long cap = (long)device_cus() * (per_cu < 4 ? per_cu : 4);
     return B <= cap ? B : 0;
 }
-static bool gru_lossdx_uses_gp(const odpd_model_t* m, int B, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || gru_uses_s16n(m, B) || gru_split_uses_s16(m, B)) return false;
-    // hidden 25..32 without the fc_hid head: the two-block steps leave nothing to gain over the row-rotated kernel (0.97x measured,
-    // profiles/r03/frozen_pa_bench.md); 17..24 (second block held twice, 8-rotation dot products) 1.07x, with the head 1.2-1.3x, hidden <= 16 1.35-1.85x
-    if (R == 2 && !DG && m->hidden > 24 && tuning().gp_max_batch < 0) return false;
-    const long max_batch = tuning().gp_max_batch;
-    if (max_batch >= 0 && B > max_batch) return false;
-    return gp_fz_grid(P, R, DG, B, T) > 0;
-}
 template <int R, int FM, bool DG>
 static int launch_gp_lossdx(hipStream_t st, const SeqArgs& a, int P) {
     const size_t lds = gp_fz_lds_bytes(P, R, DG, a.T);
@@ -1535,58 +1477,110 @@ static int launch_gp_lossdx(hipStream_t st, const SeqArgs& a, int P) {
         if (a.H <= 24) return launch_seq(st, gru_gp_train_kernel<R, FM, DG, false, true, true>, grid, lds, a);
     return launch_seq(st, gru_gp_train_kernel<R, FM, DG, false, true>, grid, lds, a);
 }
+// the fused train step: a.ckpt = the workspace of gru_plan's ws_floats (the 16-sequences-per-wave kernels)
 int gru_family_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_train_uses_gp(m, a.B, a.T)) return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_gp_train<r(), fm(), dg()>(st, a, P); });
-    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_train<r(), fm(), dg()>(st, a, P); });
+    const GruPlan p = gru_plan(m, a.B, a.T, GRU_PLAN_FUSED);
+    const int P = p.P;
+    switch (p.fused) {
+    case KS_S16X: return gru_s16x_train(st, m, a, (int)p.fused_rows);
+    case KS_S16N: return gru_s16n_launch(st, m, a, 0);
+    case KS_S16: return gru_s16_train(st, m, a);
+    case KS_GP: return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_gp_train<r(), fm(), dg()>(st, a, P); });
+    case KS_ROT: return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_train<r(), fm(), dg()>(st, a, P); });
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
 // frozen PA of a cascade: forward + loss + dL/du in one launch; loss rows = (rows, kLossCols)
 int gru_family_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_uses_s16n(m, a.B)) return gru_s16x_ok(m) ? gru_s16x_lossdx(st, m, a, gru_s16n_rows(m, a.B)) : gru_s16n_launch(st, m, a, 3);
-    if (gru_split_uses_s16(m, a.B)) return gru_s16_lossdx(st, m, a);
-    if (gru_lossdx_uses_gp(m, a.B, a.T)) return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_gp_lossdx<r(), fm(), dg()>(st, a, P); });
-    return gru_dispatch(R, FM, [&](auto r, auto fm, auto dg) { return launch_lossdx<r(), fm(), dg()>(st, a, P); });
-}
-int gru_family_lossdx_rows(const odpd_model_t* m, int B, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    if (gru_uses_s16n(m, B)) return gru_s16n_rows(m, B);
-    if (gru_split_uses_s16(m, B)) return gru_s16_rows(m, B);
-    if (gru_lossdx_uses_gp(m, B, T)) return gp_fz_grid(P, R, DG, B, T);
-    const LaunchShape ls = train_shape(P, R, DG, num_groups(B, R), T, nullptr, true);
-    return ls.grid > 0 ? ls.grid : ODPD_EUNSUPPORTED;      // frame too long for LDS-resident BPTT state: use the split calls
-}
-// rows of partials written by the backward (which = 0) or fused (which = 1, needs T) kernels
-int gru_family_rows(const odpd_model_t* m, int B, int which, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P)) return ODPD_EUNSUPPORTED;
-    const int ng = num_groups(B, R);
-    if (gru_uses_s16n(m, B)) return gru_s16n_rows(m, B);
-    if (!which) {
-        if (gru_split_uses_s16(m, B)) return gru_s16_bwd_rows(m, B);
-        const int have = bwd_shape(R, ng).grid;
-        if (gru_bwd_uses_gp(m, B, T)) { const int rows = gp_grid(P, R, DG, B, T); return rows > have ? rows : have; }
-        return have;
+    const GruPlan p = gru_plan(m, a.B, a.T, GRU_PLAN_LOSSDX);
+    const int P = p.P;
+    switch (p.lossdx) {
+    case KS_S16X: return gru_s16x_lossdx(st, m, a, (int)p.loss_rows);
+    case KS_S16N: return gru_s16n_launch(st, m, a, 3);
+    case KS_S16: return gru_s16_lossdx(st, m, a);
+    case KS_GP: return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_gp_lossdx<r(), fm(), dg()>(st, a, P); });
+    case KS_ROT: return gru_dispatch(p.R, p.FM, [&](auto r, auto fm, auto dg) { return launch_lossdx<r(), fm(), dg()>(st, a, P); });
+    default: return ODPD_EUNSUPPORTED;
     }
-    if (gru_train_uses_s16(m, B, T)) return gru_s16_rows(m, B);
-    if (gru_train_uses_gp(m, B, T)) return gp_grid(P, R, DG, B, T);
-    const LaunchShape ls = train_shape(P, R, DG, ng, T, nullptr);
-    return ls.grid > 0 ? ls.grid : ODPD_EUNSUPPORTED;
 }
 
-// Which fused kernel serves a (B,T) batch: the row-rotated kernel (4 sequences per wave, BPTT state in LDS)
-// has the shorter per-step latency and wins while the batch cannot fill the chip with 16-sequence waves; the
-// S16 kernel (gru_s16.hip) has ~1.7x the throughput once it can, and no frame-length limit.
-// odpd_set_tuning("s16_min_batch") / $ODPD_S16_MIN_BATCH override the crossover (0 = always S16 where
-// supported, a huge value = never).
-bool gru_train_uses_s16(const odpd_model_t* m, int B, int T) {
-    int FM, R, P; bool DG;
-    if (!gru_setup(m, FM, DG, R, P) || R != 1) return false;
-    if (B >= s16_min_batch_or(16L * 4 * device_cus())) return true;   // one 16-sequence wave per SIMD
-    return train_shape(P, R, DG, num_groups(B, R), T, nullptr).grid <= 0;   // frame too long for LDS checkpoints
+// Every crossover of the float GRU family.  Hidden <= 16 (R = 1): the row-rotated kernels (4 sequences per wave, BPTT state of the fused
+// kernels in LDS) have the shorter per-step latency and win while the batch cannot fill the chip with 16-sequence waves; the S16 kernels
+// (gru_s16.hip) have ~1.7x the throughput once it can — one 16-sequence wave per SIMD — and no frame-length limit.  Hidden 17 .. 32 (R = 2):
+// the generic-tile S16 kernels (gru_s16n.hip; 17 .. 24 on the bf16 matrix pipe where the "s16x" / "s16x_train" knobs allow: gru_s16x.hip)
+// take over from the two-row kernels at half that batch (measured, DGRU-23, T = 200: 1.54 vs 1.33 ms at 8192).  Below those crossovers the
+// one-sequence-per-wave kernels serve the batches whose sequences each get a SIMD of their own.  odpd_set_tuning("s16_min_batch") /
+// $ODPD_S16_MIN_BATCH override the crossover (0 = always S16 where supported, a huge value = never), "gp_max_batch" the gate-parallel bound.
+// Forward and backward of one (B, T) batch must agree on the checkpoint layout, so every rule of the split calls looks at the model and B alone.
+GruPlan gru_plan(const odpd_model_t* m, int B, int T, int parts) {
+    GruPlan p{};
+    p.need_ckpt = true;
+    p.ckpt_floats = p.bwd_rows = p.fused_rows = p.loss_rows = ODPD_EUNSUPPORTED;
+    // (kept: odpd_train_workspace_floats answers 0, not a refusal, where the fused rows are refused — a model the family does not take, a frame
+    // too long for the row-rotated kernel's LDS-resident state at hidden 17 .. 32)
+    p.ws_floats = 0;
+    if (!gru_cfg(m, p.FM, p.DG) || !(p.R = rows_per_seq(m->hidden))) return p;
+    const int R = p.R, ng = num_groups(B, R), P = p.P = gru_param_count(m->hidden, p.FM, p.DG);
+    const bool DG = p.DG;
+    const Tuning& tn = tuning();
+    const bool knobs_free = tn.s16_min_batch != 0 && tn.gp_max_batch != 0;      // neither knob pins another path
+    const bool s16n = R == 2 && B >= s16_min_batch_or(8L * 4 * device_cus());
+    const bool s16 = R == 1 && B >= s16_min_batch_or(16L * 4 * device_cus());
+    // what the 16-sequences-per-wave side of the split calls and of the fused step is, and the row-rotated side below it
+    const KernelSet big = s16 ? KS_S16 : !s16n ? KS_ROT : gru_s16x_train_ok(m) ? KS_S16X : KS_S16N;
+    // hidden 17 .. 32, 16 sequences per wave: the larger of gru_s16n.hip's layout and gru_s16x.hip's (a record every two steps) where that file
+    // takes the model — the "s16x" / "s16x_train" knobs change between sizing and launch only with a new generation, but both fit
+    const auto s16n_floats = [&] { return std::max(gru_s16n_ckpt_floats(m, B, T), gru_s16x_ok(m) ? gru_s16x_ckpt_floats(m, B, T) : (int64_t)0); };
+
+    if (parts & GRU_PLAN_SPLIT) {
+        // checkpoints: [16-sequence task][ckpt][64 lanes][4] (gru_s16.hip), or [4-sequence group][ckpt][64 lanes]
+        p.ckpt_floats = s16n ? s16n_floats() : s16 ? gru_s16_ckpt_floats(m, B, T) : (int64_t)ng * num_ckpt(T) * 64;
+        // the evaluation kernel: any batch whose sequences each get a SIMD of their own before the S16 kernels take over (then also as the
+        // checkpoint-writing forward of the split train path) ...
+        const bool eval = big == KS_ROT && knobs_free && gp_eval_batch_fits(B);
+        p.fwd_ckpt = eval ? KS_EVAL : big;
+        // ... and a few long sequences (net_eval / run_dpd) that want no checkpoints (kept: this clause does not ask the S16 crossovers)
+        p.fwd_eval = eval || (knobs_free && B <= 8 && T >= 256) ? KS_EVAL : big;
+        // weight gradients alone (dL/dy given) on the fused gate-parallel kernel: hidden <= 16, every sequence resident at once.  The caller
+        // sizes one buffer for whatever the launch asks for, so the rows are the larger of the two grids (gru_family_bwd zeroes the surplus)
+        const bool bwd_gp = R == 1 && !s16 && knobs_free && (long)B <= (long)device_cus() * gp_blocks_per_cu(P, R, DG, T, false);
+        p.bwd_w = bwd_gp ? KS_GP : big;
+        p.bwd_dx = p.bwd_wdx = big;
+        p.rot_rows = bwd_shape(R, ng).grid;
+        p.bwd_rows = s16n ? gru_s16n_rows(m, B) : s16 ? gru_s16_bwd_rows(m, B) : bwd_gp ? std::max(gp_grid(P, R, DG, B, T), p.rot_rows) : p.rot_rows;
+    }
+    if (parts & GRU_PLAN_FUSED) {
+        // S16 also where the frame is too long for the row-rotated kernel's LDS checkpoints; gate-parallel with one sequence per SIMD, all resident at once
+        const int rot_grid = big == KS_ROT ? train_shape(P, R, DG, ng, T, nullptr).grid : 0;
+        const bool too_long = R == 1 && rot_grid <= 0;
+        if (big != KS_ROT) p.fused = big;
+        else if (too_long) p.fused = KS_S16;
+        else p.fused = gp_batch_fits(B, gp_blocks_per_cu(P, R, DG, T, false), 1) ? KS_GP : KS_ROT;
+        switch (p.fused) {
+        case KS_S16X: case KS_S16N: p.fused_rows = gru_s16n_rows(m, B); p.ws_floats = s16n_floats(); break;
+        case KS_S16: p.fused_rows = gru_s16_rows(m, B); p.ws_floats = gru_s16_ckpt_floats(m, B, T); break;
+        case KS_GP: p.fused_rows = gp_grid(P, R, DG, B, T); break;
+        default: p.fused_rows = rot_grid > 0 ? rot_grid : ODPD_EUNSUPPORTED;
+        }
+    }
+    if (parts & GRU_PLAN_LOSSDX) {
+        // (workspace: the checkpoints of the split calls.)  Gate-parallel while every sequence of the batch is resident at once — but hidden
+        // 25 .. 32 without the fc_hid head: the two-block steps leave nothing to gain over the row-rotated kernel (0.97x measured,
+        // profiles/r03/frozen_pa_bench.md); 17 .. 24 (second block held twice, 8-rotation dot products) 1.07x, with the head 1.2-1.3x, hidden <= 16 1.35-1.85x
+        const bool no_gain = R == 2 && !DG && m->hidden > 24 && tn.gp_max_batch < 0, knob_bars = tn.gp_max_batch >= 0 && B > tn.gp_max_batch;
+        const int fz_grid = big == KS_ROT && !no_gain && !knob_bars ? gp_fz_grid(P, R, DG, B, T) : 0;
+        p.lossdx = s16n ? (gru_s16x_ok(m) ? KS_S16X : KS_S16N) : s16 ? KS_S16 : fz_grid > 0 ? KS_GP : KS_ROT;      // ("s16x", not "s16x_train")
+        switch (p.lossdx) {
+        case KS_S16X: case KS_S16N: p.loss_rows = gru_s16n_rows(m, B); break;
+        case KS_S16: p.loss_rows = gru_s16_rows(m, B); break;
+        case KS_GP: p.loss_rows = fz_grid; break;
+        default: {      // frame too long for LDS-resident BPTT state: use the split calls
+            const int grid = train_shape(P, R, DG, ng, T, nullptr, true).grid;
+            p.loss_rows = grid > 0 ? grid : ODPD_EUNSUPPORTED;
+        }
+        }
+    }
+    return p;
 }
 
 }  // namespace odpd

@@ -471,34 +471,25 @@ __global__ __launch_bounds__(64) void gru2_bwd_kernel(SeqArgs a) {
     }
 }
 
-bool gru2_cfg(const odpd_model_t* m, int& FM) {
-    switch (m->backbone) {
-    case ODPD_GRU: FM = FEAT_RAW2; return true;
-    case ODPD_DGRU: FM = FEAT_DGRU6; return true;
-    case ODPD_QGRU: FM = FEAT_Q4; return true;
-    case ODPD_QGRU_AMP1: FM = FEAT_A4; return true;
-    default: return false;
-    }
-}
-int gru2_P(const odpd_model_t* m, int FM) { return gru2_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), FM == FEAT_DGRU6).P; }
+int gru2_P(const odpd_model_t* m, int FM, bool DG) { return gru2_layout(m->hidden, gru_feat_dim(FM), DG).P; }
 }  // namespace
 
 // float gru / dgru / qgru / qgru_amp1 with two recurrent layers (ODPD_FLAG_TWO_LAYERS) of <= 32 hidden units
 bool gru2_ok(const odpd_model_t* m) {
-    int FM;
-    return (m->flags & ODPD_FLAG_TWO_LAYERS) && m->bits_w == 0 && m->hidden >= 1 && m->hidden <= 32 && gru2_cfg(m, FM);
+    int FM; bool DG;
+    return (m->flags & ODPD_FLAG_TWO_LAYERS) && m->bits_w == 0 && m->hidden >= 1 && m->hidden <= 32 && gru_cfg(m, FM, DG);
 }
 int64_t gru2_param_count(const odpd_model_t* m) {
-    int FM;
-    if (!gru2_cfg(m, FM)) return ODPD_EUNSUPPORTED;
-    return gru2_P(m, FM);
+    int FM; bool DG;
+    if (!gru_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
+    return gru2_P(m, FM, DG);
 }
 int64_t gru2_ckpt_floats(const odpd_model_t* m, int B, int T) { return (int64_t)B * (T + 1) * (m->backbone == ODPD_DGRU ? 6 : k2NS) * 64; }
 int gru2_rows(const odpd_model_t*, int B) { return wide_rows(B); }
 int gru2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    int FM;
-    if (!gru2_ok(m) || !gru2_cfg(m, FM)) return ODPD_EUNSUPPORTED;
-    const size_t lds = (size_t)gru2_fwd_floats(gru2_P(m, FM), FM == FEAT_DGRU6) * sizeof(float);
+    int FM; bool DG;
+    if (!gru2_ok(m) || !gru_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
+    const size_t lds = (size_t)gru2_fwd_floats(gru2_P(m, FM, DG), DG) * sizeof(float);
 #define ODPD_GRU2_FWD(FM_, DG_) \
     if (FM == FM_) return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, gru2_fwd_kernel<FM_, DG_, decltype(sv)::value>, lds, a); });
     ODPD_GRU2_FWD(FEAT_RAW2, false) ODPD_GRU2_FWD(FEAT_DGRU6, true) ODPD_GRU2_FWD(FEAT_Q4, false) ODPD_GRU2_FWD(FEAT_A4, false)
@@ -506,10 +497,10 @@ int gru2_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     return ODPD_EUNSUPPORTED;
 }
 int gru2_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    int FM;
-    if (!gru2_ok(m) || !gru2_cfg(m, FM)) return ODPD_EUNSUPPORTED;
+    int FM; bool DG;
+    if (!gru2_ok(m) || !gru_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
     if (!a.ckpt) return ODPD_EINVAL;
-    const size_t lds = (size_t)gru2_bwd_floats(gru2_P(m, FM), FM == FEAT_DGRU6) * sizeof(float);
+    const size_t lds = (size_t)gru2_bwd_floats(gru2_P(m, FM, DG), DG) * sizeof(float);
 #define ODPD_GRU2_BWD(FM_, DG_)                                                                                              \
     if (FM == FM_)                                                                                                           \
         return s16_bwd_dispatch(a, [&](auto nw, auto dx) {                                                                   \

@@ -833,18 +833,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gru16_bwd_kernel(SeqArg
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-static bool s16_cfg(const odpd_model_t* m, int& FM, bool& DG) {
-    switch (m->backbone) {
-    case ODPD_GRU: FM = FEAT_RAW2; DG = false; return true;
-    case ODPD_DGRU: FM = FEAT_DGRU6; DG = true; return true;
-    case ODPD_QGRU: FM = FEAT_Q4; DG = false; return true;
-    case ODPD_QGRU_AMP1: FM = FEAT_A4; DG = false; return true;
-    default: return false;
-    }
-}
-static int s16_param_count(int H, int FM, bool DG) {
-    return gru_layout(H, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
-}
 static size_t s16_lds_bytes(int P, int waves) {
     size_t nbytes = ((size_t)pad4(P) + s16_tab_floats(kS16Groups) + (size_t)waves * (kS16WaveFloats + kStageRowFloats)) * sizeof(float);
     const size_t red = reduce_scratch_bytes(P, waves);
@@ -867,7 +855,8 @@ static LaunchShape s16_shape(int ngroups) {
 }
 
 int gru_s16_groups(int B) { return (B + 15) / 16; }
-int64_t gru_s16_workspace_floats(const odpd_model_t* m, int B, int T) {
+// [16-sequence task][ckpt][64 lanes][4]: the checkpoints of the split calls, the workspace of the fused steps
+int64_t gru_s16_ckpt_floats(const odpd_model_t* m, int B, int T) {
     (void)m;
     return (int64_t)gru_s16_groups(B) * num_ckpt(T) * 256;
 }
@@ -969,28 +958,28 @@ static int launch_s16_bwd_mode(hipStream_t st, const SeqArgs& a, int P) {
 
 int gru_s16_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
-    if (!s16_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
-    const int P = s16_param_count(m->hidden, FM, DG);
+    const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_fwd<fm(), dg()>(st, a, P); });
 }
 int gru_s16_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
-    if (!s16_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
-    const int P = s16_param_count(m->hidden, FM, DG);
+    const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_bwd_mode<fm(), dg()>(st, a, P); });
 }
 
 int gru_s16_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
-    if (!s16_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
     if (!a0.ckpt || !a0.dx || !a0.partials || !a0.target) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
-    const int P = s16_param_count(m->hidden, FM, DG);
+    const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_lossdx_occ<fm(), dg()>(st, a, P); });
 }
 
@@ -1003,24 +992,24 @@ static int launch_s16_sweep_occ(hipStream_t st, const SeqArgs& a, int P, const S
 }
 bool gru_s16_sweep_ok(const odpd_model_t* m) {
     int FM; bool DG;
-    return s16_cfg(m, FM, DG) && m->hidden <= 16 && m->bits_w == 0 && !(m->flags & ODPD_FLAG_TWO_LAYERS);
+    return gru_cfg(m, FM, DG) && m->hidden <= 16 && m->bits_w == 0 && !(m->flags & ODPD_FLAG_TWO_LAYERS);
 }
 int gru_s16_sweep_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, const SweepRun* runs, int K, long long first) {
     int FM; bool DG;
-    if (!s16_cfg(m, FM, DG) || !gru_s16_sweep_ok(m) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || !gru_s16_sweep_ok(m) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
-    const int P = s16_param_count(m->hidden, FM, DG);
+    const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_sweep_occ<fm(), dg()>(st, a, P, runs, K, first); });
 }
 
 int gru_s16_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
-    if (!s16_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || m->hidden > 16) return ODPD_EUNSUPPORTED;
     if (!a0.ckpt) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
-    const int P = s16_param_count(m->hidden, FM, DG);
+    const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_occ<fm(), dg()>(st, a, P); });
 }
 

@@ -573,15 +573,6 @@ __global__ __launch_bounds__(s16n_two_waves_per_simd(MODE, NW, NCK) ? 512 : 256,
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-static bool s16n_cfg(const odpd_model_t* m, int& FM, bool& DG) {
-    switch (m->backbone) {
-    case ODPD_GRU: FM = FEAT_RAW2; DG = false; return true;
-    case ODPD_DGRU: FM = FEAT_DGRU6; DG = true; return true;
-    case ODPD_QGRU: FM = FEAT_Q4; DG = false; return true;
-    case ODPD_QGRU_AMP1: FM = FEAT_A4; DG = false; return true;
-    default: return false;
-    }
-}
 static int s16n_tiles(int H) { return (H + 15) / 16; }
 static LaunchShape s16n_shape(int ngroups) {      // one 4-wave workgroup per CU (one wave per SIMD)
     LaunchShape ls;
@@ -644,12 +635,12 @@ static int launch_s16n_chunks(hipStream_t st, const SeqArgs& a, int P, int mode,
 // mode 0 fused train, 1 forward, 2 backward, 3 frozen-PA loss step (forward + loss + dL/dx, a.partials = loss rows)
 int gru_s16n_launch(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int mode) {
     int FM; bool DG;
-    if (!s16n_cfg(m, FM, DG) || s16n_tiles(m->hidden) != 2) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || s16n_tiles(m->hidden) != 2) return ODPD_EUNSUPPORTED;
     if ((mode == 0 || mode == 3) && !a0.ckpt) return ODPD_EINVAL;
     if (mode == 3 && (!a0.dx || !a0.partials || !a0.target)) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
-    const int P = gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
+    const int P = gru_param_count(m->hidden, FM, DG);
     if (FM == FEAT_RAW2) return launch_s16n_chunks<FEAT_RAW2, false, 2>(st, a, P, mode, m->hidden);
     if (FM == FEAT_DGRU6) return launch_s16n_chunks<FEAT_DGRU6, true, 2>(st, a, P, mode, m->hidden);
     if (FM == FEAT_Q4) return launch_s16n_chunks<FEAT_Q4, false, 2>(st, a, P, mode, m->hidden);

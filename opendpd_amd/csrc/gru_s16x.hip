@@ -1234,18 +1234,9 @@ __global__ __launch_bounds__(NW ? 256 : 512, 1) void gru16x_bwd_kernel(SeqArgs a
 // host side
 // -------------------------------------------------------------------------------------------------
 constexpr int kS16xStride = 2;      // checkpoint stride of this kernel (its own: the workspace is private to the launch)
-static bool s16x_cfg(const odpd_model_t* m, int& FM, bool& DG) {
-    switch (m->backbone) {
-    case ODPD_GRU: FM = FEAT_RAW2; DG = false; return true;
-    case ODPD_DGRU: FM = FEAT_DGRU6; DG = true; return true;
-    case ODPD_QGRU: FM = FEAT_Q4; DG = false; return true;
-    case ODPD_QGRU_AMP1: FM = FEAT_A4; DG = false; return true;
-    default: return false;
-    }
-}
 bool gru_s16x_ok(const odpd_model_t* m) {
     int FM; bool DG;
-    return s16x_cfg(m, FM, DG) && m->hidden >= 17 && m->hidden <= 24 && m->bits_w == 0 && !(m->flags & ODPD_FLAG_TWO_LAYERS) &&
+    return gru_cfg(m, FM, DG) && m->hidden >= 17 && m->hidden <= 24 && m->bits_w == 0 && !(m->flags & ODPD_FLAG_TWO_LAYERS) &&
            tuning().s16x != 0;
 }
 int64_t gru_s16x_ckpt_floats(const odpd_model_t* m, int B, int T) {
@@ -1278,11 +1269,11 @@ static int launch_s16x_train(hipStream_t st, const SeqArgs& a, int P, int grid) 
 // (and row layout) as gru16n_kernel's train flavour, so the reduction / optimiser launches behind it are unchanged
 int gru_s16x_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int grid) {
     int FM; bool DG;
-    if (!s16x_cfg(m, FM, DG) || !gru_s16x_train_ok(m)) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || !gru_s16x_train_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a0.ckpt || !a0.partials || !a0.target) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
-    const int P = gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
+    const int P = gru_param_count(m->hidden, FM, DG);
     if (FM == FEAT_RAW2) return launch_s16x_train<FEAT_RAW2, false>(st, a, P, grid);
     if (FM == FEAT_DGRU6) return launch_s16x_train<FEAT_DGRU6, true>(st, a, P, grid);
     if (FM == FEAT_Q4) return launch_s16x_train<FEAT_Q4, false>(st, a, P, grid);
@@ -1302,11 +1293,11 @@ static int launch_s16x_fwd(hipStream_t st, const SeqArgs& a, int P) {
 }
 int gru_s16x_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     int FM; bool DG;
-    if (!s16x_cfg(m, FM, DG) || !gru_s16x_train_ok(m)) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || !gru_s16x_train_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a0.y) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
-    const int P = gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
+    const int P = gru_param_count(m->hidden, FM, DG);
     if (FM == FEAT_RAW2) return launch_s16x_fwd<FEAT_RAW2, false>(st, a, P);
     if (FM == FEAT_DGRU6) return launch_s16x_fwd<FEAT_DGRU6, true>(st, a, P);
     if (FM == FEAT_Q4) return launch_s16x_fwd<FEAT_Q4, false>(st, a, P);
@@ -1332,11 +1323,11 @@ static int launch_s16x_bwd_mode(hipStream_t st, const SeqArgs& a, int P, int row
 // rows = gru_s16n_rows(m, B): the partial rows the host reduces (the exact kernels' count)
 int gru_s16x_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int rows) {
     int FM; bool DG;
-    if (!s16x_cfg(m, FM, DG) || !gru_s16x_train_ok(m)) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || !gru_s16x_train_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a0.ckpt || !a0.dy) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
-    const int P = gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
+    const int P = gru_param_count(m->hidden, FM, DG);
     if (FM == FEAT_RAW2) return launch_s16x_bwd_mode<FEAT_RAW2, false>(st, a, P, rows);
     if (FM == FEAT_DGRU6) return launch_s16x_bwd_mode<FEAT_DGRU6, true>(st, a, P, rows);
     if (FM == FEAT_Q4) return launch_s16x_bwd_mode<FEAT_Q4, false>(st, a, P, rows);
@@ -1345,11 +1336,11 @@ int gru_s16x_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int r
 // frozen-PA loss step; the grid (= loss rows the host reduces) is gru_s16n_rows(m, B), the same as the exact-fp32 kernel's
 int gru_s16x_lossdx(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0, int grid) {
     int FM; bool DG;
-    if (!s16x_cfg(m, FM, DG) || !gru_s16x_ok(m)) return ODPD_EUNSUPPORTED;
+    if (!gru_cfg(m, FM, DG) || !gru_s16x_ok(m)) return ODPD_EUNSUPPORTED;
     if (!a0.ckpt || !a0.dx || !a0.partials || !a0.target) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = (a.B + 15) / 16;
-    const int P = gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P;
+    const int P = gru_param_count(m->hidden, FM, DG);
     if (FM == FEAT_RAW2) return launch_s16x<FEAT_RAW2, false>(st, a, P, grid);
     if (FM == FEAT_DGRU6) return launch_s16x<FEAT_DGRU6, true>(st, a, P, grid);
     if (FM == FEAT_Q4) return launch_s16x<FEAT_Q4, false>(st, a, P, grid);

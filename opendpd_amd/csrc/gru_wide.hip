@@ -435,22 +435,12 @@ __global__ __launch_bounds__(64) void wide_gru_bwd_kernel(SeqArgs a) {
     }
 }
 
-bool wide_cfg(const odpd_model_t* m, int& FM, bool& DG) {
-    switch (m->backbone) {
-    case ODPD_GRU: FM = FEAT_RAW2; DG = false; return true;
-    case ODPD_DGRU: FM = FEAT_DGRU6; DG = true; return true;
-    case ODPD_QGRU: FM = FEAT_Q4; DG = false; return true;
-    case ODPD_QGRU_AMP1: FM = FEAT_A4; DG = false; return true;
-    default: return false;
-    }
-}
-int wide_P(const odpd_model_t* m, int FM, bool DG) { return gru_layout(m->hidden, FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4), DG).P; }
 }  // namespace
 
 // float gru / dgru / qgru / qgru_amp1 of 33 .. 64 hidden units
 bool gru_wide_ok(const odpd_model_t* m) {
     int FM; bool DG;
-    return m->bits_w == 0 && m->hidden > 32 && m->hidden <= 64 && wide_cfg(m, FM, DG);
+    return m->bits_w == 0 && m->hidden > 32 && m->hidden <= 64 && gru_cfg(m, FM, DG);
 }
 int64_t gru_wide_ckpt_floats(const odpd_model_t* m, int B, int T) { return (int64_t)B * T * (m->backbone == ODPD_DGRU ? 6 : 5) * 64; }
 int gru_wide_rows(const odpd_model_t*, int B) { return wide_rows(B); }
@@ -460,8 +450,8 @@ namespace {
 template <bool S0>
 int wide_gru_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     int FM; bool DG;
-    if (!wide_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
-    const size_t lds = (size_t)wide_fwd_floats(wide_P(m, FM, DG), DG, m->hidden) * sizeof(float);
+    if (!gru_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
+    const size_t lds = (size_t)wide_fwd_floats(gru_param_count(m->hidden, FM, DG), DG, m->hidden) * sizeof(float);
 #define ODPD_WIDE_FWD(FM_, DG_) \
     if (FM == FM_) return ckpt_dispatch(a, [&](auto sv) { return wide_launch(st, wide_gru_fwd_kernel<FM_, DG_, decltype(sv)::value, S0>, lds, a); });
     ODPD_WIDE_FWD(FEAT_RAW2, false) ODPD_WIDE_FWD(FEAT_DGRU6, true) ODPD_WIDE_FWD(FEAT_Q4, false) ODPD_WIDE_FWD(FEAT_A4, false)
@@ -471,8 +461,8 @@ int wide_gru_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
 template <bool S0>
 int wide_gru_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     int FM; bool DG;
-    if (!wide_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
-    const size_t lds = (size_t)wide_bwd_floats(wide_P(m, FM, DG), DG, m->hidden) * sizeof(float);
+    if (!gru_cfg(m, FM, DG)) return ODPD_EUNSUPPORTED;
+    const size_t lds = (size_t)wide_bwd_floats(gru_param_count(m->hidden, FM, DG), DG, m->hidden) * sizeof(float);
 #define ODPD_WIDE_BWD(FM_, DG_)                                                                                                       \
     if (FM == FM_) {                                                                                                                  \
         if constexpr (S0) {                                                                                                           \
@@ -501,7 +491,7 @@ int gru_wide_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
 // the state route: float gru / dgru / qgru / qgru_amp1 of 1 .. 64 hidden units, one layer, from a caller-given initial state (a.h0)
 bool gru_state_ok(const odpd_model_t* m) {
     int FM; bool DG;
-    return m->bits_w == 0 && m->hidden >= 1 && m->hidden <= 64 && !(m->flags & ODPD_FLAG_TWO_LAYERS) && wide_cfg(m, FM, DG);
+    return m->bits_w == 0 && m->hidden >= 1 && m->hidden <= 64 && !(m->flags & ODPD_FLAG_TWO_LAYERS) && gru_cfg(m, FM, DG);
 }
 int gru_state_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
     if (!gru_state_ok(m)) return ODPD_EUNSUPPORTED;

@@ -587,42 +587,56 @@ static LaunchShape janet_bwd_shape(int ngroups) { return persistent_shape(ngroup
 // the gate-parallel fused train kernel: one sequence per single-wave workgroup, the frame's parked state in LDS
 static size_t janet_gp_lds_bytes(int P, int T) { return ((size_t)pad4(P) + janet_gp_buffer_floats(T)) * sizeof(float); }
 static int janet_gp_blocks_per_cu(int P, int T) { return gp_blocks_per_cu(janet_gp_lds_bytes(P, T), 4); }
-bool janet_train_uses_gp(const odpd_model_t* m, int B, int T) {
-    if (m->backbone != ODPD_PGJANET || m->hidden > 16 || janet_uses_s16(m, B)) return false;
-    // up to two rounds of workgroups: the alternative is the forward / loss / backward chain of the row-rotated kernels
-    return gp_batch_fits(B, janet_gp_blocks_per_cu(janet_layout(m->hidden).P, T), 2);
-}
-int janet_gp_rows(const odpd_model_t* m, int B, int T) {
-    return gp_rows(B, (int)(kMaxLds / janet_gp_lds_bytes(janet_layout(m->hidden).P, T)));
-}
 int janet_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    const int P = janet_layout(m->hidden).P;
-    const size_t lds = janet_gp_lds_bytes(P, a.T);
-    return launch_seq(st, janet_gp_train_kernel, janet_gp_rows(m, a.B, a.T), lds, a);
+    const SplitPlan p = janet_plan(m, a.B, a.T);
+    if (p.fused != KS_GP) return ODPD_EUNSUPPORTED;
+    return launch_seq(st, janet_gp_train_kernel, (int)p.fused_rows, janet_gp_lds_bytes(p.P, a.T), a);
 }
 int janet_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (m->hidden > 16) return ODPD_EUNSUPPORTED;
-    if (janet_uses_s16(m, a.B)) return janet_s16_launch(st, m, a, 1);
-    const int P = janet_layout(m->hidden).P;
-    if (gp_eval_batch_fits(a.B)) {     // sequences that each get a SIMD of their own (inference / checkpoint-writing forward)
-        const size_t lds = ((size_t)pad4(P) + kJTabFloats + kEvalChunk * 4 + kEvalChunk * kJEvalHistStride + 32) * sizeof(float);
+    const SplitPlan p = janet_plan(m, a.B, a.T);
+    switch (p.fwd(a)) {
+    case KS_S16: return janet_s16_launch(st, m, a, 1);
+    case KS_EVAL: {
+        const size_t lds = ((size_t)pad4(p.P) + kJTabFloats + kEvalChunk * 4 + kEvalChunk * kJEvalHistStride + 32) * sizeof(float);
         return ckpt_dispatch(a, [&](auto sv) { return launch_seq(st, janet_eval_kernel<sv()>, a.B, lds, a); });
     }
-    const LaunchShape ls = persistent_shape(a.ngroups, 16);
-    const size_t lds = janet_lds_bytes(P, ls.waves, false);
-    return launch_lds(st, janet_fwd_kernel<0>, ls.grid, 64 * ls.waves, lds, a);
+    case KS_ROT: {
+        const LaunchShape ls = persistent_shape(a.ngroups, 16);
+        return launch_lds(st, janet_fwd_kernel<0>, ls.grid, 64 * ls.waves, janet_lds_bytes(p.P, ls.waves, false), a);
+    }
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
 int janet_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (m->hidden > 16) return ODPD_EUNSUPPORTED;
-    if (janet_uses_s16(m, a.B)) return janet_s16_launch(st, m, a, 2);
+    const SplitPlan p = janet_plan(m, a.B, a.T);
+    if (p.bwd(a) == KS_S16) return janet_s16_launch(st, m, a, 2);
+    if (p.bwd(a) != KS_ROT) return ODPD_EUNSUPPORTED;
     const LaunchShape ls = janet_bwd_shape(a.ngroups);
-    const size_t lds = janet_lds_bytes(janet_layout(m->hidden).P, ls.waves, a.partials != nullptr);
+    const size_t lds = janet_lds_bytes(p.P, ls.waves, a.partials != nullptr);
     return s16_bwd_dispatch(a, [&](auto nw, auto dx) { return launch_lds(st, janet_bwd_kernel<nw(), dx()>, ls.grid, 64 * ls.waves, lds, a); });
 }
-int janet_family_rows(const odpd_model_t* m, int B) {
-    if (m->hidden > 16) return ODPD_EUNSUPPORTED;
-    if (janet_uses_s16(m, B)) return janet_s16_rows(m, B);
-    return janet_bwd_shape(num_groups(B, 1)).grid;
+
+// Every crossover of pgjanet at hidden <= 16 (17 .. 32: janet_wide.hip): janet_s16.hip from the batch that fills the chip (janet_uses_s16),
+// below it the row-rotated kernels, the evaluation kernel as the forward of batches whose sequences each get a SIMD of their own, and as the
+// fused train step the gate-parallel kernel for up to two rounds of workgroups — the alternative there is the forward / loss / backward
+// chain of the row-rotated kernels
+SplitPlan janet_plan(const odpd_model_t* m, int B, int T) {
+    SplitPlan p{};
+    p.need_ckpt = true;
+    p.ckpt_floats = p.bwd_rows = p.fused_rows = p.ws_floats = ODPD_EUNSUPPORTED;
+    if (m->hidden > 16) return p;
+    p.P = janet_layout(m->hidden).P;
+    const bool s16 = janet_uses_s16(m, B);
+    p.ckpt_floats = s16 ? janet_s16_ckpt_floats(m, B, T) : (int64_t)num_groups(B, 1) * num_ckpt(T) * 64;
+    p.fwd_ckpt = p.fwd_eval = s16 ? KS_S16 : gp_eval_batch_fits(B) ? KS_EVAL : KS_ROT;
+    p.bwd_w = p.bwd_dx = p.bwd_wdx = s16 ? KS_S16 : KS_ROT;
+    p.bwd_rows = s16 ? janet_s16_rows(m, B) : janet_bwd_shape(num_groups(B, 1)).grid;
+    if (m->backbone == ODPD_PGJANET && !s16 && gp_batch_fits(B, janet_gp_blocks_per_cu(p.P, T), 2)) {
+        p.fused = KS_GP;
+        p.fused_rows = gp_rows(B, (int)(kMaxLds / janet_gp_lds_bytes(p.P, T)));
+        p.ws_floats = 0;
+    }
+    return p;
 }
 
 }  // namespace odpd

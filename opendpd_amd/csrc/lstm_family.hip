@@ -1189,54 +1189,63 @@ static size_t lstm_gp_lds_bytes(int P, bool vd, int T, bool pg) {
 }
 static int lstm_gp_blocks_per_cu(int P, bool vd, int T, bool pg) { return gp_blocks_per_cu(lstm_gp_lds_bytes(P, vd, T, pg), 4); }
 static bool lstm_gp_parks_gates(int P, bool vd, int B, int T) { return (long)B <= (long)device_cus() * lstm_gp_blocks_per_cu(P, vd, T, true); }
-bool lstm_train_uses_gp(const odpd_model_t* m, int B, int T) {
-    if ((m->backbone != ODPD_LSTM && m->backbone != ODPD_VDLSTM) || m->hidden > 16 || lstm_train_uses_s16(m, B)) return false;
-    const bool vd = m->backbone == ODPD_VDLSTM;
-    if (vd && T < kHalo) return false;
-    const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
-    // up to two rounds of workgroups: the alternative here is the forward / loss / backward chain of the row-rotated kernels
-    return gp_batch_fits(B, lstm_gp_blocks_per_cu(P, vd, T, false), 2);
-}
-int lstm_gp_rows(const odpd_model_t* m, int B, int T) {
-    const bool vd = m->backbone == ODPD_VDLSTM;
-    const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
-    const bool pg = lstm_gp_parks_gates(P, vd, B, T);
-    return gp_rows(B, (int)(kMaxLds / lstm_gp_lds_bytes(P, vd, T, pg)));
-}
 int lstm_gp_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
+    const SplitPlan p = lstm_plan(m, a.B, a.T);
+    if (p.fused != KS_GP) return ODPD_EUNSUPPORTED;
     const bool vd = m->backbone == ODPD_VDLSTM;
-    const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
-    const bool pg = lstm_gp_parks_gates(P, vd, a.B, a.T);
-    const size_t lds = lstm_gp_lds_bytes(P, vd, a.T, pg);
-    const int grid = lstm_gp_rows(m, a.B, a.T);
-    auto launch = [&](auto k) { return launch_seq(st, k, grid, lds, a); };
+    const bool pg = lstm_gp_parks_gates(p.P, vd, a.B, a.T);
+    const size_t lds = lstm_gp_lds_bytes(p.P, vd, a.T, pg);
+    auto launch = [&](auto k) { return launch_seq(st, k, (int)p.fused_rows, lds, a); };
     if (vd && m->bits_w > 0) return pg ? launch(lstm_gp_train_kernel<true, true, true>) : launch(lstm_gp_train_kernel<true, false, true>);
     if (vd) return pg ? launch(lstm_gp_train_kernel<true, true>) : launch(lstm_gp_train_kernel<true, false>);
     if (m->bits_w > 0) return pg ? launch(lstm_gp_train_kernel<false, true, true>) : launch(lstm_gp_train_kernel<false, false, true>);
     return pg ? launch(lstm_gp_train_kernel<false, true>) : launch(lstm_gp_train_kernel<false, false>);
 }
 int lstm_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    const int R = rows_per_seq(m->hidden);
+    const SplitPlan p = lstm_plan(m, a.B, a.T);
+    const int R = rows_per_seq(m->hidden), P = p.P;
     const bool vd = m->backbone == ODPD_VDLSTM;
-    if (!R) return ODPD_EUNSUPPORTED;
+    if (p.fwd(a) == KS_NONE) return ODPD_EUNSUPPORTED;
     if (vd && a.T < kHalo) return ODPD_EINVAL;
-    const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
-    // sequences that each get a SIMD of their own (inference, and the checkpoint-writing forward of the split train path): the gate-parallel kernel
-    if (m->bits_w > 0 || gp_eval_batch_fits(a.B)) return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_eval<r(), v()>(st, a, P); });
+    if (p.fwd(a) == KS_EVAL) return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_eval<r(), v()>(st, a, P); });
     return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_fwd<r(), v()>(st, a, P); });
 }
 int lstm_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    const int R = rows_per_seq(m->hidden);
+    const SplitPlan p = lstm_plan(m, a.B, a.T);
+    const int R = rows_per_seq(m->hidden), P = p.P;
     const bool vd = m->backbone == ODPD_VDLSTM;
-    if (!R) return ODPD_EUNSUPPORTED;
+    if (p.bwd(a) == KS_NONE) return ODPD_EUNSUPPORTED;
     if (vd && a.T < kHalo) return ODPD_EINVAL;
-    const int P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
     return lstm_dispatch(R, vd, [&](auto r, auto v) { return lstm_launch_bwd_mode<r(), v()>(st, a, P); });
 }
-int lstm_family_rows(const odpd_model_t* m, int B) {
+
+// Every crossover of lstm / vdlstm at hidden <= 32.  The split calls stay on this file's kernels at every batch size: the row-rotated ones,
+// and as the forward the gate-parallel evaluation kernel for sequences that each get a SIMD of their own (inference, and the
+// checkpoint-writing forward of the split train path) and for the quantised heads.  The fused train step: lstm_s16.hip from the batch that
+// fills the chip (lstm_train_uses_s16; tensors only), below it the gate-parallel kernel at hidden <= 16 for up to two rounds of workgroups —
+// the alternative there is the forward / loss / backward chain of the row-rotated kernels
+SplitPlan lstm_plan(const odpd_model_t* m, int B, int T) {
+    SplitPlan p{};
+    p.need_ckpt = true;
+    p.ckpt_floats = p.bwd_rows = p.fused_rows = p.ws_floats = ODPD_EUNSUPPORTED;
     const int R = rows_per_seq(m->hidden);
-    if (!R) return ODPD_EUNSUPPORTED;
-    return lstm_bwd_shape(R, m->backbone == ODPD_VDLSTM, num_groups(B, R)).grid;
+    const bool vd = m->backbone == ODPD_VDLSTM;
+    if (!R) return p;
+    p.P = lstm_layout(m->hidden, vd, m->bits_w > 0).P;
+    p.ckpt_floats = (int64_t)num_groups(B, R) * num_ckpt(T) * 128;      // h and c
+    p.fwd_ckpt = p.fwd_eval = m->bits_w > 0 || gp_eval_batch_fits(B) ? KS_EVAL : KS_ROT;
+    p.bwd_w = p.bwd_dx = p.bwd_wdx = KS_ROT;
+    p.bwd_rows = lstm_bwd_shape(R, vd, num_groups(B, R)).grid;
+    if (lstm_train_uses_s16(m, B)) {
+        p.fused = KS_S16;
+        p.fused_rows = lstm_s16_rows(m, B);
+        p.ws_floats = lstm_s16_workspace_floats(m, B, T);
+    } else if (m->hidden <= 16 && !(vd && T < kHalo) && gp_batch_fits(B, lstm_gp_blocks_per_cu(p.P, vd, T, false), 2)) {
+        p.fused = KS_GP;
+        p.fused_rows = gp_rows(B, (int)(kMaxLds / lstm_gp_lds_bytes(p.P, vd, T, lstm_gp_parks_gates(p.P, vd, B, T))));
+        p.ws_floats = 0;
+    }
+    return p;
 }
 
 }  // namespace odpd

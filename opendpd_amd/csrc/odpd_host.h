@@ -113,6 +113,18 @@ __host__ __device__ inline GruLayout gru_layout(int H, int F, int dgru) {
     L.P = o;
     return L;
 }
+// the GRU family's template axes from the backbone: the feature map FM, and DG (the fc_hid head: dgru alone has it); its parameter count
+inline bool gru_cfg(const odpd_model_t* m, int& FM, bool& DG) {
+    switch (m->backbone) {
+    case ODPD_GRU: FM = FEAT_RAW2; DG = false; return true;
+    case ODPD_DGRU: FM = FEAT_DGRU6; DG = true; return true;
+    case ODPD_QGRU: FM = FEAT_Q4; DG = false; return true;
+    case ODPD_QGRU_AMP1: FM = FEAT_A4; DG = false; return true;
+    default: return false;
+    }
+}
+inline int gru_feat_dim(int FM) { return FM == FEAT_RAW2 ? 2 : (FM == FEAT_DGRU6 ? 6 : 4); }
+inline int gru_param_count(int H, int FM, bool DG) { return gru_layout(H, gru_feat_dim(FM), DG).P; }
 
 // qh: the nn.Linear heads are INT_Linear (`--quant` on lstm / vdlstm: the surgery swaps only those, quant/quant_envs.py:40-60) — three scale
 // parameters (weight_quantizer, act_quantizer, out_quantizer) behind each head's weight and bias, the named_parameters() order
@@ -204,6 +216,47 @@ static inline int ckpt_dispatch(const SeqArgs& a, F launch) {
 inline bool gp_eval_fits(const SeqArgs& a, int mode) { return mode == 1 && !a.ckpt && gp_eval_batch_fits(a.B); }
 template <int V> using int_c = std::integral_constant<int, V>;      // a template argument chosen at run time, handed to a generic lambda
 
+// ---- the split path of the five recurrent families, resolved once per (m, B, T) ----
+// gru_plan, lstm_plan, delta_plan, janet_plan, qat_plan (each in its family's home file) say which of the family's kernel sets serves every
+// call of a batch shape and what the buffers of those calls hold.  The size queries and the launches of capi.hip (split_step, fused_step) and
+// the family's own entry points read that one value; the family's crossovers (`*_uses_*`) are evaluated in its resolver and nowhere else.
+// The knobs are read live: a plan is computed per call and never kept.
+enum KernelSet {
+    KS_NONE,      // no kernel of the family takes the call: ODPD_EUNSUPPORTED
+    KS_ROT,       // row-rotated, four sequences (hidden 17 .. 32: two) per wave
+    KS_EVAL,      // one sequence per wave, evaluation
+    KS_GP,        // one sequence per wave (gate-parallel), the frame's BPTT state in LDS
+    KS_S16,       // 16 sequences per wave
+    KS_S16N,      // ... hidden 17 .. 32 of the GRU family (gru_s16n.hip)
+    KS_S16X,      // ... hidden 17 .. 24 of the GRU family on the bf16 matrix pipe (gru_s16x.hip)
+};
+struct SplitPlan {
+    KernelSet fwd_ckpt, fwd_eval;                              // the split forward that writes checkpoints, and the one that writes none
+    KernelSet bwd_w, bwd_dx, bwd_wdx;                          // the split backward: weight gradients, dL/dx, both
+    KernelSet fused;                                           // the fused train step (KS_NONE: the caller chains forward, loss, backward)
+    int64_t ckpt_floats, bwd_rows, fused_rows, ws_floats;      // odpd_ckpt_floats, odpd_partial_rows(fused = 0 / 1), odpd_train_workspace_floats
+    bool need_ckpt;      // the backward restarts every block but the first from a checkpoint: none given, with nck > 1, is ODPD_EINVAL
+    int P;               // parameters of the family's own layout
+    KernelSet fwd(const SeqArgs& a) const { return a.ckpt ? fwd_ckpt : fwd_eval; }
+    KernelSet bwd(const SeqArgs& a) const { return a.partials ? (a.dx ? bwd_wdx : bwd_w) : bwd_dx; }
+};
+struct GruPlan : SplitPlan {
+    KernelSet lossdx;      // the frozen-PA loss step (forward + loss + dL/dx in one launch)
+    int64_t loss_rows;     // odpd_frozen_loss_rows
+    int rot_rows;          // rows the row-rotated backward writes; bwd_rows is larger where weight gradients alone go to KS_GP
+    int FM, R;             // feature map; 16-lane rows per sequence (0: the family's kernels do not take the model, every set is KS_NONE)
+    bool DG;
+};
+// gru_family.hip: every crossover of the float GRU family.  `parts`: what the caller reads — the split calls (the sets and sizes of SplitPlan
+// but the fused ones, rot_rows), the fused step (fused, fused_rows, ws_floats), the loss step (lossdx, loss_rows); the rest stays unresolved
+// (KS_NONE, a refusal).  One fused step asks twice (fused_step, then the launcher), at a reference batch size of a 0.12 ms step
+enum { GRU_PLAN_SPLIT = 1, GRU_PLAN_FUSED = 2, GRU_PLAN_LOSSDX = 4 };
+GruPlan gru_plan(const odpd_model_t* m, int B, int T, int parts);
+SplitPlan lstm_plan(const odpd_model_t* m, int B, int T);     // lstm_family.hip
+SplitPlan delta_plan(const odpd_model_t* m, int B, int T);    // delta_family.hip
+SplitPlan janet_plan(const odpd_model_t* m, int B, int T);    // janet_family.hip
+SplitPlan qat_plan(const odpd_model_t* m, int B, int T);      // qgru_family.hip: the quantisation-aware models
+
 // one run of a lockstep sweep (K independent runs of one model shape advancing together: odpd_train_epoch_sweep, odpd_backbone_fwd_sweep);
 // the table lives in device memory, a sweep kernel's workgroup picks its entry by blockIdx.x / G
 struct SweepRun {
@@ -235,8 +288,6 @@ int gru_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_family_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_family_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_family_lossdx(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);        // frozen PA: forward + loss + dL/dx in one launch
-int gru_family_lossdx_rows(const odpd_model_t* m, int B, int T);
-int gru_family_rows(const odpd_model_t* m, int B, int which /*0 bwd, 1 fused*/, int T);
 // lockstep sweeps on the one-sequence-per-wave kernels (gru_family.hip): a.params / partials / frame_idx / y come from the table
 bool gru_sweep_train_ok(const odpd_model_t* m, int B, int T);
 int gru_sweep_train_rows(const odpd_model_t* m, int B, int T);
@@ -339,17 +390,14 @@ int gru_cascade_train(hipStream_t s, const odpd_model_t* dpd, const odpd_model_t
 // for every run): device table of K (thx, thh) pairs, 8-byte aligned, run k's delta engine at its own — delta DPDs only, else ODPD_EUNSUPPORTED
 int gru_cascade_sweep_train(hipStream_t s, const odpd_model_t* dpd, const odpd_model_t* pa, const CascArgs& a, const SweepRun* runs,
                             const float* const* pa_tab, const float* th_tab, int K, long long first);
-// 16-sequences-per-wave fused kernel (gru_s16.hip) and the rule that selects it
-bool gru_train_uses_s16(const odpd_model_t* m, int B, int T);
+// 16-sequences-per-wave kernels of hidden <= 16 (gru_s16.hip)
 int gru_s16_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_s16_lossdx(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);   // frozen PA: forward + loss + dL/dx, loss rows in partials
 int gru_s16_rows(const odpd_model_t* m, int B);
-bool gru_split_uses_s16(const odpd_model_t* m, int B);
 int gru_s16_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_s16_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int gru_s16_bwd_rows(const odpd_model_t* m, int B);
 // hidden 17..32 (gru_s16n.hip): mode 0 fused train (ckpt = workspace), 1 forward, 2 backward
-bool gru_uses_s16n(const odpd_model_t* m, int B);
 int gru_s16n_launch(hipStream_t s, const odpd_model_t* m, const SeqArgs& a, int mode);
 int gru_s16n_rows(const odpd_model_t* m, int B);
 int64_t gru_s16n_ckpt_floats(const odpd_model_t* m, int B, int T);
@@ -372,26 +420,20 @@ int launch_clip_adamw(hipStream_t st, int64_t P, float* params, float* grad, flo
 int launch_clip_optim(hipStream_t st, int kind, int64_t P, float* params, float* grad, float* state1, float* state2, int64_t step, double lr,
                       double max_norm, float* norm_out, float* loss_out, float inv_count, const unsigned char* skip = nullptr,
                       const XchgDev* xchg = nullptr);
-int64_t gru_s16_workspace_floats(const odpd_model_t* m, int B, int T);
+int64_t gru_s16_ckpt_floats(const odpd_model_t* m, int B, int T);      // [16-sequence task][ckpt][64 lanes][4]: the split calls' checkpoints and the fused steps' workspace
 // fused train step of the delta backbones at the reference's batch sizes (delta_family.hip: delta_gp_bwd_kernel<.., FUSED>)
-bool delta_train_uses_gp(const odpd_model_t* m, int B, int T);
-int delta_gp_train_rows(const odpd_model_t* m, int B, int T);
 int delta_gp_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int lstm_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int lstm_family_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
-int lstm_family_rows(const odpd_model_t* m, int B);
 // 16-sequences-per-wave fused train kernel of lstm / vdlstm (lstm_s16.hip)
 bool lstm_train_uses_s16(const odpd_model_t* m, int B);
 // gate-parallel fused train kernel of lstm / vdlstm at the reference's batch sizes (lstm_family.hip)
-bool lstm_train_uses_gp(const odpd_model_t* m, int B, int T);
-int lstm_gp_rows(const odpd_model_t* m, int B, int T);
 int lstm_gp_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int lstm_s16_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int lstm_s16_rows(const odpd_model_t* m, int B);
 int64_t lstm_s16_workspace_floats(const odpd_model_t* m, int B, int T);
 int delta_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int delta_family_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
-int delta_family_rows(const odpd_model_t* m, int B, int T);
 // 16-sequences-per-wave split kernels of the delta backbones (delta_s16.hip): mode 1 forward, 2 backward
 bool delta_uses_s16(const odpd_model_t* m, int B);
 int delta_s16_launch(hipStream_t s, const odpd_model_t* m, const SeqArgs& a, int mode);
@@ -412,10 +454,7 @@ __host__ __device__ inline JanetLayout janet_layout(int H) {
 }
 int janet_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int janet_family_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
-int janet_family_rows(const odpd_model_t* m, int B);
 // gate-parallel fused train kernel of PGJANET at the reference's batch sizes (janet_family.hip)
-bool janet_train_uses_gp(const odpd_model_t* m, int B, int T);
-int janet_gp_rows(const odpd_model_t* m, int B, int T);
 int janet_gp_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 // 16-sequences-per-wave split kernels of PGJANET (janet_s16.hip): mode 1 forward, 2 backward
 bool janet_uses_s16(const odpd_model_t* m, int B);
@@ -497,9 +536,10 @@ int64_t rvtdcnn_q_param_count(const odpd_model_t* m);
 int rvtdcnn_q_rows(const odpd_model_t* m, int B, int T);
 int rvtdcnn_q_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int rvtdcnn_q_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a, bool fused);
-int qgru_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
-int qgru_family_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
-int qgru_family_rows(const odpd_model_t* m, int B);
+// the quantisation-aware models' split calls (qgru_family.hip): row-rotated kernels there, evaluation and 16-sequences-per-wave ones by qat_plan
+int qat_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+int qat_family_bwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
+int qat_family_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int64_t qgru_param_count(const odpd_model_t* m);
 // quantised gru / dgru / qgru / qgru_amp1 / deltagru_tcnskip on the 16-sequences-per-wave mapping, hidden <= 32 (qat_s16.hip): mode 1 forward, 2 backward
 bool qat_s16_supported(const odpd_model_t* m);

@@ -441,23 +441,62 @@ static int qgru_launch_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs&
     });
 }
 
-int qgru_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (!qat_ok(m)) return ODPD_EUNSUPPORTED;
-    const int P = qgru_layout(m->hidden).P;
+int qat_family_fwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
+    const SplitPlan p = qat_plan(m, a.B, a.T);
+    const int P = p.P;
     const bool amp1 = m->backbone == ODPD_QGRU_AMP1, lut = m->bits_a <= 8;
-    if (amp1) return lut ? qgru_launch_fwd<true, true>(st, m, a, P) : qgru_launch_fwd<true, false>(st, m, a, P);
-    return lut ? qgru_launch_fwd<false, true>(st, m, a, P) : qgru_launch_fwd<false, false>(st, m, a, P);
+    switch (p.fwd(a)) {
+    case KS_EVAL: return qat_gp_eval(st, m, a);
+    case KS_S16: return qat_s16_launch(st, m, a, 1);
+    case KS_ROT:
+        if (amp1) return lut ? qgru_launch_fwd<true, true>(st, m, a, P) : qgru_launch_fwd<true, false>(st, m, a, P);
+        return lut ? qgru_launch_fwd<false, true>(st, m, a, P) : qgru_launch_fwd<false, false>(st, m, a, P);
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
-int qgru_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
-    if (!qat_ok(m)) return ODPD_EUNSUPPORTED;
-    const int P = qgru_layout(m->hidden).P;
+int qat_family_bwd(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
+    const SplitPlan p = qat_plan(m, a.B, a.T);
+    const int P = p.P;
     const bool amp1 = m->backbone == ODPD_QGRU_AMP1, lut = m->bits_a <= 8;
-    if (amp1) return lut ? qgru_launch_bwd<true, true>(st, m, a, P) : qgru_launch_bwd<true, false>(st, m, a, P);
-    return lut ? qgru_launch_bwd<false, true>(st, m, a, P) : qgru_launch_bwd<false, false>(st, m, a, P);
+    switch (p.bwd(a)) {
+    case KS_S16: return qat_s16_launch(st, m, a, 2);      // (checks its own checkpoint count)
+    case KS_ROT:
+        if (amp1) return lut ? qgru_launch_bwd<true, true>(st, m, a, P) : qgru_launch_bwd<true, false>(st, m, a, P);
+        return lut ? qgru_launch_bwd<false, true>(st, m, a, P) : qgru_launch_bwd<false, false>(st, m, a, P);
+    default: return ODPD_EUNSUPPORTED;
+    }
 }
-int qgru_family_rows(const odpd_model_t* m, int B) {
-    if (!qat_ok(m)) return ODPD_EUNSUPPORTED;
-    return qgru_bwd_shape(num_groups(B, 1)).grid;
+// the fused train step: one frame per wave at the reference's batch sizes (`workspace`: the counters or nothing), else forward-with-checkpoints +
+// backward-with-loss launches of qat_s16.hip (a.ckpt = the workspace)
+int qat_family_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a) {
+    const SplitPlan p = qat_plan(m, a.B, a.T);
+    if (p.fused == KS_S16) return qat_s16_launch(st, m, a, 0);
+    if (p.fused != KS_GP) return ODPD_EUNSUPPORTED;
+    SeqArgs b = a;
+    b.ckpt = nullptr;
+    return qat_gp_train(st, m, b);
+}
+
+// Every crossover of the quantisation-aware models (bits_w > 0 on gru, dgru, qgru, qgru_amp1, deltagru_tcnskip).  The row-rotated kernels of
+// this file (qgru / qgru_amp1, hidden <= 16, 4 sequences per wave) serve while the batch leaves the chip mostly empty, the
+// 16-sequences-per-wave ones (qat_s16.hip) otherwise and for every other kind / hidden size; a forward that wants no checkpoints, and the fused
+// train step, go to the one-sequence-per-wave engines (qat_cascade.hip) where those take the shape
+SplitPlan qat_plan(const odpd_model_t* m, int B, int T) {
+    SplitPlan p{};
+    const bool rot_ok = (m->backbone == ODPD_QGRU || m->backbone == ODPD_QGRU_AMP1) && m->hidden <= 16;
+    const bool s16 = !rot_ok || B >= s16_min_batch_or(16L * 3 * device_cus());
+    const KernelSet set = s16 ? KS_S16 : qat_ok(m) ? KS_ROT : KS_NONE;
+    p.P = qgru_layout(m->hidden).P;      // (the row-rotated kernels' layout; qat_s16.hip has its own per kind)
+    p.need_ckpt = !s16;
+    // (kept: the checkpoint query does not ask the bit widths the row-rotated kernels take; the rows do)
+    p.ckpt_floats = s16 ? qat_s16_ckpt_floats(m, B, T) : (int64_t)num_groups(B, 1) * num_ckpt(T) * 64;
+    p.bwd_rows = s16 ? qat_s16_rows(m, B) : set == KS_ROT ? qgru_bwd_shape(num_groups(B, 1)).grid : ODPD_EUNSUPPORTED;
+    p.fwd_ckpt = p.bwd_w = p.bwd_dx = p.bwd_wdx = set;
+    p.fwd_eval = qat_uses_gp_eval(m, B, false) ? KS_EVAL : set;
+    p.fused = qat_train_uses_gp(m, B, T) ? KS_GP : s16 ? KS_S16 : KS_NONE;
+    p.fused_rows = p.fused == KS_GP ? qat_gp_train_rows(m, B, T) : p.fused == KS_S16 ? qat_s16_rows(m, B) : ODPD_EUNSUPPORTED;
+    p.ws_floats = p.fused == KS_GP ? 0 : p.fused == KS_S16 ? qat_s16_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
+    return p;
 }
 int64_t qgru_param_count(const odpd_model_t* m) { return qgru_layout(m->hidden).P; }
 
