@@ -833,7 +833,7 @@ extern "C" int64_t odpd_sweep_workspace_floats(const odpd_model_t* m, int B, int
     if (!model_ok(m) || B <= 0 || T <= 0) return ODPD_EINVAL;
     if (init_state(m) || quant_cell(m)) return ODPD_EUNSUPPORTED;
     if (!(flags & ODPD_SWEEP_S16)) return 0;
-    return odpd_sweep_s16_supported(m) ? gru_s16_ckpt_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
+    return odpd_sweep_s16_supported(m) ? gru_s16_train_ws_floats(m, B, T) : (int64_t)ODPD_EUNSUPPORTED;
 }
 extern "C" int odpd_train_epoch_sweep(void* stream, const odpd_model_t* m, int K, const odpd_sweep_run_t* runs, int loss_kind, const odpd_frames_t* fr,
                                       int batch, int64_t first_step, double beta1, double beta2, double eps, double weight_decay, double max_norm,

@@ -1558,7 +1558,7 @@ GruPlan gru_plan(const odpd_model_t* m, int B, int T, int parts) {
         else p.fused = gp_batch_fits(B, gp_blocks_per_cu(P, R, DG, T, false), 1) ? KS_GP : KS_ROT;
         switch (p.fused) {
         case KS_S16X: case KS_S16N: p.fused_rows = gru_s16n_rows(m, B); p.ws_floats = s16n_floats(); break;
-        case KS_S16: p.fused_rows = gru_s16_rows(m, B); p.ws_floats = gru_s16_ckpt_floats(m, B, T); break;
+        case KS_S16: p.fused_rows = gru_s16_rows(m, B); p.ws_floats = gru_s16_train_ws_floats(m, B, T); break;
         case KS_GP: p.fused_rows = gp_grid(P, R, DG, B, T); break;
         default: p.fused_rows = rot_grid > 0 ? rot_grid : ODPD_EUNSUPPORTED;
         }

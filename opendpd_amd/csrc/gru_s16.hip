@@ -72,6 +72,16 @@ __device__ __forceinline__ void s16_fill_table(float* tab, const float* pl, cons
     __syncthreads();
 }
 
+// BPTT block length of the fused train body (steps recomputed into registers per block = distance of its checkpoints); the frozen-PA
+// variant of the body and the split kernels keep kCkptStride (they share the checkpoint layout odpd_ckpt_floats sizes).
+// -DODPD_S16_BLOCK=2 builds two-step blocks (twice the workspace; gru_s16_train_ws_floats follows): 232 registers and no scratch on the
+// headline instantiation, but 1.5 % SLOWER there — twice the per-block work (operand pulls, checkpoint traffic) — profiles/s16_blocks.md
+#ifndef ODPD_S16_BLOCK
+#define ODPD_S16_BLOCK kCkptStride
+#endif
+constexpr int kS16Block = ODPD_S16_BLOCK;
+static_assert(kS16Block >= 1 && kChunk % kS16Block == 0, "a block never straddles two staged chunks");
+
 template <int FM>
 struct S16Fw {                     // operands of the forward / recompute phase
     float whh[3][4];               // A: W_hg[m][4q+c]
@@ -186,12 +196,13 @@ constexpr bool s16_packgrad(bool pack, bool nw) { return pack && nw; }
 //   hTn  : transposed h of the step after the current one (fc_hid weight gradient operand)
 //   FUSED: `ts` holds the target, y / loss / dL/dy are formed here;  else `ts` holds dL/dy
 //   NW   : accumulate weight gradients into G        DX : write dL/dx of the block's steps to dxs
-template <int FM, bool DG, bool FUSED, bool NW, bool DX, bool FULL, bool PACK = false>
+//   S    : block length                              L2C : FUSED with the L2 loss known at compile time (else a.loss_kind decides)
+template <int FM, bool DG, bool FUSED, bool NW, bool DX, bool FULL, bool PACK = false, int S = kCkptStride, bool L2C = false>
 __device__ __forceinline__ void s16_block(const SeqArgs& a, TabPtr tl, const float (&oh)[4], S16Grad<DG>& G,
                                           const float2* xs, const float2* ts, float2* dxs, float* tiles, int n, int q, int tloc,
                                           int nstep, bool valid, bool last_blk, f32x4 h, f32x4& dh, float (&hTn)[4],
                                           float& loss_acc) {
-    constexpr int NCH = S16Cfg<FM>::NCH, S = kCkptStride;
+    constexpr int NCH = S16Cfg<FM>::NCH;
     f32x4 hp_s[S], r_s[S], z_s[S], n_s[S], g_s[S];
     float fs_s[S][NCH];
     {
@@ -235,7 +246,7 @@ __device__ __forceinline__ void s16_block(const SeqArgs& a, TabPtr tl, const flo
         wave_lds_fence();
         tile_get(t_h, n, q, hTn);
     }
-    const S16Loss lossc = s16_loss_setup(a.loss_kind == ODPD_LOSS_L2, valid ? a.inv_count : 0.0f, valid && q == 0);
+    const S16Loss lossc = s16_loss_setup(L2C || a.loss_kind == ODPD_LOSS_L2, valid ? a.inv_count : 0.0f, valid && q == 0);
 #pragma unroll
     for (int st = S - 1; st >= 0; --st) {
         if (FULL || st < nstep) {
@@ -268,7 +279,8 @@ __device__ __forceinline__ void s16_block(const SeqArgs& a, TabPtr tl, const flo
                 }
                 const float y0 = quad_sum(p0), y1 = quad_sum(p1);
                 const float d0 = y0 - tv.x, d1 = y1 - tv.y;
-                s16_loss(lossc, d0, d1, dy0, dy1, loss_acc);
+                if constexpr (L2C) s16_loss_l2(lossc, d0, d1, dy0, dy1, loss_acc);
+                else s16_loss(lossc, d0, d1, dy0, dy1, loss_acc);
             }
             if constexpr (NW) {
 #pragma unroll
@@ -478,9 +490,10 @@ __device__ __forceinline__ void s16_write_row(float* prow, const GruLayout& L, S
 // NW: weight-gradient partials (train_pa / the trained model).  !NW && DX: the frozen PA of a cascade in one launch — forward,
 // loss and dL/dx (written to a.dx), one loss partial per workgroup in a.partials[blockIdx.x * kLossCols].
 // (the body takes its workgroup index and count as arguments: the sweep launch below runs it for K models side by side)
-template <int FM, bool DG, int OCC, bool PACK, bool NW = true, bool DX = false>
+// L2C: the L2 loss at compile time (a.loss_kind == ODPD_LOSS_L2 is the launch's promise); else a.loss_kind decides in the block
+template <int FM, bool DG, int OCC, bool PACK, bool NW = true, bool DX = false, bool L2C = false>
 __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid, const int nbl) {
-    constexpr int F = S16Cfg<FM>::F, NCH = S16Cfg<FM>::NCH, S = kCkptStride;
+    constexpr int F = S16Cfg<FM>::F, NCH = S16Cfg<FM>::NCH, S = NW ? kS16Block : kCkptStride;
     constexpr int kGroups = DX ? kS16GroupsDx : kS16Groups;
     constexpr int kWave = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? kS16Tiles * kTileFloats : 0) + kStageRowFloats;
     static_assert(NCH <= 2, "operand tables and dwf accumulators are sized for two K-chunks");
@@ -509,6 +522,13 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
     S16Grad<DG> G;
     G.zero();
     float loss_acc = 0.0f;
+    // the forward pass stops at the last checkpoint: the first backward block recomputes the steps behind it (S16_FULL_FWD: the whole frame,
+    // the timing reference of profiles/s16_blocks.md)
+#ifdef ODPD_S16_FULL_FWD
+    const int Tf = a.T;
+#else
+    const int Tf = (a.nck - 1) * S;
+#endif
     const int nwaves = nbl * nwb;
     for (int grp = bid * nwb + wave; grp < a.ngroups; grp += nwaves) {
         const int b0 = grp * 16;
@@ -522,8 +542,8 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
             S16Fw<FM> w;
             s16_load_fw<FM>(w, tl);
             f32x4 h = {0.f, 0.f, 0.f, 0.f};
-            for (int t0 = 0; t0 < a.T; t0 += kChunk) {
-                const int len = min(kChunk, a.T - t0);
+            for (int t0 = 0; t0 < Tf; t0 += kChunk) {
+                const int len = min(kChunk, Tf - t0);
                 StagedChunk<1> xc;
                 stage_issue<1>(xc, {a.x}, rows, b0, a.B, t0, len, lane, {kFillX}, bf16);
                 wave_lds_fence();
@@ -548,6 +568,7 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
                     const int t1 = t0 + tt + S;
                     if (t1 < a.T) ck[(size_t)(t1 / S) * 64] = make_float4(h[0], h[1], h[2], h[3]);
                 }
+#ifdef ODPD_S16_FULL_FWD      // (Tf is a multiple of S otherwise: no tail)
                 for (; tt < len; ++tt) {
                     const float2 xv = xs[n * kChunkPad + tt];
                     float fs[NCH];
@@ -561,6 +582,7 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
                         s16_cell_fwd<FM>(w, fs, h, r, z, nn, g);
                     }
                 }
+#endif
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // own checkpoint stores precede the loads below
@@ -591,9 +613,9 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
                 cur_chunk = chunk;
             }
             if (nstep == S)
-                s16_block<FM, DG, true, NW, DX, true, PACK>(a, tl, oh, G, xs, ts, dxs, tiles, n, q, tb - t0, nstep, valid, blk == a.nck - 1, h0, dh, hTn, loss_acc);
+                s16_block<FM, DG, true, NW, DX, true, PACK, S, L2C>(a, tl, oh, G, xs, ts, dxs, tiles, n, q, tb - t0, nstep, valid, blk == a.nck - 1, h0, dh, hTn, loss_acc);
             else
-                s16_block<FM, DG, true, NW, DX, false, PACK>(a, tl, oh, G, xs, ts, dxs, tiles, n, q, tb - t0, nstep, valid, blk == a.nck - 1, h0, dh, hTn, loss_acc);
+                s16_block<FM, DG, true, NW, DX, false, PACK, S, L2C>(a, tl, oh, G, xs, ts, dxs, tiles, n, q, tb - t0, nstep, valid, blk == a.nck - 1, h0, dh, hTn, loss_acc);
         }
         if constexpr (DX) {
             if (cur_chunk >= 0) {
@@ -629,17 +651,17 @@ __device__ __forceinline__ void gru16_train_body(const SeqArgs& a, const int bid
         prow[i] = v;
     }
 }
-template <int FM, bool DG, int OCC, bool PACK, bool NW = true, bool DX = false>
+template <int FM, bool DG, int OCC, bool PACK, bool NW = true, bool DX = false, bool L2C = false>
 __global__ __launch_bounds__(64 * 4 * OCC, OCC) void gru16_train_kernel(SeqArgs a) {
-    gru16_train_body<FM, DG, OCC, PACK, NW, DX>(a, blockIdx.x, gridDim.x);
+    gru16_train_body<FM, DG, OCC, PACK, NW, DX, L2C>(a, blockIdx.x, gridDim.x);
 }
 // K independent runs of one model shape in lockstep on the 16-sequences-per-wave kernel (odpd_train_epoch_sweep, ODPD_SWEEP_S16): run k owns
 // workgroups [k G, (k + 1) G) and sees the launch it would have alone with this kernel forced (odpd_set_tuning("s16_min_batch", 0))
-template <int FM, bool DG, int OCC, bool PACK>
+template <int FM, bool DG, int OCC, bool PACK, bool L2C>
 __global__ __launch_bounds__(64 * 4 * OCC, OCC) void gru16_train_sweep_kernel(SeqArgs a, const SweepRun* __restrict__ runs, int G, long long first) {
     const SweepRun r = runs[blockIdx.x / G];
     a.params = r.params; a.partials = r.partials; a.frame_idx = r.order + first; a.ckpt = r.workspace;
-    gru16_train_body<FM, DG, OCC, PACK>(a, blockIdx.x % G, G);
+    gru16_train_body<FM, DG, OCC, PACK, true, false, L2C>(a, blockIdx.x % G, G);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -672,6 +694,8 @@ __device__ __forceinline__ float4 s16_ckpt_load(const float4* rec, int lane, int
     return v;
 }
 
+// per-wave LDS of the forward kernel: x and y chunks, the group's row offsets (stage_rows)
+constexpr int kS16FwdWaveFloats = 2 * 2 * 16 * kChunkPad + kStageRowFloats;
 // forward: y for every step, optional checkpoints of h ([task][ckpt] records, s16_ckpt_store)
 template <int FM, bool DG, bool PACK>
 __global__ __launch_bounds__(1024) void gru16_fwd_kernel(SeqArgs a) {
@@ -688,8 +712,10 @@ __global__ __launch_bounds__(1024) void gru16_fwd_kernel(SeqArgs a) {
     float oh[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) oh[e] = q == e ? 1.0f : 0.0f;
-    float2* xs = reinterpret_cast<float2*>(tab + s16_tab_floats(kS16Groups)) + (size_t)wave * (2 * 16 * kChunkPad);
+    float* wbase = tab + s16_tab_floats(kS16Groups) + (size_t)wave * kS16FwdWaveFloats;
+    float2* xs = reinterpret_cast<float2*>(wbase);
     float2* ys = xs + 16 * kChunkPad;
+    unsigned long long* rows = reinterpret_cast<unsigned long long*>(wbase + kS16FwdWaveFloats - kStageRowFloats);   // stage_rows
     S16Fw<FM> wf;
     s16_load_fw<FM>(wf, tl);
     S16Bw<FM, DG> wh;            // only the head operands (fc_hid, fc_out) are used here
@@ -699,10 +725,15 @@ __global__ __launch_bounds__(1024) void gru16_fwd_kernel(SeqArgs a) {
         const int b0 = grp * 16;
         float4* ck = a.ckpt ? reinterpret_cast<float4*>(a.ckpt) + (size_t)grp * a.nck * 64 : nullptr;
         f32x4 h = {0.f, 0.f, 0.f, 0.f};
+        wave_lds_fence();
+        stage_rows(rows, b0, a.B, a.T, lane, nullptr, 0);
+        wave_lds_fence();
         for (int t0 = 0; t0 < a.T; t0 += kChunk) {
             const int len = min(kChunk, a.T - t0);
+            StagedChunk<1> xc;
+            stage_issue<1>(xc, {a.x}, rows, b0, a.B, t0, len, lane, {make_float2(0.5f, 0.5f)}, false);
             wave_lds_fence();
-            stage_in<16>(xs, a.x, b0, a.B, a.T, t0, len, lane, make_float2(0.5f, 0.5f));
+            stage_commit<1>(xc, {xs}, b0, a.B, len, lane, false);
             wave_lds_fence();
             for (int tt = 0; tt < len; ++tt) {
                 const float2 xv = xs[n * kChunkPad + tt];
@@ -746,12 +777,16 @@ __global__ __launch_bounds__(1024) void gru16_fwd_kernel(SeqArgs a) {
     }
 }
 
+// per-wave LDS of the backward kernel: x, dL/dy (and dL/dx) chunks, the transpose tiles, the group's row offsets (stage_rows)
+__host__ __device__ constexpr int s16_bwd_wave_floats(bool nw, bool dx) {
+    return (dx ? 3 : 2) * 2 * 16 * kChunkPad + (nw ? kS16Tiles * kTileFloats : 0) + kStageRowFloats;
+}
 // backward from dL/dy: weight-gradient partials (NW) and / or dL/dx (DX)
 template <int FM, bool DG, bool NW, bool DX, int WAVES, bool PACK = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gru16_bwd_kernel(SeqArgs a) {
     constexpr int F = S16Cfg<FM>::F, S = kCkptStride;
     constexpr int kGroups = DX ? kS16GroupsDx : kS16Groups;
-    constexpr int kWave = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? kS16Tiles * kTileFloats : 0);
+    constexpr int kWave = s16_bwd_wave_floats(NW, DX);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwb = blockDim.x >> 6;
     const int n = lane & 15, q = lane >> 4;
@@ -769,6 +804,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gru16_bwd_kernel(SeqArg
     float2* dys = xs + 16 * kChunkPad;
     float2* dxs = DX ? dys + 16 * kChunkPad : nullptr;
     float* tiles = reinterpret_cast<float*>(dys + (DX ? 2 : 1) * 16 * kChunkPad);
+    unsigned long long* rows = reinterpret_cast<unsigned long long*>(wbase + kWave - kStageRowFloats);   // stage_rows
     if constexpr (NW)
         for (int i = lane; i < kTileFloats; i += 64) tiles[6 * kTileFloats + i] = 0.0f;
     S16Grad<DG> G;
@@ -778,6 +814,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gru16_bwd_kernel(SeqArg
     for (int grp = blockIdx.x * nwb + wave; grp < a.ngroups; grp += nwaves) {
         const int b0 = grp * 16;
         const float4* ck = reinterpret_cast<const float4*>(a.ckpt) + (size_t)grp * a.nck * 64;
+        wave_lds_fence();
+        stage_rows(rows, b0, a.B, a.T, lane, nullptr, 0);
+        wave_lds_fence();
         f32x4 dh = {0.f, 0.f, 0.f, 0.f};
         float hTn[4] = {0.f, 0.f, 0.f, 0.f};
         int cur_chunk = -1;
@@ -795,10 +834,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gru16_bwd_kernel(SeqArg
                         stage_out<16>(dxs, a.dx, b0, a.B, a.T, pt0, min(kChunk, a.T - pt0), lane);
                     }
                 }
-                wave_lds_fence();
                 const int len = min(kChunk, a.T - t0);
-                stage_in<16>(xs, a.x, b0, a.B, a.T, t0, len, lane, make_float2(0.5f, 0.5f));
-                stage_in<16>(dys, a.dy, b0, a.B, a.T, t0, len, lane, make_float2(0.0f, 0.0f));
+                StagedChunk<2> xd;      // x and dL/dy: one batch of loads, one wait
+                stage_issue<2>(xd, {a.x, a.dy}, rows, b0, a.B, t0, len, lane, {make_float2(0.5f, 0.5f), make_float2(0.0f, 0.0f)}, false);
+                wave_lds_fence();
+                stage_commit<2>(xd, {xs, dys}, b0, a.B, len, lane, false);
                 wave_lds_fence();
                 cur_chunk = chunk;
             }
@@ -860,6 +900,12 @@ int64_t gru_s16_ckpt_floats(const odpd_model_t* m, int B, int T) {
     (void)m;
     return (int64_t)gru_s16_groups(B) * num_ckpt(T) * 256;
 }
+// the fused train step's workspace: a checkpoint every kS16Block steps
+static int s16_train_nck(int T) { return (T + kS16Block - 1) / kS16Block; }
+int64_t gru_s16_train_ws_floats(const odpd_model_t* m, int B, int T) {
+    (void)m;
+    return (int64_t)gru_s16_groups(B) * s16_train_nck(T) * 256;
+}
 int gru_s16_rows(const odpd_model_t* m, int B) {
     (void)m;
     return s16_shape(gru_s16_groups(B)).grid;
@@ -872,6 +918,15 @@ static int s16_occ_dispatch(const SeqArgs& a, F f) {
     if (s16_occupancy(a.ngroups) == 1) return f(int_c<1>{}, std::false_type{});
     if constexpr (S16Cfg<FM>::NCH == 2) { if (a.H <= 13) return f(int_c<2>{}, std::true_type{}); }
     return f(int_c<2>{}, std::false_type{});
+}
+// the loss kind of the fused blocks: f(L2C) — L2 as its own instantiation (s16_loss_l2), L1 on the code that reads a.loss_kind
+// (-DODPD_S16_NO_L2C: every launch on the latter, the timing reference of profiles/s16_blocks.md)
+template <typename F>
+static int s16_loss_dispatch(const SeqArgs& a, F f) {
+#ifndef ODPD_S16_NO_L2C
+    if (a.loss_kind == ODPD_LOSS_L2) return f(std::true_type{});
+#endif
+    return f(std::false_type{});
 }
 // the feature map (and with it the fc_hid head, DG): f(FM, DG)
 template <typename F>
@@ -888,7 +943,9 @@ template <int FM, bool DG>
 static int launch_s16_occ(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = s16_shape(a.ngroups);
     return s16_occ_dispatch<FM>(a, [&](auto occ, auto pack) {
-        return launch_lds(st, gru16_train_kernel<FM, DG, occ(), pack()>, ls.grid, 64 * ls.waves, s16_lds_bytes(P, ls.waves), a);
+        return s16_loss_dispatch(a, [&](auto l2) {
+            return launch_lds(st, gru16_train_kernel<FM, DG, occ(), pack(), true, false, l2()>, ls.grid, 64 * ls.waves, s16_lds_bytes(P, ls.waves), a);
+        });
     });
 }
 // frozen PA of a cascade: forward + loss + dL/du in one launch (a.x = u, a.target, a.dx = du, a.partials = loss rows)
@@ -897,7 +954,9 @@ static int launch_s16_lossdx_occ(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = s16_shape(a.ngroups);
     const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16GroupsDx) + (size_t)ls.waves * (3 * 2 * 16 * kChunkPad + kStageRowFloats)) * sizeof(float);
     return s16_occ_dispatch<FM>(a, [&](auto occ, auto pack) {
-        return launch_lds(st, gru16_train_kernel<FM, DG, occ(), pack(), false, true>, ls.grid, 64 * ls.waves, lds, a);
+        return s16_loss_dispatch(a, [&](auto l2) {
+            return launch_lds(st, gru16_train_kernel<FM, DG, occ(), pack(), false, true, l2()>, ls.grid, 64 * ls.waves, lds, a);
+        });
     });
 }
 
@@ -931,7 +990,7 @@ int gru_s16_bwd_rows(const odpd_model_t* m, int B) {
 template <int FM, bool DG>
 static int launch_s16_fwd(hipStream_t st, const SeqArgs& a, int P) {
     const LaunchShape ls = s16_fwd_shape(a.ngroups);
-    const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16Groups) + (size_t)ls.waves * 2 * 2 * 16 * kChunkPad) * sizeof(float);
+    const size_t lds = ((size_t)pad4(P) + s16_tab_floats(kS16Groups) + (size_t)ls.waves * kS16FwdWaveFloats) * sizeof(float);
     auto launch = [&](auto k) { return launch_lds(st, k, ls.grid, 64 * ls.waves, lds, a); };
     if constexpr (S16Cfg<FM>::NCH == 2) { if (a.H <= 13) return launch(gru16_fwd_kernel<FM, DG, true>); }   // K-packing
     return launch(gru16_fwd_kernel<FM, DG, false>);
@@ -942,7 +1001,7 @@ static int launch_s16_bwd(hipStream_t st, const SeqArgs& a, int P) {
     LaunchShape ls = s16_bwd_shape(a.ngroups, NW, DX);
     if (NW) ls.grid = s16_bwd_shape(a.ngroups, true, false).grid;
     const int waves = ls.waves < WAVES ? ls.waves : WAVES;
-    const int wave_floats = (DX ? 3 : 2) * 2 * 16 * kChunkPad + (NW ? kS16Tiles * kTileFloats : 0);
+    const int wave_floats = s16_bwd_wave_floats(NW, DX);
     size_t lds = ((size_t)pad4(P) + s16_tab_floats(DX ? kS16GroupsDx : kS16Groups) + (size_t)waves * wave_floats) * sizeof(float);
     if (NW && lds < reduce_scratch_bytes(P, waves)) lds = reduce_scratch_bytes(P, waves);
     auto launch = [&](auto k) { return launch_lds(st, k, ls.grid, 64 * waves, lds, a); };
@@ -987,7 +1046,10 @@ template <int FM, bool DG>
 static int launch_s16_sweep_occ(hipStream_t st, const SeqArgs& a, int P, const SweepRun* runs, int K, long long first) {
     const LaunchShape ls = s16_shape(a.ngroups);
     return s16_occ_dispatch<FM>(a, [&](auto occ, auto pack) {
-        return launch_lds(st, gru16_train_sweep_kernel<FM, DG, occ(), pack()>, ls.grid * K, 64 * ls.waves, s16_lds_bytes(P, ls.waves), a, runs, ls.grid, first);
+        return s16_loss_dispatch(a, [&](auto l2) {
+            return launch_lds(st, gru16_train_sweep_kernel<FM, DG, occ(), pack(), l2()>, ls.grid * K, 64 * ls.waves, s16_lds_bytes(P, ls.waves), a, runs,
+                              ls.grid, first);
+        });
     });
 }
 bool gru_s16_sweep_ok(const odpd_model_t* m) {
@@ -999,6 +1061,7 @@ int gru_s16_sweep_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0
     if (!gru_cfg(m, FM, DG) || !gru_s16_sweep_ok(m) || K <= 0 || !runs) return ODPD_EUNSUPPORTED;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
+    a.nck = s16_train_nck(a.T);
     const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_sweep_occ<fm(), dg()>(st, a, P, runs, K, first); });
 }
@@ -1009,6 +1072,7 @@ int gru_s16_train(hipStream_t st, const odpd_model_t* m, const SeqArgs& a0) {
     if (!a0.ckpt) return ODPD_EINVAL;
     SeqArgs a = a0;
     a.ngroups = gru_s16_groups(a.B);
+    a.nck = s16_train_nck(a.T);
     const int P = gru_param_count(m->hidden, FM, DG);
     return s16_feat_dispatch(FM, [&](auto fm, auto dg) { return launch_s16_occ<fm(), dg()>(st, a, P); });
 }

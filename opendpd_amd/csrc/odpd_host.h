@@ -420,7 +420,8 @@ int launch_clip_adamw(hipStream_t st, int64_t P, float* params, float* grad, flo
 int launch_clip_optim(hipStream_t st, int kind, int64_t P, float* params, float* grad, float* state1, float* state2, int64_t step, double lr,
                       double max_norm, float* norm_out, float* loss_out, float inv_count, const unsigned char* skip = nullptr,
                       const XchgDev* xchg = nullptr);
-int64_t gru_s16_ckpt_floats(const odpd_model_t* m, int B, int T);      // [16-sequence task][ckpt][64 lanes][4]: the split calls' checkpoints and the fused steps' workspace
+int64_t gru_s16_ckpt_floats(const odpd_model_t* m, int B, int T);      // [16-sequence task][ckpt][64 lanes][4]: the split calls' checkpoints, the frozen loss step's workspace
+int64_t gru_s16_train_ws_floats(const odpd_model_t* m, int B, int T);  // the same records at the fused train step's own block length: its workspace, and a sweep run's
 // fused train step of the delta backbones at the reference's batch sizes (delta_family.hip: delta_gp_bwd_kernel<.., FUSED>)
 int delta_gp_train(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);
 int lstm_family_fwd(hipStream_t s, const odpd_model_t* m, const SeqArgs& a);

@@ -201,6 +201,13 @@ __device__ __forceinline__ void s16_loss(const S16Loss& L, float d0, float d1, f
     acc = __builtin_fmaf(L.w2, __builtin_fmaf(d0, d0, d1 * d1), acc);
     acc = __builtin_fmaf(L.w1, __builtin_fabsf(d0) + __builtin_fabsf(d1), acc);
 }
+// The L2 kind known at compile time (the fused blocks of gru_s16.hip): the two L1 terms above are c1 = w1 = 0 there, i.e. `+ 0 * sign(d)` under
+// the first rounding of each FMA and `+ 0 * (|d0| + |d1|)` on a sum that is never -0 — dropping them leaves every bit as it was.
+__device__ __forceinline__ void s16_loss_l2(const S16Loss& L, float d0, float d1, float& dy0, float& dy1, float& acc) {
+    dy0 = L.c2 * d0;
+    dy1 = L.c2 * d1;
+    acc = __builtin_fmaf(L.w2, __builtin_fmaf(d0, d0, d1 * d1), acc);
+}
 // relu'(v) as a multiplier: 0 for v <= 0, 1 for v >= 2^-100 (v_mul with the clamp modifier instead of v_cmp + v_cndmask)
 __device__ __forceinline__ float relu_gate(float v) { return __builtin_amdgcn_fmed3f(v * 0x1p100f, 0.0f, 1.0f); }
 

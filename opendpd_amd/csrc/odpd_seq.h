@@ -71,8 +71,8 @@ __device__ __forceinline__ float2 ld_iq(const float* g, size_t i, bool bf16) {
 // `fidx` (nullable): frames are windows of a resident stream, row b starts at sample fidx[b] * fstride; `bf16`: its sample format
 // BATCHED: the loads of one call in two passes (see below) — 2 N more live registers at the call site.  The element-at-a-time form exposes 2 N
 // dependent round trips per call, and a partner wave does NOT cover them where the waves of a SIMD run the same work in lockstep and reach every
-// chunk boundary together: the fused train kernel of gru_s16.hip stages through stage_rows / stage_issue / stage_commit below instead
-// (profiles/staging.md); the split kernels and the other families still call this form
+// chunk boundary together: the kernels of gru_s16.hip — the fused train body and the split forward / backward — stage through stage_rows /
+// stage_issue / stage_commit below instead (profiles/staging.md, profiles/s16_blocks.md); the other families still call this form
 template <int SPW, bool BATCHED = false>
 __device__ __forceinline__ void stage_in(float2* lds, const float* g, int b0, int B, int T, int t0, int len, int lane,
                                          float2 fill, const long long* fidx = nullptr, int fstride = 0, bool bf16 = false) {
@@ -136,7 +136,8 @@ __device__ __forceinline__ void stage_in(float2* lds, const float* g, int b0, in
     }
 }
 // -------------------------------------------------------------------------------------------------
-// The same staging in three parts, for a kernel that stages many chunks of the same 16 rows (gru16_train_body: 21 calls per group at T = 200):
+// The same staging in three parts, for a kernel that stages many chunks of the same 16 rows (gru16_train_body: 21 calls per group at T = 200;
+// gru16_fwd_kernel / gru16_bwd_kernel: 7 each, rows of a (B, T, 2) tensor):
 //   stage_rows    once per group: the sample offset of each row's first step into a 128-byte LDS slot of the wave — no frame-index load per chunk
 //   stage_issue   the N loads of every stream of a chunk back to back into registers, nothing waited for (x and the target of a backward chunk
 //                 are ONE batch: one wait for 2 N loads)
