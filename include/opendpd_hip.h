@@ -471,6 +471,20 @@ int odpd_train_epoch_dp(void* stream, void* comm, const odpd_model_t* m, int los
                         double beta2, double eps, double weight_decay, double max_norm, float* partials, float* workspace,
                         float* losses_out);
 
+/* ---- closed-form fit of gmp (csrc/gmp_ls.hip) ---------------------------------------------------------------------------------
+ * gmp is linear in its 495 real weights (backbones/gmp.py:41-48), so its L2 optimum is one symmetric solve.  For sequences x, target
+ * (B, T, 2) fp32, each with the reference's zero history, let A be the real design matrix of 2 B T rows (real part, imaginary part of
+ * every output sample) and 496 columns: column j < 495 the complex basis term that multiplies Weight[0, j] in the reference's own order
+ * (first the 11 u[t+m], then (d, i, m) d-major), column 495 the target.  The call writes G = A^T A as a full symmetric row-major
+ * 496 x 496 array of doubles: G[:495, :495] the normal matrix, G[:495, 495] the right-hand side, G[495, 495] = sum |target|^2.
+ * The basis is formed in fp64 from the fp32 samples inside the kernel and accumulated on the fp64 matrix pipe; partial sums of sample
+ * slices go to `workspace` (device, that many bytes per the size query, for the same B and T) and are added in a fixed order: no
+ * atomics, two calls give the same bits.  `m` must be the float gmp descriptor (hidden 11, bits_w = bits_a = 0, flags = 0), anything
+ * else answers ODPD_EUNSUPPORTED; null pointers or B, T <= 0 answer ODPD_EINVAL. */
+int64_t odpd_gmp_gram_workspace_bytes(const odpd_model_t* m, int B, int T);
+int odpd_gmp_gram(void* stream, const odpd_model_t* m, const float* x, const float* target, int B, int T, double* gram /* 496 * 496 */,
+                  void* workspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,8 @@ _EXPORTS = {
                                                     C.c_double, C.c_double, C.c_void_p]),
     "odpd_clip_optim_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "odpd_gmp_gram_workspace_bytes": (C.c_int64, [C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "odpd_gmp_gram": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 OPTIMIZER_IDS = {"adamw": 0, "adam": 1, "sgd": 2, "rmsprop": 3}      # enum odpd_optimizer
 

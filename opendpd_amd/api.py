@@ -6,7 +6,7 @@ import os
 import pandas as pd
 
 from . import data as D
-from .project import Project, run_run_dpd, run_train_dpd, run_train_pa
+from .project import Project, _fit_project, run_fit_dpd, run_fit_pa, run_run_dpd, run_train_dpd, run_train_pa
 
 
 def _need_name(fn, dataset_name, dataset_path):
@@ -123,3 +123,25 @@ class OpenDPDTrainer:
         if not self.dpd_trained:
             raise RuntimeError("DPD model not trained yet. Call train_dpd() first.")
         return run_dpd(**self._config(kwargs))
+
+
+def fit_pa(dataset_name=None, dataset_path=None, ridge=1e-6, seed=0, frame_length=50, accelerator="cuda", **kwargs):
+    """The gmp PA model in closed form (opendpd_amd/fit.py): the ridge least-squares optimum of the loss `train_pa(PA_backbone="gmp")`
+    descends, fitted on the training stream as one sequence and written where that call writes its model and logs — a following
+    `train_dpd(PA_backbone="gmp", PA_hidden_size=11, frame_length=...)` loads it.  One log row: EPOCH 0, N_EPOCH 1, TRAIN_LOSS = the
+    fitted stream's MSE.  `ridge` is relative to the largest eigenvalue of the normal matrix."""
+    _need_name("fit_pa", dataset_name, dataset_path)
+    proj = _fit_project("train_pa", ridge, dict(dataset_name=dataset_name, seed=seed, frame_length=frame_length, accelerator=accelerator, **kwargs))
+    run_fit_pa(proj, ridge)
+    return {"status": "completed", "model_path": proj.path_save_file_best, "log_path": proj.path_log_file_best}
+
+
+def fit_dpd(dataset_name=None, dataset_path=None, ridge=1e-6, seed=0, frame_length=50, accelerator="cuda", **kwargs):
+    """The one-shot indirect-learning gmp predistorter: the same fit with input y_train / target_gain and target x_train, saved as the
+    model `train_dpd(DPD_backbone="gmp", DPD_hidden_size=11, ...)` would save (the PA_* arguments and frame_length name its directory), so
+    that `run_dpd(DPD_backbone="gmp", DPD_hidden_size=11, ...)` loads it.  The log row holds the inverse model's own metrics on the
+    swapped splits; one-shot indirect learning carries no guarantee on the cascade."""
+    _need_name("fit_dpd", dataset_name, dataset_path)
+    proj = _fit_project("train_dpd", ridge, dict(dataset_name=dataset_name, seed=seed, frame_length=frame_length, accelerator=accelerator, **kwargs))
+    run_fit_dpd(proj, ridge)
+    return {"status": "completed", "model_path": proj.path_save_file_best, "log_path": proj.path_log_file_best}

@@ -407,3 +407,60 @@ def run_run_dpd(proj):
     out_path = os.path.join(out_dir, dpd_id + ".csv")
     pd.DataFrame({"I": X_test[:, 0], "Q": X_test[:, 1], "I_dpd": out[:, 0], "Q_dpd": out[:, 1]}).to_csv(out_path, index=False)
     return out_path
+
+
+class _NoOptimizer:
+    """what the log row reads from an optimiser, for a model that was fitted in closed form"""
+    param_groups = [{"lr": 0.0}]
+
+
+def _fit_and_log(proj, dpd_step, x_train, y_train, val_loader, test_loader, ridge):
+    """the shared body of run_fit_pa / run_fit_dpd: fit target ~ gmp(x) on the training stream as ONE sequence, evaluate the splits the
+    way an epoch does (net_eval, calculate_metrics), write the one log row and the model where the epoch loop would"""
+    from types import SimpleNamespace
+    from .fit import fit_gmp
+    start = time.time()
+    net = CoreModel(2, 11, 1, "gmp").to(proj.device)
+    model_id = proj.gen_dpd_model_id(count_net_params(net)) if dpd_step else proj.gen_pa_model_id(count_net_params(net))
+    proj.build_logger(model_id)
+    as_seq = lambda s: (s if isinstance(s, torch.Tensor) else torch.as_tensor(np.asarray(s))).to(proj.device, torch.float32).reshape(1, -1, 2)
+    fit_gmp(as_seq(x_train), as_seq(y_train), ridge=ridge, net=net)
+    proj.log_train["loss"] = float(net.gmp_fit["residual"]) / (2.0 * net.gmp_fit["n_samples"])      # nn.MSELoss over the (N, 2) stream
+    criterion = proj.build_criterion()
+    for on, log, loader in ((proj.eval_val, proj.log_val, val_loader), (proj.eval_test, proj.log_test, test_loader)):
+        if on:
+            _, pred, truth = net_eval(log, net, loader, criterion, proj.device)
+            calculate_metrics(proj.args, log, pred, truth)
+    holder = SimpleNamespace(dpd_model=net, parameters=net.parameters) if dpd_step else net
+    proj.finish_epoch(holder, _NoOptimizer(), None, 0, start, "NMSE")
+    return net
+
+
+def _fit_project(step, ridge, overrides):
+    if not ridge >= 0.0:
+        raise ValueError(f"ridge={ridge!r}: expected a number >= 0")
+    fixed = dict(PA_backbone="gmp", PA_hidden_size=11) if step == "train_pa" else dict(DPD_backbone="gmp", DPD_hidden_size=11)
+    clash = {k: v for k, v in overrides.items() if k in fixed and v != fixed[k]}
+    if clash:
+        raise ValueError(f"the closed-form fit is gmp's (memory_length 11): {clash} cannot be fitted this way")
+    hp = dict(overrides, step=step, n_epochs=1, **fixed)
+    hp.setdefault("batch_size", 1)      # the training stream is one sequence
+    return Project(**hp)
+
+
+def run_fit_pa(proj, ridge=1e-6):
+    """train_pa's result for PA_backbone gmp without the epoch loop: the ridge least-squares optimum of its L2 loss (opendpd_amd/fit.py)"""
+    proj.set_device()
+    (train, val, test), _ = proj.build_dataloaders()
+    return _fit_and_log(proj, False, train.x.float(), train.y.float(), val, test, ridge)
+
+
+def run_fit_dpd(proj, ridge=1e-6):
+    """The classical one-shot indirect-learning predistorter: the gmp post-inverse of the measured PA, x ~ gmp(y / target_gain), saved as
+    a train_dpd model.  The logged metrics are those of the inverse model on the swapped, gain-scaled splits (no PA model is involved)."""
+    proj.set_device()
+    Xtr, ytr, Xv, yv, Xte, yte = D.load_dataset(proj.dataset_name, proj.dataset_path)
+    g = proj.target_gain = D.set_target_gain(Xtr, ytr)
+    val = DataLoader(D.IQSegmentDataset(yv / g, Xv, nperseg=proj.args.nperseg), batch_size=proj.batch_size_eval, shuffle=False)
+    test = DataLoader(D.IQSegmentDataset(yte / g, Xte, nperseg=proj.args.nperseg), batch_size=proj.batch_size_eval, shuffle=False)
+    return _fit_and_log(proj, True, ytr / g, Xtr, val, test, ridge)
