@@ -8,6 +8,9 @@ reference  on the cases of every converted test_against_oracle_ragged — its ow
            the GPU at GRAD_TOL is 16x beyond what the reference's own rounding does to that block.  Observed maxima (docs/design/
            numerics.md): 6.7e-6 on the gru / lstm / janet / tcnn / delta / wide grids, 1.4e-5 on deltajanet's one-element weight_hh gate
            at H = 1 and on mcldnn, eight of whose cases draw their input from another seed for this condition (RAGGED_RESEEDED there);
+tcnn edges on the grid of tests/test_tcnn_edges_gpu.py (its own builder, every draw from the CPU generators; 8200 x 3 in place of the batches
+           it derives from the device's CU count) the fp32 oracle's y, flat gradient, every tensor and dL/dx stay within 2e-6 / 2e-5 / 2e-5 /
+           2e-6 of the fp64 oracle's; observed 2.4e-7 / 4.3e-6 / 7.2e-6 / 1.8e-7;
 bite       four faults planted in the oracle's gradient that the flat rel_err lets through at the family's GRAD_TOL fail by block; a block
            whose reference is identically zero stays on the flat scale."""
 import functools
@@ -23,6 +26,7 @@ from tests import test_gru_wide_gpu as WIDE
 from tests import test_janet_tcnn_gpu as JANET
 from tests import test_lstm_family_gpu as LSTM
 from tests import test_mcldnn_gpu as MCLDNN
+from tests import test_tcnn_edges_gpu as TCNN_EDGES
 from tests.golden_util import assert_grad_blocks, grad_block_errors, grad_blocks, net_grad_blocks, rel_err
 
 GATES = {"gru": 3, "dgru": 3, "qgru": 3, "qgru_amp1": 3, "deltagru": 3, "deltagru_tcnskip": 3, "lstm": 4, "vdlstm": 4, "deltajanet": 2}
@@ -110,6 +114,33 @@ def test_fp32_oracle_earns_the_tolerance_block_by_block(tol, bb, H, thx, thh, ca
     assert g32.size == net_grad_blocks(net)[-1][2]
     worst = assert_grad_blocks(g32, g64, net_grad_blocks(net), tol / 16)
     print(f"fp32 oracle against fp64: flat {rel_err(g32, g64):.2e}, worst block {worst}")
+
+
+# the grid of tests/test_tcnn_edges_gpu.py; the batches that module derives from the device's CU count are stood in for by 8200 x 3
+TCNN_EDGE_CASES = TCNN_EDGES.grid_cases() + [(bb, Cw, 8200, 3) for bb in TCNN_EDGES.WIDTHS for Cw in TCNN_EDGES.REGIME_WIDTHS]
+
+
+@pytest.mark.parametrize("bb,Cw,B,T", TCNN_EDGE_CASES, ids=["-".join(str(v) for v in c) for c in TCNN_EDGE_CASES])
+def test_fp32_oracle_stays_at_rounding_level_on_the_tcnn_edge_grid(bb, Cw, B, T):
+    """the inputs of the tcnn / neuraltx edge grid are well conditioned: the fp32 oracle stays within 2e-6 (y), 2e-5 (flat gradient), 2e-5
+    (every tensor on its own maximum) and 2e-6 (dL/dx) of the fp64 one, 10 to 150 times below the bounds the kernels are held to there"""
+    from oracle.oracle import Oracle, make_model
+    net, x, dy = TCNN_EDGES.edge_case(bb, Cw, B, T, device="cpu")
+    assert float(np.min(np.hypot(x[..., 0], x[..., 1]))) > 0.049      # no sample at the origin, where the reference divides by zero
+    m, p = make_model(bb, Cw), _flat(net)
+    o32, o64 = Oracle("f32"), Oracle("f64")
+    threads = o32.max_threads()
+    o32.set_threads(1)      # (as _oracle_grads: the serial sum is the same on every machine)
+    try:
+        y32, _ = o32.forward(m, p, x)
+        g32, dx32 = o32.backward(m, p, x, dy, need_dx=True)
+        y64, _ = o64.forward(m, p.astype(np.float64), x.astype(np.float64))
+        g64, dx64 = o64.backward(m, p.astype(np.float64), x.astype(np.float64), dy.astype(np.float64), need_dx=True)
+    finally:
+        o32.set_threads(threads)
+    worst = assert_grad_blocks(g32, g64, net_grad_blocks(net), 2e-5, exact_zeros=True)
+    print(f"fp32 oracle against fp64: y {rel_err(y32, y64):.2e}, flat {rel_err(g32, g64):.2e}, worst tensor {worst}, dL/dx {rel_err(dx32, dx64):.2e}")
+    assert rel_err(y32, y64) < 2e-6 and rel_err(dx32, dx64) < 2e-6
 
 
 # (family file, its ragged case, the faulty tensor, its gate or None, factor): pass the flat assertion, fail by block.  (gru's z gate is
