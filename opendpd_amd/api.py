@@ -6,7 +6,8 @@ import os
 import pandas as pd
 
 from . import data as D
-from .project import Project, _fit_project, run_fit_dpd, run_fit_pa, run_run_dpd, run_train_dpd, run_train_pa
+from .project import (Project, _direct_project, _fit_project, run_fit_dpd, run_fit_dpd_direct, run_fit_pa, run_run_dpd, run_train_dpd,
+                      run_train_pa)
 
 
 def _need_name(fn, dataset_name, dataset_path):
@@ -144,4 +145,23 @@ def fit_dpd(dataset_name=None, dataset_path=None, ridge=1e-6, seed=0, frame_leng
     _need_name("fit_dpd", dataset_name, dataset_path)
     proj = _fit_project("train_dpd", ridge, dict(dataset_name=dataset_name, seed=seed, frame_length=frame_length, accelerator=accelerator, **kwargs))
     run_fit_dpd(proj, ridge)
+    return {"status": "completed", "model_path": proj.path_save_file_best, "log_path": proj.path_log_file_best}
+
+
+def fit_dpd_direct(dataset_name=None, dataset_path=None, iterations=8, ridge=1e-6, start="ila", seed=0, frame_length=200,
+                   accelerator="cuda", PA_backbone="gru", PA_hidden_size=23, **kwargs):
+    """The gmp predistorter by direct learning: lowers the loss `train_dpd(DPD_backbone="gmp")` descends, mean((PA(DPD(x)) - gain x)^2)
+    through the frozen PA model of `save/<dataset>/train_pa/` (any backbone; built and loaded as train_dpd does), by at most `iterations`
+    preconditioned gradient steps with a line search (opendpd_amd/fit.py: refine_gmp_dpd) instead of epochs.  x is the training input cut
+    into non-overlapping frames of `frame_length` samples, each with zero history; the samples after the last whole frame are dropped.
+    `start`: "ila" (the one-shot indirect fit of fit_dpd on the same frames), "identity" (DPD(x) = x) or the path of a saved gmp train_dpd
+    model.  Model and logs go where `train_dpd(DPD_backbone="gmp", DPD_hidden_size=11, ...)` puts them, so `run_dpd` loads the result: row
+    0 of the history is the start, then one row per accepted step (EPOCH = k, TRAIN_LOSS = the loss on the frames, the cascade's validation
+    and test metrics); the saved model is the row with the best VAL_ACLR_AVG.  `ridge` is relative to the largest eigenvalue of the
+    normal matrix of the DPD's basis."""
+    _need_name("fit_dpd_direct", dataset_name, dataset_path)
+    proj = _direct_project(iterations, ridge, start, dict(dataset_name=dataset_name, seed=seed, frame_length=frame_length,
+                                                         accelerator=accelerator, PA_backbone=PA_backbone, PA_hidden_size=PA_hidden_size,
+                                                         **kwargs))
+    run_fit_dpd_direct(proj, iterations=iterations, ridge=ridge, start=start)
     return {"status": "completed", "model_path": proj.path_save_file_best, "log_path": proj.path_log_file_best}

@@ -436,14 +436,14 @@ def _fit_and_log(proj, dpd_step, x_train, y_train, val_loader, test_loader, ridg
     return net
 
 
-def _fit_project(step, ridge, overrides):
+def _fit_project(step, ridge, overrides, n_epochs=1):
     if not ridge >= 0.0:
         raise ValueError(f"ridge={ridge!r}: expected a number >= 0")
     fixed = dict(PA_backbone="gmp", PA_hidden_size=11) if step == "train_pa" else dict(DPD_backbone="gmp", DPD_hidden_size=11)
     clash = {k: v for k, v in overrides.items() if k in fixed and v != fixed[k]}
     if clash:
         raise ValueError(f"the closed-form fit is gmp's (memory_length 11): {clash} cannot be fitted this way")
-    hp = dict(overrides, step=step, n_epochs=1, **fixed)
+    hp = dict(overrides, step=step, n_epochs=n_epochs, **fixed)
     hp.setdefault("batch_size", 1)      # the training stream is one sequence
     return Project(**hp)
 
@@ -464,3 +464,68 @@ def run_fit_dpd(proj, ridge=1e-6):
     val = DataLoader(D.IQSegmentDataset(yv / g, Xv, nperseg=proj.args.nperseg), batch_size=proj.batch_size_eval, shuffle=False)
     test = DataLoader(D.IQSegmentDataset(yte / g, Xte, nperseg=proj.args.nperseg), batch_size=proj.batch_size_eval, shuffle=False)
     return _fit_and_log(proj, True, ytr / g, Xtr, val, test, ridge)
+
+
+DIRECT_STARTS = ("ila", "identity")
+
+
+def _direct_project(iterations, ridge, start, overrides):
+    """the Project of fit_dpd_direct; every argument error is raised before a directory is made"""
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError(f"iterations={iterations!r}: expected a count >= 0")
+    if start not in DIRECT_STARTS and not os.path.isfile(str(start)):
+        raise ValueError(f"start={start!r}: expected 'ila', 'identity' or the path of a saved gmp train_dpd model")
+    return _fit_project("train_dpd", ridge, overrides, n_epochs=int(iterations) + 1)
+
+
+def run_fit_dpd_direct(proj, iterations=8, ridge=1e-6, start="ila", halvings=6, tol=1e-4):
+    """train_dpd's result for DPD_backbone gmp without the epoch loop: direct learning through the frozen PA model by preconditioned
+    gradient steps (opendpd_amd/fit.py: refine_gmp_dpd).  The PA is built and loaded as run_train_dpd does.  x is the training input cut
+    into non-overlapping frames of frame_length, each with zero history; the remainder of the stream is dropped.  Row 0 of the log is the
+    start, then one row per accepted step: EPOCH = k, TRAIN_LOSS = the cascade's loss on those frames, validation and test metrics of the
+    cascade as a train_dpd epoch computes them, best model by ACLR_AVG."""
+    from types import SimpleNamespace
+    from .fit import fit_gmp, refine_gmp_dpd
+    proj.set_device()
+    Xtr, ytr, Xv, yv, Xte, yte = D.load_dataset(proj.dataset_name, proj.dataset_path)
+    g = proj.target_gain = D.set_target_gain(Xtr, ytr)
+    val = DataLoader(D.IQSegmentDataset(Xv, g * Xv, nperseg=proj.args.nperseg), batch_size=proj.batch_size_eval, shuffle=False)
+    test = DataLoader(D.IQSegmentDataset(Xte, g * Xte, nperseg=proj.args.nperseg), batch_size=proj.batch_size_eval, shuffle=False)
+    pa = CoreModel(Xtr.shape[-1], proj.PA_hidden_size, proj.PA_num_layers, proj.PA_backbone, window_size=proj.window_size,
+                   num_dvr_units=proj.num_dvr_units)
+    pa_id = proj.gen_pa_model_id(count_net_params(pa))
+    pa.load_state_dict(torch.load(os.path.join("save", proj.dataset_label, "train_pa", pa_id + ".pt"), map_location="cpu"))
+    dpd = CoreModel(Xtr.shape[-1], proj.DPD_hidden_size, proj.DPD_num_layers, proj.DPD_backbone)
+    proj.build_logger(proj.gen_dpd_model_id(count_net_params(dpd)))
+    if start not in DIRECT_STARTS:
+        dpd.load_state_dict(torch.load(start, map_location="cpu"))
+    net = CascadedModel(dpd_model=dpd, pa_model=pa)
+    net.freeze_pa_model()
+    net = net.to(proj.device)
+    F = proj.frame_length
+    n_frames = len(Xtr) // F
+    if n_frames < 1:
+        raise ValueError(f"frame_length={F}: the training stream has {len(Xtr)} samples")
+    frames = lambda s: torch.as_tensor(np.asarray(s[:n_frames * F]), dtype=torch.float32).to(proj.device).reshape(n_frames, F, 2)
+    x = frames(Xtr)
+    proj.batch_size = proj.args.batch_size = n_frames      # the frames are one batch
+    if start == "ila":
+        fit_gmp(frames(ytr / g), x, ridge=ridge, net=dpd)
+    elif start == "identity":
+        with torch.no_grad():
+            dpd.backbone.Weight.zero_()
+            dpd.backbone.Weight[0, 10] = 1.0      # the undelayed sample (gmp.py:43: u[t + m], m = 10)
+    criterion = proj.build_criterion()
+    holder = SimpleNamespace(dpd_model=dpd, parameters=dpd.parameters)      # N_PARAM counts the predistorter, the model that is saved
+    t0 = time.time()
+
+    def log_row(k, w, loss):
+        proj.log_train["loss"] = float(loss)
+        for on, log, loader in ((proj.eval_val, proj.log_val, val), (proj.eval_test, proj.log_test, test)):
+            if on:
+                _, pred, truth = net_eval(log, net, loader, criterion, proj.device)
+                calculate_metrics(proj.args, log, pred, truth)
+        proj.finish_epoch(holder, _NoOptimizer(), None, k, t0, "ACLR_AVG")
+
+    refine_gmp_dpd(dpd, pa, x, g, iterations=iterations, ridge=ridge, halvings=halvings, tol=tol, accepted=log_row)
+    return net
